@@ -29,8 +29,13 @@ the resolved mode):
     layer for 1/N of a weight stream that takes ~1.7 ms whole - replicas are the throughput
     configuration; ``tp`` is the latency / memory configuration and stays selectable.
 
-TP pass (``--tp-pass``, default ``auto`` = on when N > 1): after the data-parallel headline is
-measured, every rank frees its engine and rank 0 runs ONE tensor-parallel pass over the same N
+A plain run (``--gpus 1 --steps K --warmup W``) does only what the headline needs: load, W warm-up
+rounds, the K timed rounds, the optional ``--dump-outputs``, the result line. Everything else this
+file measures or checks - the one-client serial run, the TP pass with its correctness gate - runs
+with ``--full`` (or when its own option asks for it explicitly).
+
+TP pass (``--tp-pass``, default ``auto`` = on with ``--full`` when N > 1): after the data-parallel
+headline is measured, every rank frees its engine and rank 0 runs ONE tensor-parallel pass over the same N
 GPUs in a fresh ``torch.distributed.run`` child (its own process group; the DP ranks wait at a
 gloo barrier and touch no GPU meanwhile), bounded by ``--tp-timeout`` seconds. Its result -
 tokens/s at C clients, p50, the serial rate, and which comm path each TP message takes with the
@@ -52,9 +57,28 @@ its error and never touches the DP headline.
 Load: ``--clients C`` concurrent clients (default 6 = the reference pod's admission
 capacity, 1 in flight + MAX_QUEUE_SIZE 5, reference api.py:19,113) post the K timed
 requests; the engine decodes up to ``--max-batch M`` (default = C) of them as rows of one
-continuous batch. After the timed run, ``--serial-steps`` requests from ONE client (the
-reference's one-generation-at-a-time serving) are timed as well and reported in
+continuous batch. With ``--full``, after the timed run ``--serial-steps`` requests from ONE client
+(the reference's one-generation-at-a-time serving) are timed as well and reported in
 ``config.serial`` (rank 0's GPU group, same engine).
+
+Reproducible inputs: the weights are seeded, request i is a fixed text, and every request's
+sampler seed is derived from the messages the engine receives (not from the order in which
+concurrent requests happen to reach it), so two runs with the same arguments feed the engine the
+same inputs.
+
+``--dump-outputs DIR`` (hip backend): what the engine computes from the last timed round's inputs,
+as arrays that two builds can be compared on. The responses themselves cannot serve: they are
+samples at temperature 1.2, and the engine's logits for one input differ between two processes of
+one build at f16-rounding level (~7e-4 of the largest logit: split-K partial sums meet in
+floating-point atomics, whose order varies), which flips a sampled token within some tens of steps
+and every later token with it. So after the timed steps the last round's prompts - the token ids
+the engine received - go once more through the kernels that served them, with the sampler's draw
+replaced by a fixed token: one joint prefill of the round's prompts (``slots_begin``), each followed
+by the token ``n_vocab // 2`` (forced by a logit bias under greedy sampling), and the batched decode
+step that feeds it (``batch_step``). Written: ``DIR/step_logits.npy`` (float32 [C, n_vocab]: that
+step's logits of row k = the round's k-th request) and ``DIR/prompt_tokens.npy`` (float32 [C]: the
+prompts' lengths). Without a continuous batch (``--max-batch 1``) the same is computed on the
+single-sequence path (``eval_logits``, ``decode_logits``). The replay is outside the timed region.
 
 Admission runs the production settings (the chart's): at most MAX_QUEUE_SIZE + 1 = 6 requests
 admitted at once (the reference pod's capacity, reference api.py:19,113), all six decoding as rows
@@ -70,6 +94,7 @@ import asyncio
 import datetime
 import json
 import os
+import re
 import signal
 import socket
 import statistics
@@ -77,6 +102,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -95,6 +121,7 @@ class CountingEngine:
         self.completion_tokens = []
         self.prompt_tokens = []
         self.decode_s = []
+        self.chats = {}   # request id (make_request's i) -> the messages the engine received
 
     @property
     def batch_width(self):
@@ -104,6 +131,15 @@ class CountingEngine:
         return self.llm.n_ctx()
 
     def create_chat_completion(self, **kw):
+        # the sampler seed follows the request's content (and the engine's seed, which differs per
+        # data-parallel rank): the same request draws the same stream in every run, whichever of
+        # the concurrent requests reaches the engine first
+        if kw.get("seed") is None:
+            kw["seed"] = zlib.crc32(json.dumps(kw.get("messages"), sort_keys=True).encode(),
+                                    int(getattr(self.llm, "_seed", 0)) & 0xFFFFFFFF)
+        i = request_id_of(kw.get("messages"))
+        if i is not None:
+            self.chats[i] = kw["messages"]
         out = self.llm.create_chat_completion(**kw)
         self.completion_tokens.append(out["usage"]["completion_tokens"])
         self.prompt_tokens.append(out["usage"]["prompt_tokens"])
@@ -135,6 +171,70 @@ def make_request(i: int) -> dict:
             "user_profile": {"name": "bench"}, "context": ctx}
 
 
+def request_id_of(messages):
+    """The i of make_request(i) whose context these chat messages carry (None: not a bench request)."""
+    for m in messages or []:
+        hit = re.search(r"message (\d+)-\d+:", str(m.get("content", "")))
+        if hit:
+            return int(hit.group(1))
+    return None
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def replay_logits(llm, chats: list):
+    """--dump-outputs: the prompts of `chats` (tokenised as create_chat_completion does) through the
+    engine once more with the sampler's draw replaced by the fixed token n_vocab // 2 -
+    (logits [n, n_vocab] float32 of the decode step that feeds that token, prompt lengths [n])."""
+    import numpy as np
+    backend = getattr(llm, "_backend", None)
+    eng = getattr(backend, "engine", None)
+    if eng is None or not hasattr(eng, "decode_logits"):
+        raise SystemExit("bench.py: --dump-outputs needs the hip backend")
+    V = llm.n_vocab()
+    forced = V // 2
+    prompts = []
+    for messages in chats:
+        fr = llm._formatter(messages)
+        prompts.append(llm.tokenize(fr.prompt, add_bos=not fr.added_special, special=True))
+    n = min(len(prompts), DUMP_MAX_BYTES // (4 * V))
+    if getattr(backend, "sched", None) is not None:
+        # the continuous batch's path: one joint prefill, one batched step (the scheduler is idle:
+        # every request has returned, and the engine serialises callers anyway)
+        n = min(n, int(backend.max_batch))
+        # ... once its last pipelined step (queued before the final row's end was seen) is collected
+        seen, deadline = None, time.time() + 5.0
+        while time.time() < deadline:
+            st = backend.sched.stats()
+            if seen == st["steps"] and not st["active"] and not st["pending"]:
+                break
+            seen = st["steps"]
+            time.sleep(0.02)
+        slots = list(range(1, n + 1))
+        sp = {"temperature": 0.0, "top_k": 1, "repeat_penalty": 1.0, "logit_bias": {forced: 1e4}}
+        first = [int(t) for t in eng.slots_begin(slots, prompts[:n], [0] * n, [sp] * n)]
+        if first != [forced] * n:
+            raise RuntimeError(f"--dump-outputs: the logit bias did not force token {forced}: {first}")
+        eng.batch_step(slots)
+        logits = np.asarray(eng.batch_logits(n), np.float32).reshape(n, -1)[:, :V]
+    else:
+        rows = []
+        for prompt in prompts[:n]:
+            for pos in range(0, len(prompt), llm.n_batch):
+                eng.eval_logits(prompt[pos:pos + llm.n_batch], pos)
+            rows.append(np.asarray(eng.decode_logits(forced, len(prompt)), np.float32)[:V])
+        logits = np.stack(rows)
+    return logits, np.asarray([len(p) for p in prompts[:n]], np.float32)
+
+
+def dump_outputs(out_dir: str, logits, prompt_tokens) -> None:
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "step_logits.npy"), np.asarray(logits, np.float32))
+    np.save(os.path.join(out_dir, "prompt_tokens.npy"), np.asarray(prompt_tokens, np.float32))
+
+
 def _free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -152,6 +252,19 @@ def resolve_tp_model(args, world: int) -> str:
     if args.tp_model and args.tp_model != "auto":
         return args.tp_model
     return "llama3-70b-q4_k_m" if world >= 8 else args.model
+
+
+def resolve_tp_pass(args) -> bool:
+    """--tp-pass auto: part of --full, not of a plain run; on / off are explicit."""
+    return args.tp_pass == "on" or (args.tp_pass == "auto" and args.full)
+
+
+def resolve_serial_steps(args) -> int:
+    """Requests of the one-client serial run: an explicit --serial-steps, else max(2, steps // 4)
+    with --full and none in a plain run."""
+    if args.serial_steps >= 0:
+        return args.serial_steps
+    return max(2, args.steps // 4) if args.full else 0
 
 
 def tp_pass_cmd(args, world: int, json_out: str, check_ref: str = "") -> list:
@@ -348,11 +461,13 @@ def main() -> int:
     ap.add_argument("--clients", type=int, default=6, help="concurrent clients posting /response")
     ap.add_argument("--max-batch", type=int, default=0, help="continuous-batch rows (0 = --clients)")
     ap.add_argument("--serial-steps", type=int, default=-1,
-                    help="requests of the one-client serial run after the timed run (-1: max(2, steps // 4))")
+                    help="requests of the one-client serial run after the timed run "
+                         "(-1: max(2, steps // 4) with --full, else none)")
     ap.add_argument("--model-dir", default=os.environ.get("SYNTH_MODEL_DIR", os.path.join(
         os.environ.get("TMPDIR", "/tmp"), "llama_amd_models")))
     ap.add_argument("--tp-pass", choices=["auto", "on", "off"], default="auto",
-                    help="N > 1: a tensor-parallel pass over the same GPUs after the DP headline (config.tp)")
+                    help="N > 1: a tensor-parallel pass over the same GPUs after the DP headline (config.tp); "
+                         "auto: on with --full")
     ap.add_argument("--tp-model", default="auto",
                     help="model of the TP pass (auto: llama3-70b-q4_k_m at N >= 8, else --model)")
     ap.add_argument("--tp-check-ref", default="",
@@ -360,6 +475,11 @@ def main() -> int:
     ap.add_argument("--tp-steps", type=int, default=2, help="timed rounds of the TP pass")
     ap.add_argument("--tp-timeout", type=float, default=480.0, help="wall bound of the TP pass (s)")
     ap.add_argument("--json-out", default="", help="also write rank 0's JSON result to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the one-client serial run, the TP pass (N > 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="replay the last timed round's prompts with a fixed next token and write the logits of "
+                         "that decode step to DIR/step_logits.npy (and DIR/prompt_tokens.npy)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -378,7 +498,7 @@ def main() -> int:
 
     import torch
     import torch.distributed as dist
-    tp_pass = world > 1 and parallel == "dp" and args.tp_pass != "off"
+    tp_pass = world > 1 and parallel == "dp" and resolve_tp_pass(args)
     if world > 1:
         # control plane only (barriers, object broadcasts): the engine runs its own collectives.
         # (the DP ranks wait out rank 0's TP pass at a barrier: the timeout covers it)
@@ -442,7 +562,7 @@ def main() -> int:
     if args.clients > settings.admission_cap:
         settings.max_admitted = args.clients
     app = create_app(settings, engine=eng)
-    serial_steps = args.serial_steps if args.serial_steps >= 0 else max(2, args.steps // 4)
+    serial_steps = resolve_serial_steps(args)
 
     import httpx
 
@@ -492,6 +612,11 @@ def main() -> int:
                 return elapsed, n0, n1, time.perf_counter() - ts, sched
 
     elapsed, n0, n1, serial_s, sched = asyncio.run(run())
+    if args.dump_outputs and rank == 0:
+        # (under TP the followers still replay rank 0's engine commands: before close())
+        nc = max(1, args.clients)
+        last_round = range((args.steps - 1) * nc, args.steps * nc)
+        dump_outputs(args.dump_outputs, *replay_logits(llm, [eng.chats[i] for i in last_round]))
     llm.close()   # TP: publishes STOP, the followers' follow() returns
     del app, eng.llm
     toks = sum(eng.completion_tokens[n0:n1])
@@ -535,11 +660,6 @@ def main() -> int:
                        "requests": n1 - n0, "step": f"one round of {args.clients} concurrent /response requests",
                        "avg_prompt_tokens": round(ptoks / max(1, n1 - n0), 1),
                        "avg_output_tokens": round(toks / max(1, n1 - n0), 1),
-                       "serial": {"requests": serial_steps, "clients": 1,
-                                  "tokens_per_s": round(s_toks / serial_s, 2) if serial_steps else None,
-                                  "p50_response_ms": round(statistics.median(serial_lat) * 1e3, 1)
-                                  if serial_lat else None,
-                                  "scope": "rank 0's GPU group" if world > 1 else "whole job"},
                        "admission": {"max_queue_size": settings.max_queue_size,
                                      "admission_cap": settings.admission_cap, "max_batch": max_batch},
                        "bench_overrides": {"timeout_seconds": BENCH_TIMEOUT_S,
@@ -548,6 +668,11 @@ def main() -> int:
                                            "production": {"timeout_seconds": 25.0, "max_queue_size": 5,
                                                           "admission_cap": 6}}},
         }
+        if serial_steps > 0:
+            res["config"]["serial"] = {"requests": serial_steps, "clients": 1,
+                                       "tokens_per_s": round(s_toks / serial_s, 2),
+                                       "p50_response_ms": round(statistics.median(serial_lat) * 1e3, 1),
+                                       "scope": "rank 0's GPU group" if world > 1 else "whole job"}
         if sched:
             res["config"]["scheduler"] = sched
         if comm is not None:

@@ -80,6 +80,129 @@ def test_tp_model_follows_the_baseline_configs():
     assert "--tp-check-ref" not in bench.tp_pass_cmd(_args(), 2, "/o.json")
 
 
+def test_plain_run_leaves_the_extras_to_full():
+    """The serial run and the TP pass belong to --full (or to their own explicit option)."""
+    plain = argparse.Namespace(full=False, serial_steps=-1, steps=20, tp_pass="auto")
+    full = argparse.Namespace(full=True, serial_steps=-1, steps=20, tp_pass="auto")
+    assert bench.resolve_serial_steps(plain) == 0 and not bench.resolve_tp_pass(plain)
+    assert bench.resolve_serial_steps(full) == 5 and bench.resolve_tp_pass(full)
+    full.steps = 3
+    assert bench.resolve_serial_steps(full) == 2
+    plain.serial_steps, plain.tp_pass = 1, "on"
+    assert bench.resolve_serial_steps(plain) == 1 and bench.resolve_tp_pass(plain)
+    full.tp_pass = "off"
+    assert not bench.resolve_tp_pass(full)
+
+
+def test_request_seed_follows_the_request_not_the_arrival_order():
+    class Llm:
+        _seed = 1234
+
+        def __init__(self):
+            self.seeds = []
+
+        def create_chat_completion(self, **kw):
+            self.seeds.append(kw["seed"])
+            return {"usage": {"completion_tokens": 1, "prompt_tokens": 1}, "timings": {"decode_s": 0.0}}
+
+    a, b = bench.CountingEngine(Llm()), bench.CountingEngine(Llm())
+    m1, m2 = [{"role": "user", "content": "one"}], [{"role": "user", "content": "two"}]
+    a.create_chat_completion(messages=m1)
+    a.create_chat_completion(messages=m2)
+    b.create_chat_completion(messages=m2)
+    b.create_chat_completion(messages=m1)
+    assert a.llm.seeds == b.llm.seeds[::-1] and a.llm.seeds[0] != a.llm.seeds[1]
+    other = bench.CountingEngine(Llm())
+    other.llm._seed = 1235                      # another data-parallel rank draws another stream
+    other.create_chat_completion(messages=m1)
+    assert other.llm.seeds[0] != a.llm.seeds[0]
+    a.create_chat_completion(messages=m1, seed=7)   # an explicit seed is kept
+    assert a.llm.seeds[-1] == 7
+
+
+def test_request_id_is_read_from_the_messages():
+    req = bench.make_request(17)
+    chat = [{"role": "system", "content": "persona"}] + [{"role": m["turn"], "content": m["message"]}
+                                                          for m in req["context"]]
+    assert bench.request_id_of(chat) == 17
+    assert bench.request_id_of([{"role": "user", "content": "hello"}]) is None
+    eng = bench.CountingEngine(type("L", (), {"_seed": 1, "create_chat_completion": lambda self, **kw: {
+        "usage": {"completion_tokens": 1, "prompt_tokens": 1}, "timings": {"decode_s": 0.0}}})())
+    eng.create_chat_completion(messages=chat)
+    assert eng.chats == {17: chat}
+
+
+class _ReplayEngine:
+    """The engine calls of replay_logits: slots_begin honours the forcing logit bias, batch_logits
+    returns rows that name their prompt (padded past n_vocab, as the device buffer is)."""
+    V, PAD = 50, 14
+
+    def __init__(self):
+        self.calls = []
+
+    def decode_logits(self, tok, pos):
+        import numpy as np
+        self.calls.append(("decode", tok, pos))
+        return np.full(self.V, float(pos), np.float32)
+
+    def eval_logits(self, toks, pos):
+        self.calls.append(("eval", len(toks), pos))
+
+    def slots_begin(self, slots, prompts, keep, sps):
+        self.calls.append(("slots_begin", list(slots), [len(p) for p in prompts], list(keep)))
+        self.lens = [len(p) for p in prompts]
+        return [max(sp["logit_bias"], key=sp["logit_bias"].get) for sp in sps]
+
+    def batch_step(self, slots):
+        self.calls.append(("batch_step", list(slots)))
+        return [0] * len(slots)
+
+    def batch_logits(self, n):
+        import numpy as np
+        return np.repeat(np.asarray(self.lens[:n], np.float32)[:, None], self.V + self.PAD, axis=1)
+
+
+class _ReplayLlm:
+    n_batch = 4
+
+    def __init__(self, batched):
+        sched = type("S", (), {"stats": lambda self: {"steps": 3, "active": 0, "pending": 0}})() if batched else None
+        self._backend = type("B", (), {})()
+        self._backend.engine, self._backend.sched, self._backend.max_batch = _ReplayEngine(), sched, 2
+
+    def n_vocab(self):
+        return _ReplayEngine.V
+
+    def _formatter(self, messages):
+        return type("F", (), {"prompt": " ".join(m["content"] for m in messages), "added_special": True})()
+
+    def tokenize(self, text, add_bos, special):
+        return list(range(len(text.split())))
+
+
+def test_replay_and_dump(tmp_path):
+    """--dump-outputs: the last round's prompts, a fixed forced token, one batched step's logits
+    (rows beyond the continuous batch's width are left out); float32 files of fixed names."""
+    import numpy as np
+    chats = [[{"content": "a b c"}], [{"content": "a b c d e f"}], [{"content": "a"}]]
+    llm = _ReplayLlm(batched=True)
+    logits, lens = bench.replay_logits(llm, chats)
+    eng = llm._backend.engine
+    assert eng.calls == [("slots_begin", [1, 2], [3, 6], [0, 0]), ("batch_step", [1, 2])]
+    assert logits.shape == (2, 50) and logits.dtype == np.float32 and lens.tolist() == [3.0, 6.0]
+    assert (logits[0] == 3).all() and (logits[1] == 6).all()
+    # no continuous batch: the single-sequence path, prompts in n_batch pieces
+    llm = _ReplayLlm(batched=False)
+    logits, lens = bench.replay_logits(llm, chats[:2])
+    assert llm._backend.engine.calls == [("eval", 3, 0), ("decode", 25, 3),
+                                         ("eval", 4, 0), ("eval", 2, 4), ("decode", 25, 6)]
+    assert logits.shape == (2, 50) and (logits[1] == 6).all()
+    bench.dump_outputs(str(tmp_path / "d"), logits, lens)
+    got = np.load(tmp_path / "d" / "step_logits.npy")
+    assert got.dtype == np.float32 and (got == logits).all()
+    assert np.load(tmp_path / "d" / "prompt_tokens.npy").tolist() == [3.0, 6.0]
+
+
 class _FakeEngine:
     """eval_logits / decode_logits of a deterministic toy model (the next token's logits depend on
     the last token and the position); `bias` perturbs it like a TP engine's rounding or a bad shard."""

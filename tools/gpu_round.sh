@@ -53,20 +53,20 @@ for s in "$@"; do
     opsgpu) step opsgpu 600 $PYT tests/test_ops_gpu.py --timeout 120 ;;
     smoke) step smoke 300 python __graft_entry__.py smoke ;;
     # ---- benches
-    bench) step bench 900 python bench.py --steps 3 --warmup 1 ;;
-    bench20) step bench20 900 python bench.py --steps 20 --warmup 2 ;;
+    bench) step bench 900 python bench.py --steps 3 --warmup 1 --full ;;
+    bench20) step bench20 900 python bench.py --steps 20 --warmup 2 --full ;;
     serial) step serial 900 python bench.py --steps 10 --warmup 1 --clients 1 --max-batch 1 ;;
     benchtp2) step benchtp2 900 env LFK_BENCH_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --parallel tp --steps 6 --warmup 1 ;;
+                --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --parallel tp --steps 6 --warmup 1 --full ;;
     benchdp2) step benchdp2 900 env LFK_BENCH_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --parallel dp --steps 4 --warmup 1 ;;
+                --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --parallel dp --steps 4 --warmup 1 --full ;;
     bstep) step bstep 300 python tools/batch_bench.py --batches 1,6,8 --steps 48 ;;
     decode) step decode 600 python tools/decode_bench.py --gen 400 ;;
     decode70) step gen70 900 python tools/gen_model.py llama3-70b-q4_k_m
               step decode70 900 python tools/decode_bench.py --model llama3-70b-q4_k_m --steps 64 ;;
     mixtral) step genmx 900 python tools/gen_model.py mixtral-8x7b-q4_k_m
              step mixdec 600 python tools/decode_bench.py --model mixtral-8x7b-q4_k_m --steps 64
-             step mixtral 900 python bench.py --model mixtral-8x7b-q4_k_m --steps 2 --warmup 1 ;;
+             step mixtral 900 python bench.py --model mixtral-8x7b-q4_k_m --steps 2 --warmup 1 --full ;;
     mixprof) export TMPDIR=/tmp; step genmx 900 python tools/gen_model.py mixtral-8x7b-q4_k_m
              prof mixprof 300 tools/decode_bench.py --model mixtral-8x7b-q4_k_m --steps 32 --no-graph
              python3 tools/prof_summary.py gpurun_out/mixprof/k_kernel_stats.csv > gpurun_out/mixprof_summary.md
