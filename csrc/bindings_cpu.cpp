@@ -5,6 +5,7 @@
 #include <pybind11/stl.h>
 
 #include "bind_scheduler.h"
+#include "common.h"
 #include "cpu/cpu_backend.h"
 #include "runtime/repack.h"
 #include "runtime/tp_channel.h"
@@ -243,6 +244,15 @@ PYBIND11_MODULE(_cpu, m) {
     return cpu_sample(l, window, parse_sampling(sp), step);
   });
   m.def("uniform", &splitmix_uniform);
+
+  // the load-time planar repack (runtime/repack.cpp), as the HIP module exposes it (tests)
+  m.def("repack", [](int type, py::array_t<uint8_t, py::array::c_style> src, size_t K_src, size_t r0, size_t R,
+                     size_t c0, size_t K, size_t R_dst, int G, int off) {
+    py::array_t<uint8_t> dst(qbytes(type, R_dst, K));
+    std::memset(dst.mutable_data(), 0, dst.size());
+    repack_planar(type, src.data(), K_src, r0, R, c0, K, dst.mutable_data(), R_dst, G, off);
+    return dst;
+  });
 
   py::class_<FakeSlotEngine>(m, "FakeSlotEngine")
       .def(py::init<int, int, int, int, int>(), py::arg("n_slots"), py::arg("max_batch"), py::arg("n_ctx"),

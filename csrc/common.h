@@ -10,6 +10,12 @@
 //   Q5_K : qs[R][K/256][128] | qh[R][K/256][32] | meta[R][K/256][16]
 //   Q6_K : ql[R][K/256][128] | qh[R][K/256][64] | sc[R][K/256][16] | d[R][K/256] (f16)
 //   Q8_0 : qs[R][K/32][32]   | d[R][K/32] (f16)
+//   Q4_0 : qs[R][K/32][16]   | d[R][K/32] (f16)
+//   Q4_1 : qs[R][K/32][16]   | dm[R][K/32][2] (f16 d, m)
+//   Q5_0 : qs[R][K/32][16]   | qh[R][K/32] (u32) | d[R][K/32] (f16)
+//   Q5_1 : qs[R][K/32][16]   | qh[R][K/32] (u32) | dm[R][K/32][2] (f16 d, m)
+//          (legacy 32-weight blocks: byte j of a block's qs holds weight j in its low
+//           nibble and weight j + 16 in its high nibble; bit j of qh is weight j's 5th bit)
 //   F16 / F32 : [R][K] unchanged
 //
 // Total bytes are identical to the GGUF tensor (no padding), so 4.6 GB of
@@ -25,6 +31,10 @@ namespace lfk {
 enum QType : int {
   T_F32 = 0,
   T_F16 = 1,
+  T_Q4_0 = 2,
+  T_Q4_1 = 3,
+  T_Q5_0 = 6,
+  T_Q5_1 = 7,
   T_Q8_0 = 8,
   T_Q4_K = 12,
   T_Q5_K = 13,
@@ -42,12 +52,27 @@ inline TypeInfo type_info(int t) {
     case T_F32: return {1, 4};
     case T_F16: return {1, 2};
     case T_BF16: return {1, 2};
+    case T_Q4_0: return {32, 18};
+    case T_Q4_1: return {32, 20};
+    case T_Q5_0: return {32, 22};
+    case T_Q5_1: return {32, 24};
     case T_Q8_0: return {32, 34};
     case T_Q4_K: return {256, 144};
     case T_Q5_K: return {256, 176};
     case T_Q6_K: return {256, 210};
   }
   throw std::runtime_error("unsupported ggml type " + std::to_string(t));
+}
+
+inline bool is_legacy_block_type(int t) { return t == T_Q4_0 || t == T_Q4_1 || t == T_Q5_0 || t == T_Q5_1; }
+
+// MoE expert tensors of the legacy 32-weight block types are not supported (attention, router
+// and embeddings of such a file are): refuse the model at load, naming the tensor.
+inline void check_expert_type(const std::string& tensor, int t) {
+  if (!is_legacy_block_type(t)) return;
+  const char* n = t == T_Q4_0 ? "Q4_0" : t == T_Q4_1 ? "Q4_1" : t == T_Q5_0 ? "Q5_0" : "Q5_1";
+  throw std::runtime_error("unsupported expert tensor " + tensor + ": type " + n +
+                           " (MoE experts must be Q4_K, Q5_K, Q6_K, Q8_0, F16 or F32)");
 }
 
 inline size_t qbytes(int t, size_t rows, size_t K) {
@@ -86,6 +111,14 @@ LFK_HD Planes planes_of(int t, size_t R, size_t K) {
     case T_Q8_0:
       p.s0 = nb * 32; p.s1 = nb * 2;
       p.p0 = 0; p.p1 = R * p.s0;
+      break;
+    case T_Q4_0: case T_Q4_1:
+      p.s0 = nb * 16; p.s1 = nb * (t == T_Q4_0 ? 2 : 4);
+      p.p0 = 0; p.p1 = R * p.s0;
+      break;
+    case T_Q5_0: case T_Q5_1:
+      p.s0 = nb * 16; p.s1 = nb * 4; p.s2 = nb * (t == T_Q5_0 ? 2 : 4);
+      p.p0 = 0; p.p1 = R * p.s0; p.p2 = p.p1 + R * p.s1;
       break;
     case T_F16: case T_BF16:
       p.s0 = K * 2; break;

@@ -30,6 +30,7 @@ CpuMat load_mat(const GGUFFile& f, const std::string& name, int n_expert = 0, si
                 size_t c0 = 0, long K = -1) {
   const GGUFTensor* t = f.find(name);
   if (!t) throw std::runtime_error("missing tensor " + name);
+  if (n_expert > 0) check_expert_type(name, t->type);
   const size_t K_src = (size_t)t->ne[0], R_src = (size_t)t->ne[1];
   CpuMat m;
   m.type = t->type;
@@ -55,6 +56,7 @@ CpuMat load_gate_up(const GGUFFile& f, const std::string& g, const std::string& 
   const GGUFTensor* tu = f.find(u);
   if (!tg || !tu) throw std::runtime_error("missing " + g);
   if (tg->type != tu->type) throw std::runtime_error("gate/up projections must share a quant type");
+  if (n_expert > 0) check_expert_type(g, tg->type);
   CpuMat m;
   m.type = tg->type;
   m.K = (int)tg->ne[0];
@@ -192,6 +194,28 @@ void decode_chunk(const CpuMat& W, const uint8_t* base, size_t row, int c, Chunk
       ch.m_lo = ch.m_hi = 0.f;
       break;
     }
+    case T_Q4_0:
+    case T_Q4_1:
+    case T_Q5_0:
+    case T_Q5_1: {
+      // block c: byte i holds weight i (low nibble) and weight 16 + i (high nibble)
+      const bool five = W.type == T_Q5_0 || W.type == T_Q5_1, has_m = W.type == T_Q4_1 || W.type == T_Q5_1;
+      const uint8_t* qs = base + P.p0 + row * P.s0 + 16 * c;
+      const uint8_t* sp = five ? base + P.p2 + row * P.s2 : base + P.p1 + row * P.s1;
+      uint32_t qh = 0;
+      if (five) std::memcpy(&qh, base + P.p1 + row * P.s1 + 4 * c, 4);
+      for (int i = 0; i < 16; ++i) {
+        ch.w[i] = (int8_t)((qs[i] & 0xF) | (((qh >> i) & 1) << 4));
+        ch.w[16 + i] = (int8_t)((qs[i] >> 4) | (((qh >> (16 + i)) & 1) << 4));
+      }
+      const float d = hf(sp + (has_m ? 4 : 2) * c);
+      ch.off_lo = 32 * c;
+      ch.off_hi = 32 * c + 16;
+      ch.s_lo = ch.s_hi = d;
+      // sum = s * dot - m * sum(x): the -8 / -16 offset and the block minimum as the m term
+      ch.m_lo = ch.m_hi = has_m ? -hf(sp + 4 * c + 2) : (five ? 16.f : 8.f) * d;
+      break;
+    }
     case T_F32:
     case T_F16: {
       ch.is_float = true;
@@ -256,6 +280,30 @@ inline __m256i chunk_w(const CpuMat& W, const uint8_t* base, size_t row, int c, 
     off_lo = sb * 256 + 128 * n + o;
     off_hi = off_lo + 64;
     return _mm256_set_m128i(hi, lo);
+  } else if constexpr (QT == T_Q4_0 || QT == T_Q4_1 || QT == T_Q5_0 || QT == T_Q5_1) {
+    constexpr bool five = QT == T_Q5_0 || QT == T_Q5_1, has_m = QT == T_Q4_1 || QT == T_Q5_1;
+    const __m128i q = _mm_loadu_si128(reinterpret_cast<const __m128i*>(base + P.p0 + row * P.s0 + 16 * c));
+    __m128i lo = _mm_and_si128(q, m4), hi = _mm_and_si128(_mm_srli_epi16(q, 4), m4);
+    if constexpr (five) {
+      uint32_t qh;
+      std::memcpy(&qh, base + P.p1 + row * P.s1 + 4 * c, 4);
+      // byte i of a half <- bit i of its 16 qh bits: broadcast the two bytes, test one bit per lane
+      const __m128i sel = _mm_set_epi8(1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0);
+      const __m128i bit = _mm_set_epi8((char)0x80, 0x40, 0x20, 0x10, 8, 4, 2, 1, (char)0x80, 0x40, 0x20, 0x10, 8, 4, 2, 1);
+      const __m128i b16 = _mm_set1_epi8(0x10);
+      const __m128i bl = _mm_shuffle_epi8(_mm_cvtsi32_si128((int)(qh & 0xFFFF)), sel);
+      const __m128i bh = _mm_shuffle_epi8(_mm_cvtsi32_si128((int)(qh >> 16)), sel);
+      lo = _mm_or_si128(lo, _mm_and_si128(_mm_cmpeq_epi8(_mm_and_si128(bl, bit), bit), b16));
+      hi = _mm_or_si128(hi, _mm_and_si128(_mm_cmpeq_epi8(_mm_and_si128(bh, bit), bit), b16));
+    }
+    const uint8_t* sp = five ? base + P.p2 + row * P.s2 : base + P.p1 + row * P.s1;
+    const float d = hf(sp + (has_m ? 4 : 2) * c);
+    s_lo = s_hi = d;
+    m_lo = m_hi = has_m ? -hf(sp + 4 * c + 2) : (five ? 16.f : 8.f) * d;
+    off_lo = 32 * c;
+    off_hi = 32 * c + 16;
+    (void)sb; (void)j;
+    return _mm256_set_m128i(hi, lo);
   } else {  // Q8_0 (signed)
     const float d = hf(base + P.p1 + row * P.s1 + 2 * c);
     s_lo = s_hi = d;
@@ -318,6 +366,10 @@ void gemm_rows(const CpuMat& W, const uint8_t* base, const Q8& xq, int T, float*
     case T_Q5_K: return gemm_rows_avx2<T_Q5_K>(W, base, xq, T, y, ldy, add);
     case T_Q6_K: return gemm_rows_avx2<T_Q6_K>(W, base, xq, T, y, ldy, add);
     case T_Q8_0: return gemm_rows_avx2<T_Q8_0>(W, base, xq, T, y, ldy, add);
+    case T_Q4_0: return gemm_rows_avx2<T_Q4_0>(W, base, xq, T, y, ldy, add);
+    case T_Q4_1: return gemm_rows_avx2<T_Q4_1>(W, base, xq, T, y, ldy, add);
+    case T_Q5_0: return gemm_rows_avx2<T_Q5_0>(W, base, xq, T, y, ldy, add);
+    case T_Q5_1: return gemm_rows_avx2<T_Q5_1>(W, base, xq, T, y, ldy, add);
     default: return gemm_rows_scalar(W, base, xq, T, y, ldy, add);
   }
 }

@@ -1,6 +1,6 @@
 // Batched decode projection on MFMA (continuous batching, 1-16 activation rows):
 //   out[b][row] += sum_k W[row][k] * x[b][k]
-// W block-quantised (Q4_K / Q5_K / Q6_K / Q8_0) read from a tile-ordered copy (tile16, below);
+// W block-quantised (Q4_K / Q5_K / Q6_K / Q8_0, and Q4_0 / Q4_1 / Q5_0 / Q5_1 as Q4_K / Q5_K) read from a tile-ordered copy (tile16, below);
 // x f16 rows in a 4-group swizzled k order, staged per block in LDS - from xh (written by
 // bprep or by the attention kernel) or, for Q|K|V and gate/up, straight from the fp32
 // residual with the RMSNorm folded in.
@@ -199,10 +199,25 @@ __device__ __forceinline__ void chunk_runs(int c, int& off_lo, int& off_hi) {
 //   Q6_K: ql[h][l][16] | qx[h][l][8] | sc[r16][h][kq][(d*sc_lo, d*sc_hi) f16]   3584 B
 //         (qx: the chunk's 2-bit high fields regrouped per lane - see dequant_frags)
 //   Q8_0: qs[h][a|b][l][16] | d[h][l][2]                                        4352 B
+//   Q4_0 / Q4_1: the Q4_K step, Q5_0 / Q5_1: the Q5_K step (re-expressed exactly, below)
 // Rows past the matrix are zero.
-__host__ __device__ constexpr int t16_step_bytes(int t) {
-  return t == T_Q4_K ? 2560 : t == T_Q5_K ? 3072 : t == T_Q6_K ? 3584 : t == T_Q8_0 ? 4352 : 0;
+//
+// The legacy 32-weight blocks have no MFMA decode of their own. Two neighbouring blocks A, B
+// (64 weights) are one Q4_K / Q5_K 64-group: byte i of the group holds weight i of A in its low
+// nibble and weight i of B in its high nibble, the per-sub-block f16 pair is (d, -8d) for Q4_0,
+// (d, -16d) for Q5_0 and (d, m) for Q4_1 / Q5_1, and the blocks' qh words are regrouped into
+// Q5_K's qh[32] (bit s of byte i = 5th bit of weight i of block s). Every weight is the same
+// one-rounding q * a + b as the K-quants', so the Q4_K / Q5_K kernels serve these types as they
+// stand; callers keep passing the source type, which is mapped here.
+__host__ __device__ constexpr int t16_kernel_type(int t) {
+  return (t == T_Q4_0 || t == T_Q4_1) ? T_Q4_K : (t == T_Q5_0 || t == T_Q5_1) ? T_Q5_K : t;
 }
+__host__ __device__ constexpr int t16_step_bytes(int t) {
+  const int k = t16_kernel_type(t);
+  return k == T_Q4_K ? 2560 : k == T_Q5_K ? 3072 : k == T_Q6_K ? 3584 : k == T_Q8_0 ? 4352 : 0;
+}
+
+int t16_format(int type) { return t16_kernel_type(type); }
 
 size_t t16_bytes(int type, int rows, int K) {
   return (size_t)((rows + 15) / 16) * (size_t)(K / 256) * (size_t)t16_step_bytes(type);
@@ -301,6 +316,78 @@ __global__ __launch_bounds__(64) void t16_repack_kernel(QMat w, uint8_t* dst, in
   }
 }
 
+// legacy source types -> the Q4_K / Q5_K step format (see the layout comment above)
+template <int T>
+__global__ __launch_bounds__(64) void t16_repack_legacy_kernel(QMat w, uint8_t* dst, int swiglu) {
+  static_assert(is_legacy_v<T>, "legacy 32-weight block types only");
+  const int s = blockIdx.x, t = blockIdx.y, steps = gridDim.x;
+  const int l = threadIdx.x, r16 = l & 15, kq = l >> 4;
+  int row = t * 16 + r16;
+  bool ok = row < w.rows;
+  if (swiglu) {  // as t16_repack_kernel
+    const int f = 8 * t + (r16 & 7);
+    row = 64 * (f >> 5) + (r16 >= 8 ? 32 : 0) + (f & 31);
+    ok = f < w.rows / 2;
+  }
+  const size_t r = ok ? (size_t)row : 0;
+  uint8_t* blk = dst + ((size_t)t * steps + s) * t16_step_bytes(T);
+  const Planes& P = w.P;
+  const uint8_t* p0 = w.base + P.p0 + r * P.s0;
+  const uint8_t* p1 = w.base + P.p1 + r * P.s1;
+  const uint8_t* p2 = w.base + P.p2 + r * P.s2;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    // chunk j of the step: bytes 16 (j & 1) .. +15 of 64-group j >> 1 = blocks A = 2 (j >> 1), A + 1
+    const int j = 4 * h + kq, blkA = 8 * s + 2 * (j >> 1);
+    const uint4 a = *reinterpret_cast<const uint4*>(p0 + 16 * blkA);
+    const uint4 b = *reinterpret_cast<const uint4*>(p0 + 16 * (blkA + 1));
+    auto mix = [&](unsigned x, unsigned y) {  // weights 16 (j & 1) + .. of A (low nibbles) and B (high)
+      return (j & 1) ? (((x >> 4) & 0x0F0F0F0Fu) | (y & 0xF0F0F0F0u)) : ((x & 0x0F0F0F0Fu) | ((y << 4) & 0xF0F0F0F0u));
+    };
+    *reinterpret_cast<uint4*>(blk + h * 1024 + l * 16) =
+        ok ? make_uint4(mix(a.x, b.x), mix(a.y, b.y), mix(a.z, b.z), mix(a.w, b.w)) : make_uint4(0, 0, 0, 0);
+  }
+  if (kq != 0) return;
+  const uint8_t* sp = legacy_has_h<T> ? p2 : p1;
+  unsigned outw[8];
+#pragma unroll
+  for (int sb = 0; sb < 8; ++sb) {
+    const int c = 8 * s + sb;
+    float d, m;
+    if constexpr (legacy_has_m<T>) {
+      const unsigned dm = *reinterpret_cast<const unsigned*>(sp + 4 * c);
+      d = h2f(dm & 0xFFFF);
+      m = h2f(dm >> 16);
+    } else {
+      d = h2f(*reinterpret_cast<const unsigned short*>(sp + 2 * c));
+      m = (T == T_Q4_0 ? -8.f : -16.f) * d;
+    }
+    const h2_t p = {(_Float16)d, (_Float16)m};
+    outw[sb] = ok ? as_u(p) : 0u;
+  }
+  uint4* dst16 = reinterpret_cast<uint4*>(blk + (legacy_has_h<T> ? 2560 : 2048) + r16 * 32);
+  dst16[0] = make_uint4(outw[0], outw[1], outw[2], outw[3]);
+  dst16[1] = make_uint4(outw[4], outw[5], outw[6], outw[7]);
+  if constexpr (legacy_has_h<T>) {
+    unsigned qh[8];
+#pragma unroll
+    for (int sb = 0; sb < 8; ++sb) qh[sb] = ok ? *reinterpret_cast<const unsigned*>(p1 + 4 * (8 * s + sb)) : 0u;
+    unsigned hw[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {  // dword i = bytes 4i .. 4i + 3 of Q5_K's qh[32]
+      unsigned v = 0u;
+#pragma unroll
+      for (int b8 = 0; b8 < 4; ++b8)
+#pragma unroll
+        for (int sb = 0; sb < 8; ++sb) v |= ((qh[sb] >> (4 * i + b8)) & 1u) << (8 * b8 + sb);
+      hw[i] = v;
+    }
+    uint4* h16 = reinterpret_cast<uint4*>(blk + 2048 + r16 * 32);
+    h16[0] = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+    h16[1] = make_uint4(hw[4], hw[5], hw[6], hw[7]);
+  }
+}
+
 void t16_repack(const QMat& w, uint8_t* dst, hipStream_t st, bool swiglu) {
   if (!bmm_supported(w.type, w.K)) throw std::runtime_error("t16_repack: unsupported type / K");
   if (swiglu && w.rows % 64) throw std::runtime_error("t16_repack: SwiGLU copy needs 32-row gate / up groups");
@@ -310,7 +397,12 @@ void t16_repack(const QMat& w, uint8_t* dst, hipStream_t st, bool swiglu) {
     case T_Q4_K: hipLaunchKernelGGL(t16_repack_kernel<T_Q4_K>, grid, dim3(64), 0, st, w, dst, sw); break;
     case T_Q5_K: hipLaunchKernelGGL(t16_repack_kernel<T_Q5_K>, grid, dim3(64), 0, st, w, dst, sw); break;
     case T_Q6_K: hipLaunchKernelGGL(t16_repack_kernel<T_Q6_K>, grid, dim3(64), 0, st, w, dst, sw); break;
-    default: hipLaunchKernelGGL(t16_repack_kernel<T_Q8_0>, grid, dim3(64), 0, st, w, dst, sw); break;
+    case T_Q8_0: hipLaunchKernelGGL(t16_repack_kernel<T_Q8_0>, grid, dim3(64), 0, st, w, dst, sw); break;
+    case T_Q4_0: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q4_0>, grid, dim3(64), 0, st, w, dst, sw); break;
+    case T_Q4_1: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q4_1>, grid, dim3(64), 0, st, w, dst, sw); break;
+    case T_Q5_0: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q5_0>, grid, dim3(64), 0, st, w, dst, sw); break;
+    case T_Q5_1: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q5_1>, grid, dim3(64), 0, st, w, dst, sw); break;
+    default: throw std::runtime_error("t16_repack: unsupported type");
   }
 }
 
@@ -1637,7 +1729,8 @@ bool bmm_qkv_fits(int K, int B) { return K % 256 == 0 && B >= 1 && bmm_lds(B, K 
 bool bmm_norm_fits(int K, int B) { return bmm_qkv_fits(K, B) && K == 4096 && B <= 8; }
 
 bool bmm_supported(int type, int K) {
-  if (type != T_Q4_K && type != T_Q5_K && type != T_Q6_K && type != T_Q8_0) return false;
+  const int k = t16_kernel_type(type);  // the legacy 32-block types run as Q4_K / Q5_K
+  if (k != T_Q4_K && k != T_Q5_K && k != T_Q6_K && k != T_Q8_0) return false;
   return K % 256 == 0;  // 256 k per step
 }
 
@@ -1811,6 +1904,7 @@ static void launch_qkv_sk(BmmArgs a, hipStream_t s) {
 bool bmm_qkv_sk_defers_rope() { return bmm_il(); }
 
 bool bmm_qkv_sk_supported(int tq, int tk, int tv, int K, int B) {
+  tq = t16_kernel_type(tq); tk = t16_kernel_type(tk); tv = t16_kernel_type(tv);
   if (B < 1 || B > 8 || K % 256 || !bmm_supported(tq, K) || !bmm_supported(tk, K) || !bmm_supported(tv, K)) return false;
   const int t2 = tk != tq ? tk : tv;
   if (tk != tq && tv != tk) return false;  // at most two runs: Q [| K] of one type, the rest of another
@@ -1850,6 +1944,12 @@ void bmm(const BmmArgs& a0, hipStream_t s) {
   BmmArgs a = a0;
   bmm_check(a);
   if (a.n_out <= 0) return;
+  a.w.type = t16_kernel_type(a.w.type);  // the tile16 copy's format (device code never reads the type)
+  a.type2 = a.type2 ? t16_kernel_type(a.type2) : 0;
+  if (a.qkv_sk && a.seg_split < a.nseg && a.type2 == a.w.type) {  // two source types, one tile16 format: one run
+    a.seg_split = a.nseg;
+    a.type2 = 0;
+  }
   if (a.qkv_sk) {
     const bool two = a.seg_split < a.nseg;
     const int t2 = two ? a.type2 : 0;
@@ -1860,7 +1960,8 @@ void bmm(const BmmArgs& a0, hipStream_t s) {
     else if (a.w.type == T_Q4_K) launch_qkv_sk<T_Q4_K, 0>(a, s);
     else if (a.w.type == T_Q5_K) launch_qkv_sk<T_Q5_K, 0>(a, s);
     else if (a.w.type == T_Q6_K) launch_qkv_sk<T_Q6_K, 0>(a, s);
-    else launch_qkv_sk<T_Q8_0, 0>(a, s);
+    else if (a.w.type == T_Q8_0) launch_qkv_sk<T_Q8_0, 0>(a, s);
+    else throw std::runtime_error("bmm: unsupported weight type");
     return;
   }
   switch (a.w.type) {
@@ -1875,7 +1976,8 @@ void bmm(const BmmArgs& a0, hipStream_t s) {
 bool bmm_ffn_chain_supported(const BmmArgs& gu, const BmmArgs& dn) {
   return gu.swiglu_epi && !gu.ew && !gu.qkv_epi && gu.nseg == 1 && gu.B <= 8 && (!gu.xf || gu.w.K == 4096) &&
          !dn.swiglu_epi && !dn.ew && !dn.qkv_epi && !dn.xf && !dn.one_part && !dn.store_out && dn.nseg == 1 &&
-         dn.B == gu.B && gu.w.type == T_Q4_K && (dn.w.type == T_Q4_K || dn.w.type == T_Q6_K) &&
+         dn.B == gu.B && t16_kernel_type(gu.w.type) == T_Q4_K &&
+         (t16_kernel_type(dn.w.type) == T_Q4_K || dn.w.type == T_Q6_K) &&
          dn.xh == gu.h_out && dn.ldh == gu.ldh_out && dn.w.K == gu.n_out / 2;
 }
 
@@ -1906,7 +2008,7 @@ void bmm_ffn_chain(const BmmArgs& gu0, const BmmArgs& dn0, int* cnt, int* err, h
 }
 
 bool bmm_wo_ffn_chain_supported(const BmmArgs& wo, const BmmArgs& gu, const BmmArgs& dn) {
-  return bmm_il() && bmm_ffn_chain_supported(gu, dn) && gu.xf && wo.w.type == T_Q4_K && !wo.ew && !wo.xf &&
+  return bmm_il() && bmm_ffn_chain_supported(gu, dn) && gu.xf && t16_kernel_type(wo.w.type) == T_Q4_K && !wo.ew && !wo.xf &&
          !wo.swiglu_epi && !wo.qkv_epi && !wo.one_part && !wo.store_out && !wo.zero && wo.nseg == 1 && wo.B == gu.B &&
          wo.out == gu.xf && wo.ldo == gu.ldxf && wo.n_out == gu.w.K;
 }
@@ -1956,7 +2058,7 @@ bool bmm_qkv2(const BmmArgs& a0, const BmmArgs& b0, hipStream_t s) {
   int nbb = std::min(tb, std::max(1, cap - na));
   a.nb1 = na;
   const dim3 grid(na + nbb), blk(512);
-  const int ta_ = a.w.type, tb_ = b.w.type;
+  const int ta_ = t16_kernel_type(a.w.type), tb_ = t16_kernel_type(b.w.type);
   if (ta_ == T_Q4_K && tb_ == T_Q6_K) hipLaunchKernelGGL((bmm_kernel<T_Q4_K, 8, 1, T_Q6_K>), grid, blk, lds, s, a, b);
   else if (ta_ == T_Q4_K && tb_ == T_Q5_K) hipLaunchKernelGGL((bmm_kernel<T_Q4_K, 8, 1, T_Q5_K>), grid, blk, lds, s, a, b);
   else return false;
@@ -2289,11 +2391,12 @@ void gemm_t16(const GemmT16Args& a, int epi, hipStream_t s) {
     throw std::runtime_error("gemm_t16: output");
   }
   if (reinterpret_cast<uintptr_t>(a.x) % 16) throw std::runtime_error("gemm_t16: X must be 16-byte aligned");
-  switch (a.w.type) {
+  switch (t16_kernel_type(a.w.type)) {
     case T_Q4_K: gemm_t16_epi<T_Q4_K>(a, epi, s); break;
     case T_Q5_K: gemm_t16_epi<T_Q5_K>(a, epi, s); break;
     case T_Q6_K: gemm_t16_epi<T_Q6_K>(a, epi, s); break;
-    default: gemm_t16_epi<T_Q8_0>(a, epi, s); break;
+    case T_Q8_0: gemm_t16_epi<T_Q8_0>(a, epi, s); break;
+    default: throw std::runtime_error("gemm_t16: unsupported weight type");
   }
 }
 

@@ -260,6 +260,10 @@ void gemm_dq(const GemmArgs& a, int epi, hipStream_t s) {
     case T_Q5_K: launch_gemm<T_Q5_K>(a, epi, s); break;
     case T_Q6_K: launch_gemm<T_Q6_K>(a, epi, s); break;
     case T_Q8_0: launch_gemm<T_Q8_0>(a, epi, s); break;
+    case T_Q4_0: launch_gemm<T_Q4_0>(a, epi, s); break;
+    case T_Q4_1: launch_gemm<T_Q4_1>(a, epi, s); break;
+    case T_Q5_0: launch_gemm<T_Q5_0>(a, epi, s); break;
+    case T_Q5_1: launch_gemm<T_Q5_1>(a, epi, s); break;
     case T_F16: launch_gemm<T_F16>(a, epi, s); break;
     case T_F32: launch_gemm<T_F32>(a, epi, s); break;
     default: throw std::runtime_error("gemm_dq: unsupported weight type");

@@ -297,6 +297,7 @@ struct AttnWo1Args {
   int n_wo = 0;  // Wo blocks
 };
 
+#ifndef LFK_GEMV_LEGACY_TU
 template <int QT, int HD, int G>
 __global__ __launch_bounds__(256) void attn_wo1_kernel(AttnWo1Args p) {
   const AttnWo1Args* k = (const AttnWo1Args*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -351,6 +352,8 @@ QMat make_qmat(const void* base, int type, int rows, int K, size_t expert_stride
   m.expert_stride = expert_stride;
   return m;
 }
+
+#endif  // !LFK_GEMV_LEGACY_TU
 
 static inline int grid_for(int items, int per_block = 4) {
   int b = (items + per_block - 1) / per_block;
@@ -553,7 +556,7 @@ static void launch_gemv_splitk(const GemvArgs& a, hipStream_t s) {
 
 template <int QT, int EPI>
 static void launch_gemv(const GemvArgs& a, hipStream_t s) {
-  if constexpr (EPI == EPI_ADD && (QT == T_Q4_K || QT == T_Q5_K || QT == T_Q6_K || QT == T_Q8_0)) {
+  if constexpr (EPI == EPI_ADD && (QT == T_Q4_K || QT == T_Q5_K || QT == T_Q6_K || QT == T_Q8_0 || is_legacy_v<QT>)) {
     if (!a.dbg_clk && a.w.K >= 4096 && !a.debug) return launch_gemv_splitk<QT>(a, s);
   }
   if (a.dbg_clk) {
@@ -575,6 +578,20 @@ static void gemv_t(const GemvArgs& a, int epi, hipStream_t s) {
   }
 }
 
+#ifdef LFK_GEMV_LEGACY_TU
+// gemv_legacy.hip: the legacy 32-block types' instantiations, compiled beside the rest
+void gemv_legacy(const GemvArgs& a, int epi, hipStream_t s) {
+  switch (a.w.type) {
+    case T_Q4_0: gemv_t<T_Q4_0>(a, epi, s); break;
+    case T_Q4_1: gemv_t<T_Q4_1>(a, epi, s); break;
+    case T_Q5_0: gemv_t<T_Q5_0>(a, epi, s); break;
+    case T_Q5_1: gemv_t<T_Q5_1>(a, epi, s); break;
+    default: throw std::runtime_error("gemv: unsupported weight type");
+  }
+}
+#else
+void gemv_legacy(const GemvArgs& a, int epi, hipStream_t s);
+
 void gemv(const GemvArgs& a, int epi, hipStream_t s) {
   if (epi == EPI_SWIGLU && (a.n_out % 32)) throw std::runtime_error("gemv: swiglu features must be a multiple of 32");
   if (a.w.K % 32) throw std::runtime_error("gemv: K must be a multiple of 32");
@@ -584,11 +601,13 @@ void gemv(const GemvArgs& a, int epi, hipStream_t s) {
     case T_Q5_K: gemv_t<T_Q5_K>(a, epi, s); break;
     case T_Q6_K: gemv_t<T_Q6_K>(a, epi, s); break;
     case T_Q8_0: gemv_t<T_Q8_0>(a, epi, s); break;
+    case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: gemv_legacy(a, epi, s); break;
     case T_F16: gemv_t<T_F16>(a, epi, s); break;
     case T_F32: gemv_t<T_F32>(a, epi, s); break;
     default: throw std::runtime_error("gemv: unsupported weight type");
   }
 }
+#endif  // LFK_GEMV_LEGACY_TU
 
 // ------------------------------------------------------------------ QKV + RoPE + KV append
 // One launch for the Q, K and V projections. Their rows form at most two runs of
@@ -746,6 +765,19 @@ static void launch_qkv1(QkvLaunch L, int rows, hipStream_t s) {
   }));
 }
 
+#ifdef LFK_GEMV_LEGACY_TU
+void gemv_qkv1_legacy(const QkvLaunch& L, int type, int rows, hipStream_t s) {
+  switch (type) {
+    case T_Q4_0: launch_qkv1<T_Q4_0>(L, rows, s); break;
+    case T_Q4_1: launch_qkv1<T_Q4_1>(L, rows, s); break;
+    case T_Q5_0: launch_qkv1<T_Q5_0>(L, rows, s); break;
+    case T_Q5_1: launch_qkv1<T_Q5_1>(L, rows, s); break;
+    default: throw std::runtime_error("gemv_qkv: unsupported type");
+  }
+}
+#else
+void gemv_qkv1_legacy(const QkvLaunch& L, int type, int rows, hipStream_t s);
+
 // two type runs in one launch: (2 rows, 2 passes) items for the first run and
 // (2 rows, 1 pass) for the second (keeps the combined kernel near 128 VGPRs)
 template <int QT0, int QT1>
@@ -790,6 +822,7 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
       case T_Q5_K: launch_qkv1<T_Q5_K>(L, rows_of(0, 3), s); return;
       case T_Q6_K: launch_qkv1<T_Q6_K>(L, rows_of(0, 3), s); return;
       case T_Q8_0: launch_qkv1<T_Q8_0>(L, rows_of(0, 3), s); return;
+      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: gemv_qkv1_legacy(L, run_type[0], rows_of(0, 3), s); return;
       case T_F16: launch_qkv1<T_F16>(L, rows_of(0, 3), s); return;
       case T_F32: launch_qkv1<T_F32>(L, rows_of(0, 3), s); return;
       default: throw std::runtime_error("gemv_qkv: unsupported type");
@@ -815,6 +848,7 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
       case T_Q5_K: launch_qkv1<T_Q5_K>(Li, m[i]->rows, s); break;
       case T_Q6_K: launch_qkv1<T_Q6_K>(Li, m[i]->rows, s); break;
       case T_Q8_0: launch_qkv1<T_Q8_0>(Li, m[i]->rows, s); break;
+      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: gemv_qkv1_legacy(Li, m[i]->type, m[i]->rows, s); break;
       case T_F16: launch_qkv1<T_F16>(Li, m[i]->rows, s); break;
       case T_F32: launch_qkv1<T_F32>(Li, m[i]->rows, s); break;
       default: throw std::runtime_error("gemv_qkv: unsupported type");
@@ -911,5 +945,7 @@ void moe_route(const float* logits, int n_expert, int k, int* ids, float* w, hip
   if (n_expert > 64 || k > n_expert) throw std::runtime_error("moe_route: n_expert must be <= 64");
   hipLaunchKernelGGL(moe_route_kernel, dim3(1), dim3(64), 0, s, logits, n_expert, k, ids, w);
 }
+
+#endif  // LFK_GEMV_LEGACY_TU
 
 }  // namespace lfk

@@ -247,6 +247,8 @@ bool bmm_qkv2(const BmmArgs& a, const BmmArgs& b, hipStream_t s);
 bool bmm_qkv_sk_defers_rope();
 // the batched path's weight copy: per 16-row tile and 256-k step one contiguous block
 size_t t16_bytes(int type, int rows, int K);
+// the tile16 step format a type's copy is written in: Q4_0 / Q4_1 -> Q4_K, Q5_0 / Q5_1 -> Q5_K, else the type
+int t16_format(int type);
 // swiglu: `planar` is a gate/up matrix in 32-row gate / up groups (upload_gate_up); the copy
 // regroups it per tile as 8 gate rows + the 8 up rows of the same features
 void t16_repack(const QMat& planar, uint8_t* dst, hipStream_t s, bool swiglu = false);

@@ -2,6 +2,7 @@
 // RMSNorm->bf16 for the prefill GEMMs (K2), prefill RoPE + KV append (K5/K6),
 // helpers, and the on-device synthetic weight generator.
 #include <algorithm>
+#include <stdexcept>
 #include <hip/hip_bf16.h>
 
 #include "kernels.h"
@@ -36,6 +37,7 @@ __global__ __launch_bounds__(128) void embed_kernel(QMat e, const int* tokens, i
 
 void embed_rows(const QMat& emb, const int* tokens, int T, float* x, hipStream_t s, int* zero, int zero_n) {
   if (T <= 0) return;
+  if (!dispatchable_type(emb.type)) throw std::runtime_error("embed_rows: unsupported embedding type");
   hipLaunchKernelGGL(embed_kernel, dim3(T), dim3(128), 0, s, emb, tokens, T, x, zero, zero ? zero_n : 0);
 }
 
@@ -173,6 +175,7 @@ __global__ __launch_bounds__(128) void batch_embed_kernel(QMat e, const int* slo
 void batch_gather_embed(const int* slots, int B, const int* state, int* tok, int* pos, const QMat& emb, float* x,
                         hipStream_t s, int* zero, int zero_n, int zero_stride) {
   if (B <= 0) return;
+  if (!dispatchable_type(emb.type)) throw std::runtime_error("batch_gather_embed: unsupported embedding type");
   hipLaunchKernelGGL(batch_embed_kernel, dim3(B), dim3(128), 0, s, emb, slots, state, tok, pos, x, zero,
                      zero ? zero_n : 0, zero_stride);
 }
@@ -220,6 +223,17 @@ __global__ void fix_scales_kernel(uint8_t* base, int type, size_t nblocks, Plane
       reinterpret_cast<__half*>(base + P.p3)[b] = __float2half(std / (73.9f * 18.5f) * jit);
     } else if (type == T_Q8_0) {
       reinterpret_cast<__half*>(base + P.p1)[b] = __float2half(std / 73.9f * jit);
+    } else if (type == T_Q4_0 || type == T_Q4_1 || type == T_Q5_0 || type == T_Q5_1) {
+      // q uniform in [0, nmax]; the -8 / -16 offset or m = -d nmax / 2 centres the weights
+      const float nmax = (type == T_Q4_0 || type == T_Q4_1) ? 15.f : 31.f;
+      const __half d = __float2half(std / sqrtf(((nmax + 1.f) * (nmax + 1.f) - 1.f) / 12.f) * jit);
+      uint8_t* sp = base + ((type == T_Q4_0 || type == T_Q4_1) ? P.p1 : P.p2);
+      if (type == T_Q4_0 || type == T_Q5_0) {
+        reinterpret_cast<__half*>(sp)[b] = d;
+      } else {
+        reinterpret_cast<__half*>(sp)[2 * b] = d;
+        reinterpret_cast<__half*>(sp)[2 * b + 1] = __float2half(-__half2float(d) * nmax * 0.5f);
+      }
     } else if (type == T_F32) {
       // uniform in [-sqrt(3) std, sqrt(3) std]
       const float u = u01(mix64(seed ^ (b * 0x9E37ull)));
@@ -238,8 +252,10 @@ void fill_random_planar(uint8_t* base, int type, size_t rows, size_t K, float st
   hipLaunchKernelGGL(fill_bytes_kernel, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t*>(base), bytes / 4, seed);
   size_t nblocks;
   if (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K) nblocks = rows * (K / 256);
-  else if (type == T_Q8_0) nblocks = rows * (K / 32);
-  else nblocks = rows * K;
+  else if (type == T_Q8_0 || type == T_Q4_0 || type == T_Q4_1 || type == T_Q5_0 || type == T_Q5_1)
+    nblocks = rows * (K / 32);
+  else if (type == T_F16 || type == T_BF16 || type == T_F32) nblocks = rows * K;
+  else throw std::runtime_error("fill_random_planar: unsupported type");
   hipLaunchKernelGGL(fix_scales_kernel, dim3(2048), dim3(256), 0, s, base, type, nblocks, P, std, seed + 1);
 }
 

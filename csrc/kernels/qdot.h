@@ -12,6 +12,8 @@
 //                                      hi 16 @ +32               (sub-block 2g+1)
 //   Q6_K      : j=c&7, n=j>>2, o=16(j&3): lo 16 @ sb*256+128n+o, hi 16 @ +64
 //   Q8_0/F16/F32: 32 contiguous @ 32c
+//   Q4_0/Q4_1/Q5_0/Q5_1: chunk c = block c, 32 contiguous @ 32c like Q8_0: the low nibbles
+//                        are weights 32c .. 32c+15, the high nibbles 32c+16 .. 32c+31
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -113,7 +115,7 @@ __device__ __forceinline__ void load_x(XChunk& X, const int8_t* xq, const float*
     off_hi = off_lo + 64;
     blo = off_lo >> 5;
     bhi = blo + 2;
-  } else {  // Q8_0 / F16 / F32: 32 contiguous values = one x block
+  } else {  // Q8_0 / legacy 32-blocks / F16 / F32: 32 contiguous values = one x block
     off_lo = 32 * c;
     off_hi = off_lo + 16;
     blo = bhi = c;
@@ -129,6 +131,86 @@ __device__ __forceinline__ void load_x(XChunk& X, const int8_t* xq, const float*
   int s1 = dot4(X.hi[0], ones, dot4(X.hi[1], ones, dot4(X.hi[2], ones, dot4(X.hi[3], ones, 0))));
   X.slo = X.dlo * (float)s0;
   X.shi = X.dhi * (float)s1;
+}
+
+// ---- legacy 32-weight blocks (Q4_0 / Q4_1 / Q5_0 / Q5_1): w = d * q + m with m = -8d / -16d
+// for the symmetric types. One raw form for all four: the 16 quant bytes, the 5-bit types' high
+// bits and the scale field (d, or d | m << 16).
+template <int T> inline constexpr bool is_legacy_v = (T == T_Q4_0 || T == T_Q4_1 || T == T_Q5_0 || T == T_Q5_1);
+template <int T> inline constexpr bool legacy_has_m = (T == T_Q4_1 || T == T_Q5_1);
+template <int T> inline constexpr bool legacy_has_h = (T == T_Q5_0 || T == T_Q5_1);
+struct LegacyRaw {
+  int4 q;
+  unsigned h, s;
+};
+
+// block c of a row: plane row pointers p0 (qs), p1 and p2 as planes_of orders them
+template <int T, bool NT>
+__device__ __forceinline__ void legacy_load(LegacyRaw& w, const uint8_t* p0, const uint8_t* p1, const uint8_t* p2,
+                                            int c) {
+  if constexpr (NT) w.q = ld_nt16(p0 + 16 * c);
+  else w.q = *reinterpret_cast<const int4*>(p0 + 16 * c);
+  const uint8_t* sp = legacy_has_h<T> ? p2 : p1;
+  if constexpr (legacy_has_h<T>) w.h = *reinterpret_cast<const unsigned*>(p1 + 4 * c);
+  else w.h = 0u;
+  if constexpr (legacy_has_m<T>) w.s = *reinterpret_cast<const unsigned*>(sp + 4 * c);
+  else w.s = *reinterpret_cast<const unsigned short*>(sp + 2 * c);
+}
+
+template <int T>
+__device__ __forceinline__ void legacy_scale(const LegacyRaw& w, float& d, float& m) {
+  d = h2f(w.s & 0xFFFF);
+  if constexpr (legacy_has_m<T>) m = h2f(w.s >> 16);
+  else m = (T == T_Q4_0 ? -8.f : -16.f) * d;
+}
+
+// quant dword i (i = 0..3) as bytes: lo = weights 4i .. 4i+3, hi = weights 16+4i .. 16+4i+3.
+// 5-bit types: the four qh bits of a dword are spread to bit 0 of its four bytes by one 24-bit
+// multiply (bit k lands on 8k; the partial products meet no other bit, so nothing carries).
+template <int T>
+__device__ __forceinline__ void legacy_quants(const LegacyRaw& w, int i, int& lo, int& hi) {
+  const unsigned q = (unsigned)(i == 0 ? w.q.x : i == 1 ? w.q.y : i == 2 ? w.q.z : w.q.w);
+  unsigned l = q & 0x0F0F0F0Fu, h = (q >> 4) & 0x0F0F0F0Fu;
+  if constexpr (legacy_has_h<T>) {
+    const unsigned bl = __umul24((w.h >> (4 * i)) & 0xFu, 0x00204081u) & 0x01010101u;
+    const unsigned bh = __umul24((w.h >> (16 + 4 * i)) & 0xFu, 0x00204081u) & 0x01010101u;
+    l |= bl << 4;
+    h |= bh << 4;
+  }
+  lo = (int)l;
+  hi = (int)h;
+}
+
+template <int T>
+__device__ __forceinline__ float legacy_dot(const LegacyRaw& w, const XChunk& X) {
+  int acc = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int lo, hi;
+    legacy_quants<T>(w, i, lo, hi);
+    acc = dot4(lo, X.lo[i], acc);
+    acc = dot4(hi, X.hi[i], acc);
+  }
+  float d, m;
+  legacy_scale<T>(w, d, m);
+  // sum((d q + m) x) = d * dot + m * sum(x): the offset / min goes through the x sums
+  return d * (X.dlo * (float)acc) + m * (X.slo + X.shi);
+}
+
+template <int T>
+__device__ __forceinline__ void legacy_decode(const LegacyRaw& w, float* out) {
+  float d, m;
+  legacy_scale<T>(w, d, m);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int lo, hi;
+    legacy_quants<T>(w, i, lo, hi);
+#pragma unroll
+    for (int b8 = 0; b8 < 4; ++b8) {
+      out[4 * i + b8] = d * (float)((lo >> (8 * b8)) & 0xFF) + m;
+      out[16 + 4 * i + b8] = d * (float)((hi >> (8 * b8)) & 0xFF) + m;
+    }
+  }
 }
 
 // 6-bit (sc, m) pair for sub-blocks 2g and 2g+1 from the 12 packed scale bytes (ggml get_scale_min_k4).
@@ -222,6 +304,10 @@ __device__ __forceinline__ float chunk_dot(const uint8_t* __restrict__ base, con
     acc = dot4(b.z, X.hi[2], acc);
     acc = dot4(b.w, X.hi[3], acc);
     return d * X.dlo * (float)acc;
+  } else if constexpr (is_legacy_v<T>) {
+    LegacyRaw w;
+    legacy_load<T, true>(w, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, base + P.p2 + row * P.s2, c);
+    return legacy_dot<T>(w, X);
   } else {  // F32 / F16 weights: dequantised x
     float s = 0.f;
     const int xv[8] = {X.lo[0], X.lo[1], X.lo[2], X.lo[3], X.hi[0], X.hi[1], X.hi[2], X.hi[3]};
@@ -257,6 +343,10 @@ template <> struct WRaw<T_Q4_K> { int4 q, m; };
 template <> struct WRaw<T_Q5_K> { int4 q, h, m; };
 template <> struct WRaw<T_Q6_K> { int4 l, h; int slo, shi; unsigned d; };
 template <> struct WRaw<T_Q8_0> { int4 a, b; unsigned d; };
+template <> struct WRaw<T_Q4_0> : LegacyRaw {};
+template <> struct WRaw<T_Q4_1> : LegacyRaw {};
+template <> struct WRaw<T_Q5_0> : LegacyRaw {};
+template <> struct WRaw<T_Q5_1> : LegacyRaw {};
 template <> struct WRaw<T_F16> { uint4 w[4]; };
 template <> struct WRaw<T_F32> { float4 w[8]; };
 
@@ -299,6 +389,8 @@ __device__ __forceinline__ void wload(WRaw<T>& w, const RowPtr& R, int c) {
     w.a = ld_nt16(R.p0 + 32 * c);
     w.b = ld_nt16(R.p0 + 32 * c + 16);
     w.d = *reinterpret_cast<const unsigned short*>(R.p1 + 2 * c);
+  } else if constexpr (is_legacy_v<T>) {
+    legacy_load<T, true>(w, R.p0, R.p1, R.p2, c);
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) w.w[i] = reinterpret_cast<const uint4*>(R.p0 + 64 * c)[i];
@@ -358,6 +450,8 @@ __device__ __forceinline__ float wdot(const WRaw<T>& w, const XChunk& X, int c) 
     acc = dot4(w.b.z, X.hi[2], acc);
     acc = dot4(w.b.w, X.hi[3], acc);
     return h2f(w.d & 0xFFFF) * X.dlo * (float)acc;
+  } else if constexpr (is_legacy_v<T>) {
+    return legacy_dot<T>(w, X);
   } else {
     const int xv[8] = {X.lo[0], X.lo[1], X.lo[2], X.lo[3], X.hi[0], X.hi[1], X.hi[2], X.hi[3]};
     float s = 0.f;
@@ -442,6 +536,10 @@ __device__ __forceinline__ void dequant32(const uint8_t* __restrict__ base, cons
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int b8 = 0; b8 < 4; ++b8) out[4 * i + b8] = d * (float)(signed char)((qv[i] >> (8 * b8)) & 0xFF);
+  } else if constexpr (is_legacy_v<T>) {
+    LegacyRaw w;
+    legacy_load<T, false>(w, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, base + P.p2 + row * P.s2, q);
+    legacy_decode<T>(w, out);
   } else if constexpr (T == T_F32) {
     const float4* wp = reinterpret_cast<const float4*>(base + row * P.s0 + 128 * q);
 #pragma unroll
@@ -469,6 +567,10 @@ template <> struct DqRaw<T_Q4_K> { int4 a, b, m; };
 template <> struct DqRaw<T_Q5_K> { int4 a, b, m, h0, h1; };
 template <> struct DqRaw<T_Q6_K> { int4 la, lb, ha, hb, sc; unsigned d; };
 template <> struct DqRaw<T_Q8_0> { int4 a, b; unsigned d; };
+template <> struct DqRaw<T_Q4_0> : LegacyRaw {};
+template <> struct DqRaw<T_Q4_1> : LegacyRaw {};
+template <> struct DqRaw<T_Q5_0> : LegacyRaw {};
+template <> struct DqRaw<T_Q5_1> : LegacyRaw {};
 template <> struct DqRaw<T_F16> { uint4 w[4]; };
 template <> struct DqRaw<T_F32> { float4 w[8]; };
 
@@ -501,6 +603,8 @@ __device__ __forceinline__ void dq_load(DqRaw<T>& r, const uint8_t* __restrict__
     r.a = qp[0];
     r.b = qp[1];
     r.d = *reinterpret_cast<const unsigned short*>(base + P.p1 + row * P.s1 + 2 * q);
+  } else if constexpr (is_legacy_v<T>) {
+    legacy_load<T, false>(r, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, base + P.p2 + row * P.s2, q);
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) r.w[i] = reinterpret_cast<const uint4*>(base + row * P.s0 + 64 * q)[i];
@@ -558,6 +662,8 @@ __device__ __forceinline__ void dq_decode(const DqRaw<T>& r, int q, float* out) 
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int b8 = 0; b8 < 4; ++b8) out[4 * i + b8] = d * (float)(signed char)((qv[i] >> (8 * b8)) & 0xFF);
+  } else if constexpr (is_legacy_v<T>) {
+    legacy_decode<T>(r, out);
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -576,15 +682,25 @@ __device__ __forceinline__ void dq_decode(const DqRaw<T>& r, int q, float* out) 
   }
 }
 
-// Dispatch helper: call F.template operator()<T>() for the runtime type (wave-uniform).
+// Dispatch helper: call F.template operator()<T>() for the runtime type (wave-uniform). A type
+// outside the list runs nothing: host launchers check with dispatchable_type() and throw.
+LFK_HD bool dispatchable_type(int t) {
+  return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0 || t == T_Q4_0 || t == T_Q4_1 || t == T_Q5_0 ||
+         t == T_Q5_1 || t == T_F16 || t == T_F32;
+}
 #define LFK_DISPATCH_TYPE(t, ...)                          \
   switch (t) {                                             \
     case T_Q4_K: { constexpr int QT = T_Q4_K; __VA_ARGS__; } break; \
     case T_Q5_K: { constexpr int QT = T_Q5_K; __VA_ARGS__; } break; \
     case T_Q6_K: { constexpr int QT = T_Q6_K; __VA_ARGS__; } break; \
     case T_Q8_0: { constexpr int QT = T_Q8_0; __VA_ARGS__; } break; \
+    case T_Q4_0: { constexpr int QT = T_Q4_0; __VA_ARGS__; } break; \
+    case T_Q4_1: { constexpr int QT = T_Q4_1; __VA_ARGS__; } break; \
+    case T_Q5_0: { constexpr int QT = T_Q5_0; __VA_ARGS__; } break; \
+    case T_Q5_1: { constexpr int QT = T_Q5_1; __VA_ARGS__; } break; \
     case T_F16: { constexpr int QT = T_F16; __VA_ARGS__; } break;   \
-    default: { constexpr int QT = T_F32; __VA_ARGS__; } break;      \
+    case T_F32: { constexpr int QT = T_F32; __VA_ARGS__; } break;   \
+    default: break;                                                 \
   }
 
 }  // namespace lfk

@@ -219,6 +219,7 @@ QMat Engine::upload_matrix(const GGUFFile& f, const std::string& name, size_t r0
                            int n_expert) {
   const GGUFTensor* t = f.find(name);
   if (!t) throw std::runtime_error("missing tensor " + name);
+  if (n_expert > 0) check_expert_type(name, t->type);
   const size_t K_src = (size_t)t->ne[0];
   const size_t R_src = (size_t)t->ne[1];
   const int E = n_expert > 0 ? n_expert : 1;
@@ -243,6 +244,7 @@ QMat Engine::upload_gate_up(const GGUFFile& f, const std::string& gate, const st
   const GGUFTensor* tu = f.find(up);
   if (!tg || !tu) throw std::runtime_error("missing " + gate + " / " + up);
   if (tg->type != tu->type) throw std::runtime_error("gate/up projections must share a quant type");
+  if (n_expert > 0) check_expert_type(gate, tg->type);
   if (F % 32) throw std::runtime_error("n_ff per rank must be a multiple of 32");
   const size_t K = (size_t)tg->ne[0];
   const int E = n_expert > 0 ? n_expert : 1;
@@ -1246,7 +1248,8 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     a.nseg = 3;
     a.seg_base[1] = L.t_wk.base; a.seg_rows[1] = L.t_wk.rows; a.seg_out[1] = qkv_b_ + nq_;
     a.seg_base[2] = L.t_wv.base; a.seg_rows[2] = L.t_wv.rows; a.seg_out[2] = qkv_b_ + nq_ + nkvd_;
-    const int tq = L.t_wq.type, tk = L.t_wk.type, tv = L.t_wv.type;
+    // runs of equal tile16 format (Q4_0 / Q4_1 copies are in the Q4_K format, Q5_0 / Q5_1 in Q5_K's)
+    const int tq = t16_format(L.t_wq.type), tk = t16_format(L.t_wk.type), tv = t16_format(L.t_wv.type);
     a.seg_split = tk != tq ? 1 : tv != tq ? 2 : 3;
     a.type2 = tk != tq ? tk : tv != tq ? tv : 0;
     a.qkv_sk = true;
@@ -1263,7 +1266,7 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     std::vector<BmmArgs> rl;
     for (int i = 0; i < 3;) {
       int j = i + 1;
-      while (j < 3 && m[j]->type == m[i]->type) ++j;
+      while (j < 3 && t16_format(m[j]->type) == t16_format(m[i]->type)) ++j;
       for (int b0 = 0; b0 < B; b0 += kBmmMaxRows) {
         BmmArgs a;
         a.w = *m[i]; a.xh = xh_b_ + (size_t)b0 * d; a.ldh = d;

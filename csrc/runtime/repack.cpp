@@ -15,6 +15,7 @@ void repack_planar(int type, const uint8_t* src, size_t K_src, size_t r0, size_t
   const Planes P = planes_of(type, R_dst, K);
   switch (type) {
     case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_Q8_0: case T_F16: case T_BF16: case T_F32: break;
+    case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: break;
     default: throw std::runtime_error("repack: unsupported type");
   }
 #pragma omp parallel for schedule(static)
@@ -54,6 +55,27 @@ void repack_planar(int type, const uint8_t* src, size_t K_src, size_t r0, size_t
           std::memcpy(dst + P.p0 + dr * P.s0 + b * 32, blk + 2, 32);
         }
         break;
+      case T_Q4_0:
+      case T_Q4_1: {
+        const size_t sc = type == T_Q4_0 ? 2 : 4;  // d, or d and m
+        for (size_t b = 0; b < nb; ++b) {
+          const uint8_t* blk = srow + b * ti.bytes;
+          std::memcpy(dst + P.p1 + dr * P.s1 + b * sc, blk, sc);
+          std::memcpy(dst + P.p0 + dr * P.s0 + b * 16, blk + sc, 16);
+        }
+        break;
+      }
+      case T_Q5_0:
+      case T_Q5_1: {
+        const size_t sc = type == T_Q5_0 ? 2 : 4;
+        for (size_t b = 0; b < nb; ++b) {
+          const uint8_t* blk = srow + b * ti.bytes;
+          std::memcpy(dst + P.p2 + dr * P.s2 + b * sc, blk, sc);
+          std::memcpy(dst + P.p1 + dr * P.s1 + b * 4, blk + sc, 4);
+          std::memcpy(dst + P.p0 + dr * P.s0 + b * 16, blk + sc + 4, 16);
+        }
+        break;
+      }
       case T_F16:
       case T_BF16:
         std::memcpy(dst + dr * P.s0, srow, K * 2);

@@ -50,6 +50,10 @@ GGML_BLOCK = {
     GGMLType.F32: (1, 4),
     GGMLType.F16: (1, 2),
     GGMLType.BF16: (1, 2),
+    GGMLType.Q4_0: (32, 18),
+    GGMLType.Q4_1: (32, 20),
+    GGMLType.Q5_0: (32, 22),
+    GGMLType.Q5_1: (32, 24),
     GGMLType.Q8_0: (32, 34),
     GGMLType.Q4_K: (256, 144),
     GGMLType.Q5_K: (256, 176),
@@ -61,7 +65,11 @@ QK_K = 256
 # llama_ftype values written to general.file_type
 FTYPE_ALL_F32 = 0
 FTYPE_MOSTLY_F16 = 1
+FTYPE_MOSTLY_Q4_0 = 2
+FTYPE_MOSTLY_Q4_1 = 3
 FTYPE_MOSTLY_Q8_0 = 7
+FTYPE_MOSTLY_Q5_0 = 8
+FTYPE_MOSTLY_Q5_1 = 9
 FTYPE_MOSTLY_Q4_K_M = 15
 FTYPE_MOSTLY_Q5_K_M = 17
 FTYPE_MOSTLY_Q6_K = 18

@@ -1,5 +1,6 @@
 """NumPy reference implementation of the ggml block formats used by Q4_K_M /
-Q8_0 GGUF files: Q4_K, Q5_K, Q6_K, Q8_0 (+ F16/BF16/F32).
+Q8_0 and the legacy Q4_0 / Q4_1 / Q5_0 / Q5_1 GGUF files: Q4_K, Q5_K, Q6_K, Q8_0,
+Q4_0, Q4_1, Q5_0, Q5_1 (+ F16/BF16/F32).
 
 This is the *reference* every native path is tested against (T1 in SURVEY
 §4.3): the C++ CPU backend, the GPU repack and the HIP kernels must reproduce
@@ -7,6 +8,12 @@ This is the *reference* every native path is tested against (T1 in SURVEY
 
 Block layouts:
   Q8_0  34 B / 32 w : d f16 | qs int8[32]                 w = d*q
+  Q4_0  18 B / 32 w : d f16 | qs[16]                      w = d*(q-8)
+  Q4_1  20 B / 32 w : d f16 | m f16 | qs[16]              w = d*q + m
+  Q5_0  22 B / 32 w : d f16 | qh u32 | qs[16]             w = d*(q-16)   (5th bit from qh)
+  Q5_1  24 B / 32 w : d f16 | m f16 | qh u32 | qs[16]     w = d*q + m
+                      (weight j < 16: low nibble of qs[j], bit j of qh;
+                       weight j + 16: high nibble of qs[j], bit j + 16 of qh)
   Q4_K 144 B / 256 w: d f16 | dmin f16 | scales[12] | qs[128]
                       w = d*sc_j*q - dmin*m_j ; 6-bit (sc,m) packed, get_scale_min_k4
   Q5_K 176 B / 256 w: d | dmin | scales[12] | qh[32] | qs[128]  (5th bit from qh)
@@ -59,6 +66,37 @@ def _blocks(data: np.ndarray, ggml_type) -> np.ndarray:
     assert raw.size % bb == 0
     return raw.reshape(-1, bb)
 
+
+
+LEGACY_TYPES = (GGMLType.Q4_0, GGMLType.Q4_1, GGMLType.Q5_0, GGMLType.Q5_1)
+
+
+def _legacy_fields(b: np.ndarray, t):
+    """Blocks uint8 [nb, bytes] of a legacy type -> (d f16 [nb], m f16 [nb] or None, q uint8 [nb, 32])."""
+    has_m = t in (GGMLType.Q4_1, GGMLType.Q5_1)
+    has_h = t in (GGMLType.Q5_0, GGMLType.Q5_1)
+    o = 0
+    d = b[:, 0:2].copy().view(np.float16)[:, 0]
+    o += 2
+    m = None
+    if has_m:
+        m = b[:, o:o + 2].copy().view(np.float16)[:, 0]
+        o += 2
+    qh = None
+    if has_h:
+        qh = b[:, o:o + 4].copy().view("<u4")[:, 0]
+        o += 4
+    qs = b[:, o:o + 16]
+    q = np.concatenate([qs & 0xF, qs >> 4], axis=1).astype(np.uint8)
+    if has_h:
+        bits = ((qh[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1).astype(np.uint8)
+        q |= bits << 4
+    return d, m, q
+
+
+def _legacy_offset(t) -> int:
+    return 8 if t == GGMLType.Q4_0 else 16
+
 # ------------------------------------------------------------- dequantise
 
 
@@ -70,7 +108,7 @@ def dequantize(data, ggml_type, n_elements: int | None = None, arith: str = "f32
     rounded to f16 once, and every weight is ONE f16 rounding of q*scale + offset (a fused
     v_pk_fma_f16). Returned as float32 (exact f16 values)."""
     t = GGMLType(ggml_type)
-    if arith == "f16" and t in (GGMLType.Q8_0, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K):
+    if arith == "f16" and t in (GGMLType.Q8_0, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K) + LEGACY_TYPES:
         return _dequantize_f16(data, t, n_elements)
     if t == GGMLType.F32:
         return np.frombuffer(bytes(data) if not isinstance(data, np.ndarray) else data.tobytes(),
@@ -86,6 +124,13 @@ def dequantize(data, ggml_type, n_elements: int | None = None, arith: str = "f32
         d = b[:, 0:2].copy().view(np.float16).astype(np.float32)  # [nb,1]
         q = b[:, 2:34].view(np.int8).astype(np.float32)
         out = d * q
+    elif t in LEGACY_TYPES:
+        d, m, q = _legacy_fields(b, t)
+        d = d.astype(np.float32)[:, None]
+        if m is None:
+            out = d * (q.astype(np.float32) - np.float32(_legacy_offset(t)))
+        else:
+            out = d * q.astype(np.float32) + m.astype(np.float32)[:, None]
     elif t in (GGMLType.Q4_K, GGMLType.Q5_K):
         d = b[:, 0:2].copy().view(np.float16).astype(np.float32)
         dmin = b[:, 2:4].copy().view(np.float16).astype(np.float32)
@@ -144,6 +189,12 @@ def _dequantize_f16(data, t, n_elements):
         d = b[:, 0:2].copy().view(np.float16).astype(np.float64)
         q = b[:, 2:34].view(np.int8).astype(np.float64)
         out = h(d * q)
+    elif t in LEGACY_TYPES:
+        # the tile16 copy stores (d, -8d) / (d, -16d) / (d, m) as an f16 pair per block
+        d, m, q = _legacy_fields(b, t)
+        a = d.astype(np.float64)
+        off = h(-_legacy_offset(t) * a) if m is None else m.astype(np.float64)
+        out = h(q.astype(np.float64) * a[:, None] + off[:, None])
     elif t in (GGMLType.Q4_K, GGMLType.Q5_K):
         d = b[:, 0:2].copy().view(np.float16).astype(np.float64)[:, 0]
         dmin = b[:, 2:4].copy().view(np.float16).astype(np.float64)[:, 0]
@@ -210,6 +261,35 @@ def quantize(x: np.ndarray, ggml_type) -> np.ndarray:
         out[:, 0:2] = _f16(d).reshape(-1, 1).view(np.uint8)
         out[:, 2:] = q.view(np.uint8)
         return out.reshape(-1)
+    if t in LEGACY_TYPES:
+        nmax = 15 if t in (GGMLType.Q4_0, GGMLType.Q4_1) else 31
+        xb = x.reshape(-1, 32)
+        nb = xb.shape[0]
+        if t in (GGMLType.Q4_0, GGMLType.Q5_0):
+            # ggml: the value of largest magnitude maps to the most negative level
+            off = _legacy_offset(t)
+            vmax = np.take_along_axis(xb, np.argmax(np.abs(xb), axis=1)[:, None], axis=1)[:, 0]
+            d16 = _f16(vmax / -off)
+            m16 = None
+            df = d16.astype(np.float32)
+            inv = np.where(df != 0, 1.0 / np.where(df != 0, df, 1), 0)
+            q = np.clip(np.rint(xb * inv[:, None]) + off, 0, nmax).astype(np.uint8)
+        else:
+            mn = xb.min(axis=1)
+            d16 = _f16((xb.max(axis=1) - mn) / nmax)
+            m16 = _f16(mn)
+            df = d16.astype(np.float32)
+            inv = np.where(df > 0, 1.0 / np.where(df > 0, df, 1), 0)
+            q = np.clip(np.rint((xb - m16.astype(np.float32)[:, None]) * inv[:, None]), 0, nmax).astype(np.uint8)
+        cols = [d16.reshape(-1, 1).view(np.uint8)]
+        if m16 is not None:
+            cols.append(m16.reshape(-1, 1).view(np.uint8))
+        if nmax == 31:
+            qh = (((q >> 4) & 1).astype(np.uint32) << np.arange(32, dtype=np.uint32)[None, :]).sum(
+                axis=1, dtype=np.uint32)
+            cols.append(qh.astype("<u4").reshape(-1, 1).view(np.uint8))
+        cols.append((q[:, :16] & 0xF) | ((q[:, 16:] & 0xF) << 4))
+        return np.concatenate(cols, axis=1).reshape(-1)
     if t in (GGMLType.Q4_K, GGMLType.Q5_K):
         nmax = 15 if t == GGMLType.Q4_K else 31
         xb = x.reshape(-1, 8, 32)
@@ -298,6 +378,14 @@ def random_blocks(ggml_type, n_elements: int, rng: np.random.Generator, std: flo
         d = np.full(nb, std / np.sqrt(var), np.float32) * rng.uniform(0.5, 1.5, nb).astype(np.float32)
         raw[:, 0:2] = _f16(d).reshape(-1, 1).view(np.uint8)
         raw[:, 2:4] = _f16(d * nmax / 2).reshape(-1, 1).view(np.uint8)
+    elif t in LEGACY_TYPES:
+        # q uniform in [0, nmax]: variance (nmax + 1)^2 / 12 (the offset or m centres it)
+        nmax = 15 if t in (GGMLType.Q4_0, GGMLType.Q4_1) else 31
+        d = np.full(nb, std / np.sqrt(((nmax + 1) ** 2 - 1) / 12.0), np.float32) * \
+            rng.uniform(0.5, 1.5, nb).astype(np.float32)
+        raw[:, 0:2] = _f16(d).reshape(-1, 1).view(np.uint8)
+        if t in (GGMLType.Q4_1, GGMLType.Q5_1):
+            raw[:, 2:4] = _f16(-d * nmax / 2).reshape(-1, 1).view(np.uint8)
     elif t == GGMLType.Q6_K:
         # scales int8 uniform [-128,127] (rms ~73.9); q-32 uniform [-32,31] (rms ~18.5)
         d = np.full(nb, std / (73.9 * 18.5), np.float32) * rng.uniform(0.5, 1.5, nb).astype(np.float32)

@@ -9,6 +9,9 @@ follow the upstream Q4_K_M mix rule::
     attn_v, ffn_down -> Q6_K when use_more_bits (70B: non-bumped attn_v -> Q5_K)
     8-expert models  -> attn_k/attn_v Q8_0
     output.weight    -> Q6_K ; token_embd -> Q4_K ; norms/router -> F32
+
+The legacy file types ("q4_0", "q4_1", "q5_0", "q5_1") are uniform: every 2-D tensor,
+token_embd included, has the file's type and output.weight is Q6_K, as llama.cpp writes them.
 """
 from __future__ import annotations
 
@@ -19,7 +22,8 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .constants import (FTYPE_MOSTLY_Q4_K_M, FTYPE_MOSTLY_Q8_0, GGMLType, GGUFValueType,
+from .constants import (FTYPE_MOSTLY_Q4_0, FTYPE_MOSTLY_Q4_1, FTYPE_MOSTLY_Q4_K_M, FTYPE_MOSTLY_Q5_0,
+                        FTYPE_MOSTLY_Q5_1, FTYPE_MOSTLY_Q8_0, GGMLType, GGUFValueType,
                         TOKEN_TYPE_BYTE, TOKEN_TYPE_CONTROL, TOKEN_TYPE_NORMAL)
 from .quants import random_blocks
 from .writer import GGUFWriter
@@ -61,7 +65,7 @@ class ModelSpec:
     n_vocab: int
     rope_base: float
     tokenizer: str            # "bpe" | "spm"
-    quant: str                # "q4_k_m" | "q8_0" | "f32" | "mixed-test"
+    quant: str                # "q4_k_m" | "q8_0" | "f32" | "mixed-test" | LEGACY_QUANTS | "legacy-mixed-test"
     n_expert: int = 0
     n_expert_used: int = 0
     n_ctx_train: int = 8192
@@ -74,6 +78,14 @@ class ModelSpec:
     def head_dim(self) -> int:
         return self.n_embd // self.n_head
 
+
+# uniform legacy (32-weight block) file types: quant name -> (tensor type, general.file_type)
+LEGACY_QUANTS = {
+    "q4_0": (GGMLType.Q4_0, FTYPE_MOSTLY_Q4_0),
+    "q4_1": (GGMLType.Q4_1, FTYPE_MOSTLY_Q4_1),
+    "q5_0": (GGMLType.Q5_0, FTYPE_MOSTLY_Q5_0),
+    "q5_1": (GGMLType.Q5_1, FTYPE_MOSTLY_Q5_1),
+}
 
 SPECS: Dict[str, ModelSpec] = {
     "llama3-8b-q4_k_m": ModelSpec("Llama-3-8B", 4096, 32, 32, 8, 14336, 128256, 500000.0, "bpe", "q4_k_m"),
@@ -139,6 +151,19 @@ SPECS: Dict[str, ModelSpec] = {
                                  n_ctx_train=512),
 }
 
+# the legacy 32-weight block formats (Q4_0 / Q4_1 / Q5_0 / Q5_1) over existing shapes
+SPECS.update({
+    "tiny-llama3-q4_0": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama3-q4_0", quant="q4_0"),
+    "tiny-llama3-q5_1": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama3-q5_1", quant="q5_1"),
+    "tiny-llama3-legacy-mixed": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama3-legacy-mixed",
+                                        quant="legacy-mixed-test"),
+    "tiny-legacy-mixed-1l": replace(SPECS["tiny-mixed-1l"], name="tiny-legacy-mixed-1l",
+                                    quant="legacy-mixed-test"),
+    # n_ff = 576: the down projection's K is not a multiple of 256 (no tile16 copy)
+    "tiny-q5_0-oddff": replace(SPECS["tiny-q8-oddff"], name="tiny-q5_0-oddff", quant="q5_0"),
+    "llama3-8b-q4_0": replace(SPECS["llama3-8b-q4_k_m"], name="Llama-3-8B-Q4_0", quant="q4_0"),
+})
+
 
 def use_more_bits(i: int, n: int) -> bool:
     return i < n // 8 or i >= 7 * n // 8 or (i - n // 8) % 3 == 2
@@ -153,6 +178,15 @@ def tensor_types(spec: ModelSpec, layer: int) -> Dict[str, GGMLType]:
     if q == "f32":
         t = GGMLType.F32
         return {k: t for k in ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")}
+    if q in LEGACY_QUANTS:
+        t = LEGACY_QUANTS[q][0]
+        return {k: t for k in ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")}
+    if q == "legacy-mixed-test":  # the four legacy formats and Q8_0 in one model
+        cyc = [GGMLType.Q4_0, GGMLType.Q4_1, GGMLType.Q5_0, GGMLType.Q5_1, GGMLType.Q8_0]
+        names = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_down")
+        out = {k: cyc[(layer + j) % 5] for j, k in enumerate(names)}
+        out["ffn_up"] = out["ffn_gate"]  # gate/up are one interleaved matrix on the GPU
+        return out
     if q == "mixed-test":  # every quant format in one model, to test all kernels end to end
         cyc = [GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K, GGMLType.Q8_0]
         names = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_down")
@@ -232,6 +266,10 @@ def tensor_plan(spec: ModelSpec, n_vocab: int) -> List[Tuple[str, GGMLType, Tupl
         emb_t, out_t = GGMLType.Q8_0, GGMLType.Q8_0
     elif spec.quant == "f32":
         emb_t, out_t = GGMLType.F32, GGMLType.F32
+    elif spec.quant in LEGACY_QUANTS:
+        emb_t, out_t = LEGACY_QUANTS[spec.quant][0], GGMLType.Q6_K
+    elif spec.quant == "legacy-mixed-test":
+        emb_t, out_t = GGMLType.Q5_0, GGMLType.Q6_K
     else:
         emb_t, out_t = GGMLType.Q4_K, GGMLType.Q6_K
     plan = [("token_embd.weight", emb_t, (d, n_vocab))]
@@ -260,8 +298,12 @@ def tensor_plan(spec: ModelSpec, n_vocab: int) -> List[Tuple[str, GGMLType, Tupl
 
 def hparams_metadata(spec: ModelSpec, n_vocab: int) -> Dict:
     a = "llama"
+    if spec.quant in LEGACY_QUANTS:
+        ftype = LEGACY_QUANTS[spec.quant][1]
+    else:
+        ftype = FTYPE_MOSTLY_Q8_0 if spec.quant == "q8_0" else FTYPE_MOSTLY_Q4_K_M
     md = {"general.architecture": a, "general.name": spec.name + " (synthetic random-init)",
-          "general.file_type": FTYPE_MOSTLY_Q8_0 if spec.quant == "q8_0" else FTYPE_MOSTLY_Q4_K_M,
+          "general.file_type": ftype,
           f"{a}.context_length": spec.n_ctx_train, f"{a}.embedding_length": spec.n_embd,
           f"{a}.block_count": spec.n_layer, f"{a}.feed_forward_length": spec.n_ff,
           f"{a}.rope.dimension_count": spec.head_dim, f"{a}.attention.head_count": spec.n_head,

@@ -28,7 +28,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 EXT = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 
-HIP_SOURCES = ["kernels/gemv.hip", "kernels/attention.hip", "kernels/sampler.hip", "kernels/gemm.hip",
+HIP_SOURCES = ["kernels/gemv.hip", "kernels/gemv_legacy.hip", "kernels/attention.hip", "kernels/sampler.hip", "kernels/gemm.hip",
                "kernels/misc.hip", "kernels/bmm.hip",
                "kernels/moe.hip", "kernels/p2p_allreduce.hip"]
 HOST_HIP_SOURCES = ["runtime/engine.cpp", "runtime/p2p.cpp", "runtime/scheduler.cpp",

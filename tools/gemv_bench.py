@@ -14,12 +14,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 Q4_K, Q5_K, Q6_K, Q8_0 = 12, 13, 14, 8
+Q4_0, Q4_1, Q5_0, Q5_1 = 2, 3, 6, 7
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--only", default="")
+    ap.add_argument("--only", default="", help="comma-separated substrings of the kernel names to run")
     ap.add_argument("--eager", action="store_true", help="plain launches (for rocprofv3 kernel traces)")
     ap.add_argument("--debug", action="store_true", help="also time kernel prefixes (stage breakdown)")
     args = ap.parse_args()
@@ -29,7 +30,7 @@ def main():
     res = {}
 
     def timed(name, fn, nbytes):
-        if args.only and args.only not in name:
+        if args.only and not any(o in name for o in args.only.split(",")):
             return
         if args.eager:
             for _ in range(args.reps):
@@ -81,8 +82,13 @@ def main():
         ("lmhead_q6k_128256x4096", Q6_K, V, d, 0, True),
         ("wq_q4k_4096x4096_norm", Q4_K, d, d, 0, True),
         ("wv_q6k_1024x4096_norm", Q6_K, 1024, d, 0, True),
+        # the legacy 32-weight blocks beside their K-quant counterparts (Q4_0 is 4.5 bits per weight as Q4_K)
+        ("wo_q40_4096x4096_add", Q4_0, d, d, 1, False),
+        ("gateup_q40_28672x4096_swiglu", Q4_0, 2 * F, d, 2, True),
+        ("down_q40_4096x14336_add", Q4_0, d, F, 1, False),
+        ("gateup_q51_28672x4096_swiglu", Q5_1, 2 * F, d, 2, True),
     ]:
-        if args.only and args.only not in name:
+        if args.only and not any(o in name for o in args.only.split(",")):
             continue
         nb = hip.qbytes(t, R, K)
         ws = [mat(t, R, K, 1000 * len(bufs) + c + 1)[0] for c in range(copies(nb))]
@@ -124,6 +130,18 @@ def main():
                          pos.data_ptr(), rope.data_ptr(), st)
         timed(name, fn, nq_b + nk_b + nvb)
     del wqs, wks, wv4s, wv6s
+    lq = [mat(Q4_0, d, d, 500 + c)[0] for c in range(NC)]
+    lk = [mat(Q4_0, 1024, d, 600 + c)[0] for c in range(NC)]
+    lv = [mat(Q4_0, 1024, d, 700 + c)[0] for c in range(NC)]
+
+    def fn_l(st=s):
+        c = qctr[0] % NC
+        qctr[0] += 1
+        hip.gemv_qkv(lq[c].data_ptr(), Q4_0, lk[c].data_ptr(), Q4_0, lv[c].data_ptr(), Q4_0, d, 1024, d,
+                     x.data_ptr(), nw.data_ptr(), 1e-5, q.data_ptr(), kc.data_ptr(), vc.data_ptr(), n_ctx, hd,
+                     pos.data_ptr(), rope.data_ptr(), st)
+    timed("qkv_q40_all", fn_l, hip.qbytes(Q4_0, d, d) + 2 * hip.qbytes(Q4_0, 1024, d))
+    del lq, lk, lv
 
     # decode attention, 32 q heads on 8 kv heads, hd 128, at a few KV lengths
     part = torch.empty(hip.attn_decode_workspace_floats(n_ctx, 32, hd), device="cuda")
