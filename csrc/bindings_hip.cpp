@@ -353,9 +353,10 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("swiglu_group") = 32);
   m.def("bmm", [](uintptr_t w, int type, int rows, int K, uintptr_t xh, int ldh, uintptr_t out, int ldo, int B,
                   uintptr_t stream, int debug, uintptr_t h_out, int ldh_out, uintptr_t xf, int ldxf,
-                  uintptr_t norm, float eps, bool store_out, uintptr_t dbg_clk) {
+                  uintptr_t norm, float eps, bool store_out, uintptr_t dbg_clk, int tr) {
     BmmArgs a;
     a.debug = debug;
+    a.tr = tr;
     a.dbg_clk = P<long long>(dbg_clk);
     a.w = make_qmat(P<void>(w), type, rows, K);
     a.xh = P<__half>(xh); a.ldh = ldh; a.out = P<float>(out); a.ldo = ldo; a.n_out = rows; a.B = B;
@@ -371,15 +372,16 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("w"), py::arg("type"), py::arg("rows"), py::arg("K"), py::arg("xh"), py::arg("ldh"), py::arg("out"),
      py::arg("ldo"), py::arg("B"), py::arg("stream"), py::arg("debug") = 0, py::arg("h_out") = 0,
      py::arg("ldh_out") = 0, py::arg("xf") = 0, py::arg("ldxf") = 0, py::arg("norm") = 0, py::arg("eps") = 1e-5f,
-     py::arg("store_out") = false, py::arg("dbg_clk") = 0);
+     py::arg("store_out") = false, py::arg("dbg_clk") = 0, py::arg("tr") = -1);
   // the gate/up + down chain in one launch (tests/test_kernels_gpu.py::test_bmm_ffn_chain_*): gate/up
   // rows in the SwiGLU tile16 copy (wg, 2F x K), down (wd, K x F) over the f16 SwiGLU output hout
   // [B][F]; out [B][K] accumulates; cnt >= 64 ints, zeroed by the caller
   m.def("chain_layout", []() { return std::make_tuple(kChainStride, kChainXcds, kChainInts); });
   m.def("bmm_ffn_chain", [](uintptr_t wg, int tg, int F, int K, uintptr_t xh, uintptr_t xf, uintptr_t norm, float eps,
                             uintptr_t wd, int td, uintptr_t hout, uintptr_t out, int B, uintptr_t cnt,
-                            uintptr_t stream) {
+                            uintptr_t stream, int tr) {
     BmmArgs gu, dn;
+    dn.tr = tr;
     gu.w = make_qmat(P<void>(wg), tg, 2 * F, K);
     gu.xh = P<__half>(xh); gu.ldh = K; gu.n_out = 2 * F; gu.B = B;
     gu.swiglu_epi = true; gu.h_out = P<__half>(hout); gu.ldh_out = F;
@@ -393,13 +395,14 @@ PYBIND11_MODULE(_hip, m) {
     hip_ok("bmm_ffn_chain");
   }, py::arg("wg"), py::arg("tg"), py::arg("F"), py::arg("K"), py::arg("xh"), py::arg("xf"), py::arg("norm"),
      py::arg("eps"), py::arg("wd"), py::arg("td"), py::arg("hout"), py::arg("out"), py::arg("B"), py::arg("cnt"),
-     py::arg("stream"));
+     py::arg("stream"), py::arg("tr") = -1);
   // Wo -> gate/up -> down in one launch (tests/test_kernels_gpu.py::test_bmm_wo_ffn_chain_*): Wo adds
   // W_o . xa into the residual rows `resid`, the gate/up stages norm(resid), the down adds into resid
   m.def("bmm_wo_ffn_chain", [](uintptr_t wo, int to, int Kwo, uintptr_t xa, uintptr_t wg, int tg, int F, int K,
                                uintptr_t norm, float eps, uintptr_t wd, int td, uintptr_t xh, uintptr_t hout,
-                               uintptr_t resid, int B, uintptr_t cnt, uintptr_t stream) {
+                               uintptr_t resid, int B, uintptr_t cnt, uintptr_t stream, int tr) {
     BmmArgs o, gu, dn;
+    o.tr = dn.tr = tr;
     o.w = make_qmat(P<void>(wo), to, K, Kwo);
     o.xh = P<__half>(xa); o.ldh = Kwo; o.out = P<float>(resid); o.ldo = K; o.n_out = K; o.B = B;
     gu.w = make_qmat(P<void>(wg), tg, 2 * F, K);
@@ -413,7 +416,7 @@ PYBIND11_MODULE(_hip, m) {
     hip_ok("bmm_wo_ffn_chain");
   }, py::arg("wo"), py::arg("to"), py::arg("Kwo"), py::arg("xa"), py::arg("wg"), py::arg("tg"), py::arg("F"),
      py::arg("K"), py::arg("norm"), py::arg("eps"), py::arg("wd"), py::arg("td"), py::arg("xh"), py::arg("hout"),
-     py::arg("resid"), py::arg("B"), py::arg("cnt"), py::arg("stream"));
+     py::arg("resid"), py::arg("B"), py::arg("cnt"), py::arg("stream"), py::arg("tr") = -1);
   m.def("bmm_norm_fits", &bmm_norm_fits);
   m.def("bmm_supported", &bmm_supported);
   m.def("t16_bytes", &t16_bytes);
@@ -576,8 +579,9 @@ PYBIND11_MODULE(_hip, m) {
   m.def("bmm_qkv_sk", [](uintptr_t wq, int tq, int nq, uintptr_t wk, int tk, uintptr_t wv, int tv, int nkv, int K,
                          uintptr_t xf, int ldxf, uintptr_t norm, float eps, int B, uintptr_t out, int ldo,
                          uintptr_t ss_out, uintptr_t pos, uintptr_t rope, int head_dim, int n_ctx, uintptr_t stream,
-                         uintptr_t zero, int zero_n, uintptr_t dbg_clk) {
+                         uintptr_t zero, int zero_n, uintptr_t dbg_clk, int tr) {
     BmmArgs a;
+    a.tr = tr;
     a.w = make_qmat(P<void>(wq), tq, nq, K); a.n_out = nq; a.out = P<float>(out); a.ldo = ldo; a.B = B;
     a.nseg = 3;
     a.seg_base[1] = P<uint8_t>(wk); a.seg_rows[1] = nkv; a.seg_out[1] = P<float>(out) + nq;
@@ -594,7 +598,8 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("wq"), py::arg("tq"), py::arg("nq"), py::arg("wk"), py::arg("tk"), py::arg("wv"), py::arg("tv"),
      py::arg("nkv"), py::arg("K"), py::arg("xf"), py::arg("ldxf"), py::arg("norm"), py::arg("eps"), py::arg("B"),
      py::arg("out"), py::arg("ldo"), py::arg("ss_out"), py::arg("pos"), py::arg("rope"), py::arg("head_dim"),
-     py::arg("n_ctx"), py::arg("stream"), py::arg("zero") = 0, py::arg("zero_n") = 0, py::arg("dbg_clk") = 0);
+     py::arg("n_ctx"), py::arg("stream"), py::arg("zero") = 0, py::arg("zero_n") = 0, py::arg("dbg_clk") = 0,
+     py::arg("tr") = -1);
   m.def("bmm_qkv_sk_supported", &bmm_qkv_sk_supported);
   m.def("bmm_qkv_sk_defers_rope", &bmm_qkv_sk_defers_rope);
   m.def("attn_decode_workspace_floats", &attn_decode_workspace_floats);

@@ -8,12 +8,21 @@
 // Why MFMA: with 2-16 rows the integer-dot GEMV (bgemv.hip) does B dot products per decoded
 // weight on the VALU and ran VALU/epilogue-bound (6.2 ms per 8B step at B = 8,
 // profiles/README.md). Here a wave owns a 16-row weight tile and feeds it to
-// v_mfma_f32_16x16x32_f16 as the A operand, the activation rows as B: the matrix core does
-// all 16 columns in the same 16 cycles, so the per-weight work is the dequantisation only
-// (independent of B) and the weights stay ONE HBM stream. The kernel is bound by instruction
-// issue (profiles/README.md, r2g/r2i), so the dequantisation is counted per instruction.
+// v_mfma_f32_16x16x32_f16 against the activation rows: the matrix core does all 16 activation
+// rows in the same 16 cycles, so the per-weight work is the dequantisation only (independent of
+// B) and the weights stay ONE HBM stream. The kernel is bound by instruction issue
+// (profiles/README.md, r2g/r2i), so the dequantisation is counted per instruction.
 //
-// Dequantisation straight into MFMA fragments: lane l holds A[row l&15][k = 8(l>>4) + j];
+// Operand roles: the A and B lane maps of this MFMA are the same function of (lane & 15, k =
+// 8(lane>>4) + j), so one pair of fragments serves both orientations (bmm_step's TR):
+//   weights as A, x as B (the SwiGLU, RoPE / KV-append and head epilogues, bmm_kernel):
+//     lane (kq, r16) ends with C[weight row 4kq + i][activation r16], i = 0..3;
+//   x as A, weights as B (TR: the wave-owned epilogues that add split-K partials - Wo, down, the
+//   deferred-RoPE split-K Q|K|V; LFK_BMM_TR=0 / BmmArgs::tr = 0 restore the first form):
+//     lane (kq, r16) ends with C[activation 4kq + i][weight row r16] - a lane row holds 16
+//     adjacent outputs of one activation row, one whole 64-byte line per atomic request.
+//
+// Dequantisation straight into MFMA fragments: lane l holds W[row l&15][k = 8(l>>4) + j];
 // lane group kq = l>>4 takes chunk 8s + 4h + kq (32 weights: a low and a high 16-run) of its
 // row at step s. Quant bytes are masked to one value per byte (low / high nibbles, plus the
 // Q5_K / Q6_K high bits), one v_perm_b32 per pair puts two bytes under the f16 exponent of
@@ -21,7 +30,7 @@
 // (d*sc, -dmin*m) - pre-decoded per sub-block in the Q4_K tile16 copy. A pair holds bytes
 // (0, 2) or (1, 3) of a dword, so the k order inside each 4-group is (0, 2, 1, 3); x is
 // written in that order. MFMA m of a chunk takes 8 weights of ONE run (low run 0-7 / 8-15,
-// then high run 0-7 / 8-15): its B operand is one 16-byte LDS read as it stands.
+// then high run 0-7 / 8-15): its x operand is one 16-byte LDS read as it stands.
 //
 // Work items are (16-row tile, K part); partial tiles are added to `out` atomically (split-K
 // keeps >= 2 waves per SIMD busy on every projection shape, including the 256-tile Wo /
@@ -487,8 +496,15 @@ __device__ __forceinline__ int raw_word(const BRawT<T>& w) {
 // IL: all 8 B-operand LDS reads first (the dequantisation then covers their latency; read per
 // chunk, each group of 4 was waited for right behind its issue), both chunks dequantised, and the
 // two accumulators' MFMAs alternating (one chain after the other stalled on every MFMA)
-template <int QT, bool RAW = false, bool IL = false>
+// TR: the two operands swapped - the x fragment as A, the weights as B (both lane maps are the same
+// function of (lane & 15, k = 8 (lane >> 4) + j)): the same products, the tile transposed
+template <int QT, bool RAW = false, bool IL = false, bool TR = false>
 __device__ __forceinline__ void bmm_step(const BRawT<QT>* wc, int s, int kq, const __half* xrow, f4_t& acc, f4_t& acc2) {
+  auto mfma = [](uint4 w, uint4 x, f4_t c) {
+    const h8_t wf = __builtin_bit_cast(h8_t, w), xf = __builtin_bit_cast(h8_t, x);
+    if constexpr (TR) return __builtin_amdgcn_mfma_f32_16x16x32_f16(xf, wf, c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, xf, c, 0, 0, 0);
+  };
   // MFMA m takes 8 weights of ONE run: the low run's 0-7 / 8-15 (m = 0 / 1), then the high run's
   // (m = 2 / 3) - pairs of quant dwords 2(m % 2), 2(m % 2) + 1 - so its B operand is the 16-byte
   // LDS read as it stands (taking 4 halves from each run cost 3 v_mov per MFMA)
@@ -520,10 +536,8 @@ __device__ __forceinline__ void bmm_step(const BRawT<QT>* wc, int s, int kq, con
     deq(1, 8 * s + 4 + kq, F1);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_t, frag(F0, m)),
-                                                   __builtin_bit_cast(h8_t, xr[0][m]), acc, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_t, frag(F1, m)),
-                                                    __builtin_bit_cast(h8_t, xr[1][m]), acc2, 0, 0, 0);
+      acc = mfma(frag(F0, m), xr[0][m], acc);
+      acc2 = mfma(frag(F1, m), xr[1][m], acc2);
     }
   } else {
 #pragma unroll
@@ -539,8 +553,7 @@ __device__ __forceinline__ void bmm_step(const BRawT<QT>* wc, int s, int kq, con
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         f4_t& ac = h == 0 ? acc : acc2;
-        ac = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_t, frag(F, m)),
-                                                    __builtin_bit_cast(h8_t, xr[m]), ac, 0, 0, 0);
+        ac = mfma(frag(F, m), xr[m], ac);
       }
     }
   }
@@ -1204,7 +1217,15 @@ static bool bmm_il() {
   }();
   return v;
 }
-
+// transposed tiles (wt_body's TR) in the epilogues that add split-K partials;
+// LFK_BMM_TR=0 for the A/B; BmmArgs::tr picks it per call (tests)
+static bool bmm_tr(const BmmArgs& a) {
+  static const bool v = [] {
+    const char* e = std::getenv("LFK_BMM_TR");
+    return !(e && e[0] == '0');
+  }();
+  return a.tr < 0 ? v : a.tr != 0;
+}
 
 // SK: the split-K Q|K|V launch (segments, RoPE'd atomic partials, per-part norm staging) - a
 // compile-time switch: the generic code paths cost the gate/up / Wo / down instantiations ~0.7 us
@@ -1218,8 +1239,11 @@ static bool bmm_il() {
 // K part's gate/up tiles, kChainWaitWo: wait for every Wo block) - as a runtime branch the staging
 // paths with the weights issued before x merged into the step loop, and the waitcnt pass then
 // drained the weight ring at every round of every wave-owned kernel
+// TR: the transposed tile (bmm_step's TR) in the epilogues that add fp32 partials - EPI 2, the
+// split-K Q|K|V with its RoPE deferred (SK && IL), and EPI 0 when the launch has no SwiGLU epilogue
+// and no folded norm (the launchers send no other shape here)
 template <int QT, int PD, bool SK, int NW = 8, bool MOE = false, bool XF = false, int DBG = 0, bool IL = false,
-          int EPI = 0, int CR = 0>
+          int EPI = 0, int CR = 0, bool TR = false>
 __device__ __forceinline__ void wt_body(const BmmArgs& a, const int run, const int bid, const int nblk) {
   constexpr int R = PD + 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1444,7 +1468,27 @@ __device__ __forceinline__ void wt_body(const BmmArgs& a, const int run, const i
   const __half* xrow = xs + (col_ok ? r16 : 0) * ldx - k0;  // indexed by global k
   f4_t acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
   int ci = 0, cstep = 0;  // compute cursor (step s0 + cstep of tile ci)
-  auto finish = [&]() {   // tile ci is complete in acc + acc2: C[row 4kq + i][col r16]
+  // tile ci is complete in acc + acc2: C[weight row 4kq + i][activation column r16]; TR:
+  // C[activation row 4kq + i][weight row r16] - the 16 lanes of a lane row hold 16 adjacent outputs
+  // of ONE activation row, so each atomic instruction covers B whole 64-byte segments instead of 16
+  // bytes of each of B lines, four times over: float atomics leave L2 as one memory-side request per
+  // 64-byte line touched, whatever part of the line is filled (TCC_EA0_ATOMIC per Wo launch at B = 6:
+  // 49152 -> 12288, profiles/README.md)
+  auto add_tr = [&](float* o, int row0, int n_out, bool atomic) {  // o: the segment's out, row0: the tile's first weight row
+    if (row0 + r16 < n_out) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int b = 4 * kq + i;
+        if (b < a.B) {
+          float* p = o + (size_t)b * a.ldo + row0 + r16;
+          if (atomic) atomicAdd(p, acc[i]);
+          else if (a.store_out) *p = acc[i];
+          else *p += acc[i];  // one owner per (row, column)
+        }
+      }
+    }
+  };
+  auto finish = [&]() {
     acc += acc2;
     if (a.debug == 3) {  // microbenchmark: no epilogue writes (an empty asm keeps the tile live)
       asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]));
@@ -1452,7 +1496,9 @@ __device__ __forceinline__ void wt_body(const BmmArgs& a, const int run, const i
       acc2 = acc;
       return;
     }
-    if (a.xf && !SK) acc *= cs;
+    if constexpr (!TR) {
+      if (a.xf && !SK) acc *= cs;
+    }
     const int gt = tile_of(ci);
     if constexpr (SK) {
       const int sg = seg_of(gt), kind = sg == 0 ? a.qkv.kind[0] : sg == 1 ? a.qkv.kind[1] : a.qkv.kind[2];
@@ -1470,12 +1516,14 @@ __device__ __forceinline__ void wt_body(const BmmArgs& a, const int run, const i
       if constexpr (!IL) {
         if (ci + 1 < nt) rope_load(ci + 1);
       }
-      if (col_ok) {
+      if constexpr (TR) {  // (IL only: y = acc)
+        add_tr(sg == 0 ? a.out : sg == 1 ? a.seg_out[1] : a.seg_out[2], (gt - seg_first(sg)) * 16, n_out, true);
+      } else if (col_ok) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           if (row0 + i < n_out) atomicAdd(o + row0 + i, y[i]);
       }
-    } else if (EPI == 1 || (EPI == 0 && a.swiglu_epi)) {
+    } else if (EPI == 1 || (EPI == 0 && !TR && a.swiglu_epi)) {
       // rows 0-7 (lanes 0-31): gate of features 8 gt + 4 kq + i; rows 8-15 (lanes 32-63): up
       f4_t up;
 #pragma unroll
@@ -1498,6 +1546,7 @@ __device__ __forceinline__ void wt_body(const BmmArgs& a, const int run, const i
         if (lane == 0) __hip_atomic_fetch_add(a.chain_cnt + (gt / a.chain_tpp * kChainXcds + (xcc_id() & (kChainXcds - 1))) * kChainStride, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     } else if (EPI == 3) {  // one part, plain stores (the batched head's logits): no loads in the loop
+      // (the transposed tile - whole 64-byte segments - measured 79.0 vs 78.4 us per head launch: not used)
       if (col_ok) {
         float* o = a.out + (size_t)r16 * a.ldo;
 #pragma unroll
@@ -1507,7 +1556,9 @@ __device__ __forceinline__ void wt_body(const BmmArgs& a, const int run, const i
         }
       }
     } else if (EPI == 2) {  // split-K only: fp32 atomics, no read-modify-write path
-      if (col_ok) {
+      if constexpr (TR) {
+        add_tr(a.out, gt * 16, a.n_out, true);
+      } else if (col_ok) {
         float* o = a.out + (size_t)r16 * a.ldo;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1515,6 +1566,8 @@ __device__ __forceinline__ void wt_body(const BmmArgs& a, const int run, const i
           if (row < a.n_out) atomicAdd(o + row, acc[i]);
         }
       }
+    } else if (TR) {
+      add_tr(a.out, gt * 16, a.n_out, kparts > 1);
     } else if (col_ok) {
       float* o = a.out + (size_t)r16 * a.ldo;
 #pragma unroll
@@ -1540,7 +1593,7 @@ __device__ __forceinline__ void wt_body(const BmmArgs& a, const int run, const i
     if constexpr (DBG == 4 || DBG == 5)
       asm volatile("" ::"v"(raw_word<QT>(buf[r][0])), "v"(raw_word<QT>(buf[r][1])));
     else
-      bmm_step<QT, DBG == 7, IL>(buf[r], s0 + cstep, kq, xrow, acc, acc2);
+      bmm_step<QT, DBG == 7, IL, TR>(buf[r], s0 + cstep, kq, xrow, acc, acc2);
     if (++cstep == ns) {
       finish();
       cstep = 0;
@@ -1587,10 +1640,10 @@ __device__ __forceinline__ void wt_body(const BmmArgs& a, const int run, const i
 // parameter made the compiler copy the whole block to scratch, as in bmm_kernel)
 // (PD > 2: one block per CU - the launchers' LDS request - so a register budget of 256, not 128)
 // EPI: the epilogue as a compile-time kind (0 any, 1 SwiGLU, 2 split-K atomics, 3 one-part plain stores)
-template <int QT, int PD, bool MOE = false, bool XF = false, bool IL = false, int EPI = 0>
+template <int QT, int PD, bool MOE = false, bool XF = false, bool IL = false, int EPI = 0, bool TR = false>
 __global__ __launch_bounds__(512, PD > 2 ? 1 : 2) void bmm_wt_kernel(BmmArgs a) {
   const BmmArgs* ka = (const BmmArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  wt_body<QT, PD, false, 8, MOE, XF, 0, IL, EPI>(*ka, 0, blockIdx.x, gridDim.x);
+  wt_body<QT, PD, false, 8, MOE, XF, 0, IL, EPI, 0, TR>(*ka, 0, blockIdx.x, gridDim.x);
   (void)a;
 }
 
@@ -1602,45 +1655,47 @@ __global__ __launch_bounds__(512, 2) void bmm_wt_dbg_kernel(BmmArgs a) {
 }
 
 // split-K Q|K|V of one weight type
-template <int QT, int PD, bool XF = false, bool IL = false>
+template <int QT, int PD, bool XF = false, bool IL = false, bool TR = false>
 __global__ __launch_bounds__(512, 2) void bmm_sk_kernel(BmmArgs a) {
   const BmmArgs* ka = (const BmmArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  wt_body<QT, PD, true, 8, false, XF, 0, IL>(*ka, 0, blockIdx.x, gridDim.x);
+  wt_body<QT, PD, true, 8, false, XF, 0, IL, 0, 0, TR>(*ka, 0, blockIdx.x, gridDim.x);
   (void)a;
 }
 
 // split-K Q|K|V over two weight types (Q|K Q4_K + V Q6_K / Q5_K on the bumped layers of the
 // K-quant mixes, Q Q4_K + K|V Q8_0 in Mixtral's): groups from a.nb1 on are run B, type QT2 (a
 // uniform branch per block; each run's body keeps its own registers)
-template <int QT, int QT2, int PD, bool XF = false, bool IL = false>
+template <int QT, int QT2, int PD, bool XF = false, bool IL = false, bool TR = false>
 __global__ __launch_bounds__(512, 2) void bmm_wt2_kernel(BmmArgs a) {
   const BmmArgs* ka = (const BmmArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  if ((int)blockIdx.x / ka->kparts >= ka->nb1) wt_body<QT2, PD, true, 8, false, XF, 0, IL>(*ka, 1, blockIdx.x, gridDim.x);
-  else wt_body<QT, PD, true, 8, false, XF, 0, IL>(*ka, 0, blockIdx.x, gridDim.x);
+  if ((int)blockIdx.x / ka->kparts >= ka->nb1) wt_body<QT2, PD, true, 8, false, XF, 0, IL, 0, 0, TR>(*ka, 1, blockIdx.x, gridDim.x);
+  else wt_body<QT, PD, true, 8, false, XF, 0, IL, 0, 0, TR>(*ka, 0, blockIdx.x, gridDim.x);
   (void)a;
 }
 
 // The SwiGLU gate/up (QT1, producer) and the down projection (QT2, consumer) in ONE launch:
 // blocks [0, a.nb1) run the gate/up, the rest the down (their own BmmArgs: the second kernarg).
-template <int QT1, int QT2, bool IL = false, int PD = 2>
+// (TR: the down role's split-K adds as whole 64-byte segments; IL only)
+template <int QT1, int QT2, bool IL = false, bool TR = false, int PD = 2>
 __global__ __launch_bounds__(512, PD > 2 ? 1 : 2) void bmm_chain_kernel(BmmArgs a, BmmArgs b) {
   const BmmArgs* ka = (const BmmArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   const int n1 = ka[0].nb1;
   if ((int)blockIdx.x < n1) wt_body<QT1, PD, false, 8, false, true, 0, IL, IL ? 1 : 0>(ka[0], 0, blockIdx.x, n1);
-  else wt_body<QT2, PD, false, 8, false, true, 0, IL, IL ? 2 : 0, kChainConsume>(ka[1], 0, blockIdx.x - n1, gridDim.x - n1);
+  else wt_body<QT2, PD, false, 8, false, true, 0, IL, IL ? 2 : 0, kChainConsume, IL && TR>(ka[1], 0, blockIdx.x - n1, gridDim.x - n1);
   (void)a;
   (void)b;
 }
 
 // Wo (QT0, split-K into the residual) -> gate/up (QT1) -> down (QT2) in ONE launch (bmm_wo_ffn_chain)
-template <int QT0, int QT1, int QT2>
+// (TR: the Wo and down roles)
+template <int QT0, int QT1, int QT2, bool TR = false>
 __global__ __launch_bounds__(512, 2) void bmm_chain3_kernel(BmmArgs a, BmmArgs b, BmmArgs c) {
   const BmmArgs* ka = (const BmmArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   const int n0 = ka[0].nb1, n1 = ka[1].nb1;
   const int bid = blockIdx.x;
-  if (bid < n0) wt_body<QT0, 2, false, 8, false, true, 0, true, 2>(ka[0], 0, bid, n0);
+  if (bid < n0) wt_body<QT0, 2, false, 8, false, true, 0, true, 2, 0, TR>(ka[0], 0, bid, n0);
   else if (bid < n0 + n1) wt_body<QT1, 2, false, 8, false, true, 0, true, 1, kChainWaitWo>(ka[1], 0, bid - n0, n1);
-  else wt_body<QT2, 2, false, 8, false, true, 0, true, 2, kChainConsume>(ka[2], 0, bid - n0 - n1, gridDim.x - n0 - n1);
+  else wt_body<QT2, 2, false, 8, false, true, 0, true, 2, kChainConsume, TR>(ka[2], 0, bid - n0 - n1, gridDim.x - n0 - n1);
   (void)a;
   (void)b;
   (void)c;
@@ -1745,6 +1800,14 @@ static int bmm_cus() {
   return cus;
 }
 
+// K-part counts of the split-K shapes, for the sweeps (profiles/README.md): LFK_BMM_WTK_PARTS (Wo /
+// down; unset = the rule below; more than 14 parts only with LFK_FFN_CHAIN=0, the chains' counters
+// hold that many), LFK_BMM_QKV_PARTS (split-K Q|K|V; unset = 4)
+static int bmm_env_parts(const char* name) {
+  const char* e = std::getenv(name);
+  return e ? std::max(0, std::atoi(e)) : 0;
+}
+
 // The wave-owned launch shape (K parts, steps per part, one block per CU): sets a.spp / a.kparts,
 // returns the block count and the dynamic LDS (wt_k: split-K shapes; else the one-part SwiGLU)
 static int wt_config(BmmArgs& a, bool wt_k, size_t& lds) {
@@ -1756,6 +1819,8 @@ static int wt_config(BmmArgs& a, bool wt_k, size_t& lds) {
   if (wt_k) {  // one 8-wave block per CU: parts = CUs x 8 waves / tiles, >= 2 steps per part
     // (8 parts for the 256-tile shapes; 4 / 16 measured 7 / 13 % slower steps, r3 sweep)
     kparts = std::max(1, std::min(steps / 2, (cus * 8 + tiles / 2) / std::max(1, tiles)));
+    static const int env_parts = bmm_env_parts("LFK_BMM_WTK_PARTS");
+    if (env_parts > 0 && !a.ew) kparts = std::max(1, std::min(steps / 2, env_parts));
     if (a.ew) {
       // MoE down (K = the experts' F concatenated): every part inside one expert, the parts of
       // an unrouted expert skipped whole; parts per expert: the count nearest the dense rule
@@ -1783,6 +1848,12 @@ static int wt_config(BmmArgs& a, bool wt_k, size_t& lds) {
 // profiles/README.md round 5)
 template <int QT, int EPI>
 static void launch_wt_il(int nblk, size_t lds, const BmmArgs& a, hipStream_t s) {
+  if constexpr (EPI == 0 || EPI == 2) {
+    if (bmm_tr(a)) {
+      hipLaunchKernelGGL((bmm_wt_kernel<QT, 2, false, true, true, EPI, true>), dim3(nblk), dim3(512), lds, s, a);
+      return;
+    }
+  }
   hipLaunchKernelGGL((bmm_wt_kernel<QT, 2, false, true, true, EPI>), dim3(nblk), dim3(512), lds, s, a);
 }
 
@@ -1812,6 +1883,7 @@ static void launch_bmm(BmmArgs a, hipStream_t s) {
     // (x-first staging everywhere: weights-first measured 2.295 vs 2.246 ms per B = 6 step, r5b)
     if (a.ew && bmm_il()) {  // MoE: the experts' SwiGLU gate/up (EPI 1) and grouped down (split-K, EPI 2)
       if (wt_sw) hipLaunchKernelGGL((bmm_wt_kernel<QT, 2, true, true, true, 1>), dim3(nblk), dim3(512), lds, s, a);
+      else if (a.kparts > 1 && bmm_tr(a)) hipLaunchKernelGGL((bmm_wt_kernel<QT, 2, true, true, true, 2, true>), dim3(nblk), dim3(512), lds, s, a);
       else if (a.kparts > 1) hipLaunchKernelGGL((bmm_wt_kernel<QT, 2, true, true, true, 2>), dim3(nblk), dim3(512), lds, s, a);
       else hipLaunchKernelGGL((bmm_wt_kernel<QT, 2, true, true, true, 0>), dim3(nblk), dim3(512), lds, s, a);
     } else if (a.ew) hipLaunchKernelGGL((bmm_wt_kernel<QT, 2, true, true>), dim3(nblk), dim3(512), lds, s, a);
@@ -1884,7 +1956,8 @@ static void launch_qkv_sk(BmmArgs a, hipStream_t s) {
   }
   const int steps = a.w.K / 256;
   // 4 parts x 8-tile groups measured best at B = 6 (8 x 8: +3 %, 4 x 6 / 2 x 3: +1-4 %, 16 x 6: +15 %)
-  const int kparts = std::max(1, std::min(steps, 4));
+  static const int env_parts = bmm_env_parts("LFK_BMM_QKV_PARTS");
+  const int kparts = std::max(1, std::min(steps, env_parts > 0 ? env_parts : 4));
   a.spp = (steps + kparts - 1) / kparts;
   a.kparts = (steps + a.spp - 1) / a.spp;
   a.tpg = 8;
@@ -1893,10 +1966,12 @@ static void launch_qkv_sk(BmmArgs a, hipStream_t s) {
   const dim3 grid((ga + gb) * a.kparts);
   const size_t lds = 256 + (size_t)a.B * (a.spp * 256 + kWtXPad) * 2;
   if constexpr (QT2 == 0) {
-    if (bmm_il()) hipLaunchKernelGGL((bmm_sk_kernel<QT, 2, true, true>), grid, dim3(512), lds, s, a);  // (un-RoPE'd sums)
+    if (bmm_il() && bmm_tr(a)) hipLaunchKernelGGL((bmm_sk_kernel<QT, 2, true, true, true>), grid, dim3(512), lds, s, a);
+    else if (bmm_il()) hipLaunchKernelGGL((bmm_sk_kernel<QT, 2, true, true>), grid, dim3(512), lds, s, a);  // (un-RoPE'd sums)
     else hipLaunchKernelGGL((bmm_sk_kernel<QT, 2, true>), grid, dim3(512), lds, s, a);
   } else {
-    if (bmm_il()) hipLaunchKernelGGL((bmm_wt2_kernel<QT, QT2, 2, true, true>), grid, dim3(512), lds, s, a);
+    if (bmm_il() && bmm_tr(a)) hipLaunchKernelGGL((bmm_wt2_kernel<QT, QT2, 2, true, true, true>), grid, dim3(512), lds, s, a);
+    else if (bmm_il()) hipLaunchKernelGGL((bmm_wt2_kernel<QT, QT2, 2, true, true>), grid, dim3(512), lds, s, a);
     else hipLaunchKernelGGL((bmm_wt2_kernel<QT, QT2, 2, true>), grid, dim3(512), lds, s, a);
   }
 }
@@ -1998,7 +2073,10 @@ void bmm_ffn_chain(const BmmArgs& gu0, const BmmArgs& dn0, int* cnt, int* err, h
   gu.nb1 = n1;
   const dim3 grid(n1 + n2);
   const size_t lds = std::max(lds1, lds2);
-  if (bmm_il()) {
+  if (bmm_il() && bmm_tr(dn)) {
+    if (dn.w.type == T_Q6_K) hipLaunchKernelGGL((bmm_chain_kernel<T_Q4_K, T_Q6_K, true, true>), grid, dim3(512), lds, s, gu, dn);
+    else hipLaunchKernelGGL((bmm_chain_kernel<T_Q4_K, T_Q4_K, true, true>), grid, dim3(512), lds, s, gu, dn);
+  } else if (bmm_il()) {
     if (dn.w.type == T_Q6_K) hipLaunchKernelGGL((bmm_chain_kernel<T_Q4_K, T_Q6_K, true>), grid, dim3(512), lds, s, gu, dn);
     else hipLaunchKernelGGL((bmm_chain_kernel<T_Q4_K, T_Q4_K, true>), grid, dim3(512), lds, s, gu, dn);
   } else {
@@ -2030,7 +2108,10 @@ void bmm_wo_ffn_chain(const BmmArgs& wo0, const BmmArgs& gu0, const BmmArgs& dn0
   dn.chain_err = err; dn.chain_staged = n1; dn.chain_poll = 8;
   const dim3 grid(n0 + n1 + n2);
   const size_t lds = std::max(lds0, std::max(lds1, lds2));
-  if (dn.w.type == T_Q6_K) hipLaunchKernelGGL((bmm_chain3_kernel<T_Q4_K, T_Q4_K, T_Q6_K>), grid, dim3(512), lds, s, wo, gu, dn);
+  if (bmm_tr(dn)) {  // (one orientation for both split-K roles: dn's)
+    if (dn.w.type == T_Q6_K) hipLaunchKernelGGL((bmm_chain3_kernel<T_Q4_K, T_Q4_K, T_Q6_K, true>), grid, dim3(512), lds, s, wo, gu, dn);
+    else hipLaunchKernelGGL((bmm_chain3_kernel<T_Q4_K, T_Q4_K, T_Q4_K, true>), grid, dim3(512), lds, s, wo, gu, dn);
+  } else if (dn.w.type == T_Q6_K) hipLaunchKernelGGL((bmm_chain3_kernel<T_Q4_K, T_Q4_K, T_Q6_K>), grid, dim3(512), lds, s, wo, gu, dn);
   else hipLaunchKernelGGL((bmm_chain3_kernel<T_Q4_K, T_Q4_K, T_Q4_K>), grid, dim3(512), lds, s, wo, gu, dn);
 }
 

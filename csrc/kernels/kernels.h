@@ -196,6 +196,9 @@ struct BmmArgs {
   const float* ew = nullptr;
   int ew_ld = 0, tiles_per_expert = 0, steps_per_expert = 0;
   bool one_part = false;           // plain projection as one K part (8-wave blocks, no atomics)
+  int tr = -1;                     // wave-owned split-K epilogues: 1 = transposed tiles (activation rows x 16 adjacent
+                                   // outputs: whole 64-byte segments per atomic add), 0 = weight rows x activation
+                                   // columns, -1 = the process default (LFK_BMM_TR, transposed unless 0)
   long long* dbg_clk = nullptr;    // microbenchmarks only: per-block wall_clock64 stamps [grid][8]
   int nb1 = 0;                     // bmm_qkv2: blocks of the first run; split-K Q|K|V: first group of run B
   // Split-K Q|K|V (qkv_sk, batched decode, B <= 8): segments 0..nseg-1 (Q, K, V rows; kinds in
