@@ -234,6 +234,16 @@ PYBIND11_MODULE(_cpu, m) {
              }
              return py::array_t<float>(v.size(), v.data());
            })
+      .def_property_readonly("hparams", [](const CpuEngine& e) {
+        const HParams& h = e.hparams();
+        py::dict d;
+        d["n_vocab"] = h.n_vocab; d["n_embd"] = h.n_embd; d["n_layer"] = h.n_layer; d["n_head"] = h.n_head;
+        d["n_head_kv"] = h.n_head_kv; d["head_dim"] = h.head_dim; d["n_ff"] = h.n_ff;
+        d["n_expert"] = h.n_expert; d["n_expert_used"] = h.n_expert_used;
+        d["rope_base"] = h.rope_base; d["rms_eps"] = h.rms_eps;
+        d["arch"] = h.arch; d["rope_neox"] = h.rope_neox; d["qkv_bias"] = h.qkv_bias;
+        return d;
+      })
       .def_property_readonly("n_vocab", &CpuEngine::n_vocab)
       .def_property_readonly("n_layer", &CpuEngine::n_layer)
       .def_property_readonly("n_ctx", &CpuEngine::n_ctx);

@@ -11,6 +11,8 @@
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
+
+#include <array>
 #include <rccl/rccl.h>
 
 #include "bind_scheduler.h"
@@ -276,6 +278,7 @@ PYBIND11_MODULE(_hip, m) {
         d["n_head_kv"] = h.n_head_kv; d["head_dim"] = h.head_dim; d["n_ff"] = h.n_ff;
         d["n_expert"] = h.n_expert; d["n_expert_used"] = h.n_expert_used;
         d["rope_base"] = h.rope_base; d["rms_eps"] = h.rms_eps;
+        d["arch"] = h.arch; d["rope_neox"] = h.rope_neox; d["qkv_bias"] = h.qkv_bias;
         return d;
       });
 
@@ -454,8 +457,10 @@ PYBIND11_MODULE(_hip, m) {
 
   m.def("gemv_qkv", [](uintptr_t wq, int tq, uintptr_t wk, int tk, uintptr_t wv, int tv, int nq, int nkv, int K,
                        uintptr_t x, uintptr_t norm, float eps, uintptr_t q_out, uintptr_t kc, uintptr_t vc, int n_ctx,
-                       int hd, uintptr_t pos, uintptr_t rope, uintptr_t stream) {
+                       int hd, uintptr_t pos, uintptr_t rope, uintptr_t stream, uintptr_t bq, uintptr_t bk,
+                       uintptr_t bv) {
     QkvArgs a;
+    a.bq = P<float>(bq); a.bk = P<float>(bk); a.bv = P<float>(bv);
     a.wq = make_qmat(P<void>(wq), tq, nq, K);
     a.wk = make_qmat(P<void>(wk), tk, nkv, K);
     a.wv = make_qmat(P<void>(wv), tv, nkv, K);
@@ -464,7 +469,10 @@ PYBIND11_MODULE(_hip, m) {
     a.pos = P<int>(pos); a.rope = P<float2>(rope);
     gemv_qkv(a, S(stream));
     hip_ok("gemv_qkv");
-  });
+  }, py::arg("wq"), py::arg("tq"), py::arg("wk"), py::arg("tk"), py::arg("wv"), py::arg("tv"), py::arg("nq"),
+     py::arg("nkv"), py::arg("K"), py::arg("x"), py::arg("norm"), py::arg("eps"), py::arg("q_out"), py::arg("kc"),
+     py::arg("vc"), py::arg("n_ctx"), py::arg("hd"), py::arg("pos"), py::arg("rope"), py::arg("stream"),
+     py::arg("bq") = 0, py::arg("bk") = 0, py::arg("bv") = 0);
 
   m.def("moe_down", [](uintptr_t w, int type, int rows, int K, size_t expert_stride, uintptr_t h, uintptr_t ids,
                        uintptr_t ew, int n_slots, uintptr_t out, uintptr_t stream) {
@@ -549,8 +557,9 @@ PYBIND11_MODULE(_hip, m) {
                           int hd, float scale, uintptr_t part, uintptr_t out, uintptr_t stream, uintptr_t counters,
                           int debug_stop, uintptr_t dbg_clk, int batch, uintptr_t slots, size_t slot_stride,
                           uintptr_t out_h, uintptr_t qkv_raw, size_t qkv_ld, size_t k_off, size_t v_off, uintptr_t ss,
-                          float inv_k, float eps, uintptr_t rope_freq) {
+                          float inv_k, float eps, uintptr_t rope_freq, uintptr_t qkv_bias) {
     AttnDecodeArgs a;
+    a.qkv_bias = P<float>(qkv_bias);
     a.rope_freq = P<float>(rope_freq);
     a.qkv_raw = P<float>(qkv_raw); a.qkv_ld = qkv_ld; a.k_off = k_off; a.v_off = v_off;
     a.ss = P<float>(ss); a.inv_k = inv_k; a.eps = eps;
@@ -573,7 +582,7 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("debug_stop") = 0, py::arg("dbg_clk") = 0, py::arg("batch") = 0, py::arg("slots") = 0,
      py::arg("slot_stride") = 0, py::arg("out_h") = 0, py::arg("qkv_raw") = 0, py::arg("qkv_ld") = 0,
      py::arg("k_off") = 0, py::arg("v_off") = 0, py::arg("ss") = 0, py::arg("inv_k") = 0.f, py::arg("eps") = 1e-5f,
-     py::arg("rope_freq") = 0);
+     py::arg("rope_freq") = 0, py::arg("qkv_bias") = 0);
   // split-K Q|K|V (BmmArgs::qkv_sk) over tile16 copies: RoPE'd partial sums added into out [B][ldo]
   // (Q at 0, K at nq, V at nq + nkv), the rows' sums of squares into ss_out [B]
   m.def("bmm_qkv_sk", [](uintptr_t wq, int tq, int nq, uintptr_t wk, int tk, uintptr_t wv, int tv, int nkv, int K,
@@ -604,8 +613,16 @@ PYBIND11_MODULE(_hip, m) {
   m.def("bmm_qkv_sk_defers_rope", &bmm_qkv_sk_defers_rope);
   m.def("attn_decode_workspace_floats", &attn_decode_workspace_floats);
   m.def("attn_prefill", [](uintptr_t q, uintptr_t kc, uintptr_t vc, int T, int pos0, int n_ctx, int n_head, int n_kv,
-                           int hd, float scale, uintptr_t out, uintptr_t stream, bool out_bf16, bool out_h) {
+                           int hd, float scale, uintptr_t out, uintptr_t stream, bool out_bf16, bool out_h,
+                           const std::vector<std::array<int, 4>>& pieces, size_t slot_stride) {
     AttnPrefillArgs a;
+    // packed pieces: (row, n, pos, slot) each, against caches slot * slot_stride halves in
+    if (pieces.size() > (size_t)AttnPrefillArgs::kMaxPieces) throw std::runtime_error("attn_prefill: too many pieces");
+    a.n_pieces = (int)pieces.size();
+    a.slot_stride = slot_stride;
+    for (int i = 0; i < a.n_pieces; ++i) {
+      a.pc_row[i] = pieces[i][0]; a.pc_n[i] = pieces[i][1]; a.pc_pos[i] = pieces[i][2]; a.pc_slot[i] = pieces[i][3];
+    }
     a.q = P<float>(q); a.k_cache = P<__half>(kc); a.v_cache = P<__half>(vc); a.T = T; a.pos0 = pos0;
     a.n_ctx = n_ctx; a.n_head = n_head; a.n_kv_head = n_kv; a.head_dim = hd; a.scale = scale;
     if (out_h) a.out_h = P<__half>(out);
@@ -616,7 +633,7 @@ PYBIND11_MODULE(_hip, m) {
     hip_ok("attn_prefill");
   }, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("T"), py::arg("pos0"), py::arg("n_ctx"), py::arg("n_head"),
      py::arg("n_kv"), py::arg("hd"), py::arg("scale"), py::arg("out"), py::arg("stream"), py::arg("out_bf16") = false,
-     py::arg("out_h") = false);
+     py::arg("out_h") = false, py::arg("pieces") = std::vector<std::array<int, 4>>{}, py::arg("slot_stride") = 0);
   m.def("embed", [](uintptr_t w, int type, int V, int d, uintptr_t tokens, int T, uintptr_t x, uintptr_t stream) {
     embed_rows(make_qmat(P<void>(w), type, V, d), P<int>(tokens), T, P<float>(x), S(stream));
     hip_ok("embed");

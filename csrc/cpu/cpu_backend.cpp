@@ -27,7 +27,7 @@ inline uint16_t f2h(float f) { return _cvtss_sh(f, 0); }
 // rows [r0, r0+R) x columns [c0, c0+K) of a (per-expert) ggml matrix -> planar; rows past the
 // source are zero (vocab padding of the last TP shard). R < 0 / K < 0 = everything.
 CpuMat load_mat(const GGUFFile& f, const std::string& name, int n_expert = 0, size_t r0 = 0, long R = -1,
-                size_t c0 = 0, long K = -1) {
+                size_t c0 = 0, long K = -1, size_t neox_hd = 0) {
   const GGUFTensor* t = f.find(name);
   if (!t) throw std::runtime_error("missing tensor " + name);
   if (n_expert > 0) check_expert_type(name, t->type);
@@ -43,7 +43,7 @@ CpuMat load_mat(const GGUFFile& f, const std::string& name, int n_expert = 0, si
   m.data.assign(one * E, 0);
   for (int e = 0; e < E; ++e)
     repack_planar(m.type, f.data(*t) + src_one * e, K_src, r0, avail, c0, m.K, m.data.data() + one * e, m.rows, 0,
-                  0);
+                  0, neox_hd);
   m.P = planes_of(m.type, m.rows, m.K);
   m.expert_stride = n_expert > 0 ? one : 0;
   return m;
@@ -485,22 +485,20 @@ CpuEngine::CpuEngine(const std::string& path, const CpuOptions& o)
       n_batch_(std::max(1, std::min(o.n_batch, 128))) {
   omp_set_num_threads(n_threads_);
   GGUFFile f(path);
-  std::string arch = f.get_str("general.architecture", "llama");
-  auto gi = [&](const char* k, int64_t d) { return (int)f.get_int(arch + "." + k, d); };
-  n_embd_ = gi("embedding_length", 0);
-  n_layer_ = gi("block_count", 0);
-  n_head_ = gi("attention.head_count", 0);
-  n_head_kv_ = gi("attention.head_count_kv", n_head_);
-  head_dim_ = gi("rope.dimension_count", n_embd_ / n_head_);
-  n_ff_ = gi("feed_forward_length", 0);
-  n_expert_ = gi("expert_count", 0);
-  n_expert_used_ = gi("expert_used_count", 0);
-  eps_ = (float)f.get_float(arch + ".attention.layer_norm_rms_epsilon", 1e-5);
-  rope_base_ = (float)f.get_float(arch + ".rope.freq_base", 10000.0);
-  if (n_ctx_ <= 0) n_ctx_ = gi("context_length", 2048);
-  const GGUFTensor* emb = f.find("token_embd.weight");
-  if (!emb) throw std::runtime_error("missing token_embd.weight");
-  n_vocab_ = (int)emb->ne[1];
+  hp_ = read_hparams(f);  // (gguf.h: the GPU engine's reader)
+  if (hp_.n_head <= 0) throw std::runtime_error("cpu backend: attention.head_count missing");
+  n_embd_ = hp_.n_embd;
+  n_layer_ = hp_.n_layer;
+  n_head_ = hp_.n_head;
+  n_head_kv_ = hp_.n_head_kv;
+  head_dim_ = hp_.head_dim;
+  n_ff_ = hp_.n_ff;
+  n_expert_ = hp_.n_expert;
+  n_expert_used_ = hp_.n_expert_used;
+  eps_ = hp_.rms_eps;
+  rope_base_ = hp_.rope_base;
+  if (n_ctx_ <= 0) n_ctx_ = hp_.n_ctx_train;
+  n_vocab_ = hp_.n_vocab;
   if (head_dim_ % 32) throw std::runtime_error("cpu backend: head_dim must be a multiple of 32");
   sp_ = make_shard_plan(n_head_, n_head_kv_, head_dim_, n_ff_, n_vocab_, o.tp_size, o.tp_rank, o.tensor_split);
   layer_end_ = o.layer_end < 0 ? n_layer_ : std::min(o.layer_end, n_layer_);
@@ -516,8 +514,23 @@ CpuEngine::CpuEngine(const std::string& path, const CpuOptions& o)
     CpuLayer& L = layers_[l];
     L.attn_norm = load_f32(f, p + "attn_norm.weight");
     L.ffn_norm = load_f32(f, p + "ffn_norm.weight");
-    L.wq = load_mat(f, p + "attn_q.weight", 0, sp_.q_row0(), sp_.nq);
-    L.wk = load_mat(f, p + "attn_k.weight", 0, sp_.kv_row0(), sp_.nkvd);
+    // NeoX RoPE (qwen2): q / k rows (and bias entries) permuted inside each head, as on the GPU, so
+    // that the adjacent-pair rotation below is the model's
+    const size_t neox = hp_.rope_neox ? (size_t)head_dim_ : 0;
+    L.wq = load_mat(f, p + "attn_q.weight", 0, sp_.q_row0(), sp_.nq, 0, -1, neox);
+    L.wk = load_mat(f, p + "attn_k.weight", 0, sp_.kv_row0(), sp_.nkvd, 0, -1, neox);
+    if (hp_.qkv_bias) {
+      auto slice = [&](const char* nm, size_t r0, size_t R, bool perm) {
+        const std::vector<float> all = load_f32(f, p + nm);
+        if (all.size() < r0 + R) throw std::runtime_error(p + nm + ": too short");
+        std::vector<float> o(R);
+        for (size_t r = 0; r < R; ++r) o[r] = all[r0 + (perm && neox ? neox_src_row(r, neox) : r)];
+        return o;
+      };
+      L.bq = slice("attn_q.bias", sp_.q_row0(), sp_.nq, true);
+      L.bk = slice("attn_k.bias", sp_.kv_row0(), sp_.nkvd, true);
+      L.bv = slice("attn_v.bias", sp_.kv_row0(), sp_.nkvd, false);
+    }
     L.wv = load_mat(f, p + "attn_v.weight", 0, sp_.kv_row0(), sp_.nkvd);
     L.wo = load_mat(f, p + "attn_output.weight", 0, 0, -1, sp_.q_row0(), sp_.nq);
     if (n_expert_ > 0) {
@@ -691,6 +704,15 @@ void CpuEngine::run_layers(float* x, int T, int pos0, int l0, int l1) {
     gemm_rows(L.wq, L.wq.data.data(), xq, T, q.data(), nq, false);
     gemm_rows(L.wk, L.wk.data.data(), xq, T, k.data(), nkv, false);
     gemm_rows(L.wv, L.wv.data.data(), xq, T, v.data(), nkv, false);
+    if (!L.bq.empty()) {  // Q|K|V biases: on the projection, before the rotation
+      for (int t = 0; t < T; ++t) {
+        for (int i = 0; i < nq; ++i) q[(size_t)t * nq + i] += L.bq[i];
+        for (int i = 0; i < nkv; ++i) {
+          k[(size_t)t * nkv + i] += L.bk[i];
+          v[(size_t)t * nkv + i] += L.bv[i];
+        }
+      }
+    }
     for (int t = 0; t < T; ++t) {
       const int pos = pos0 + t;
       auto rope = [&](float* r, int n) {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../common.h"
+#include "../runtime/gguf.h"
 #include "../runtime/shard.h"
 
 namespace lfk {
@@ -28,6 +29,7 @@ struct CpuMat {
 
 struct CpuLayer {
   std::vector<float> attn_norm, ffn_norm;
+  std::vector<float> bq, bk, bv;  // Q|K|V biases of this rank's rows (qwen2; empty: none)
   CpuMat wq, wk, wv, wo, w_gu, w_down, router, gu_exps, down_exps;
 };
 
@@ -76,6 +78,7 @@ class CpuEngine {
   size_t kv_state_bytes(int n) const { return 2 * (kc_.size() / (size_t)n_ctx_) * (size_t)n * sizeof(uint16_t); }
   void kv_transfer(void* buf, int n, bool load);
 
+  const HParams& hparams() const { return hp_; }
   int n_vocab() const { return n_vocab_; }
   int n_embd() const { return n_embd_; }
   int n_layer() const { return n_layer_; }
@@ -92,6 +95,7 @@ class CpuEngine {
   void reduce(float* y, size_t n);
 
   CpuOptions opt_;
+  HParams hp_;
   ShardPlan sp_;
   int layer_end_ = 0;
   std::function<void(float*, size_t)> allreduce_;

@@ -19,28 +19,34 @@
 
 namespace lfk {
 
-template <int HD, int G, bool TL>
+template <int HD, int G, bool TL, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeArgs a) {
-  attn_decode_body<HD, G, TL>(a);
+  attn_decode_body<HD, G, TL, BIAS>(a);
 }
 
 size_t attn_decode_workspace_floats(int n_ctx, int n_head, int head_dim) {
   return (size_t)((n_ctx + CH - 1) / CH) * n_head * (head_dim + 2);
 }
 
-template <int HD, bool TL>
+template <int HD, bool TL, bool BIAS = false>
 static void launch_attn_decode_tl(const AttnDecodeArgs& a, int G, dim3 grid, hipStream_t s) {
   switch (G) {
-    case 1: hipLaunchKernelGGL((attn_decode_kernel<HD, 1, TL>), grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((attn_decode_kernel<HD, 2, TL>), grid, dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((attn_decode_kernel<HD, 4, TL>), grid, dim3(256), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((attn_decode_kernel<HD, 8, TL>), grid, dim3(256), 0, s, a); break;
-    default: throw std::runtime_error("attn_decode: gqa group must be 1, 2, 4 or 8");
+    case 1: hipLaunchKernelGGL((attn_decode_kernel<HD, 1, TL, BIAS>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((attn_decode_kernel<HD, 2, TL, BIAS>), grid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((attn_decode_kernel<HD, 3, TL, BIAS>), grid, dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((attn_decode_kernel<HD, 4, TL, BIAS>), grid, dim3(256), 0, s, a); break;
+    case 5: hipLaunchKernelGGL((attn_decode_kernel<HD, 5, TL, BIAS>), grid, dim3(256), 0, s, a); break;
+    case 6: hipLaunchKernelGGL((attn_decode_kernel<HD, 6, TL, BIAS>), grid, dim3(256), 0, s, a); break;
+    case 7: hipLaunchKernelGGL((attn_decode_kernel<HD, 7, TL, BIAS>), grid, dim3(256), 0, s, a); break;
+    case 8: hipLaunchKernelGGL((attn_decode_kernel<HD, 8, TL, BIAS>), grid, dim3(256), 0, s, a); break;
+    default: throw std::runtime_error("attn_decode: gqa group must be 1 to 8");
   }
 }
 template <int HD>
 static void launch_attn_decode(const AttnDecodeArgs& a, int G, dim3 grid, hipStream_t s) {
-  if (a.dbg_clk) launch_attn_decode_tl<HD, true>(a, G, grid, s);
+  if (a.qkv_bias && a.dbg_clk) launch_attn_decode_tl<HD, true, true>(a, G, grid, s);
+  else if (a.qkv_bias) launch_attn_decode_tl<HD, false, true>(a, G, grid, s);
+  else if (a.dbg_clk) launch_attn_decode_tl<HD, true>(a, G, grid, s);
   else launch_attn_decode_tl<HD, false>(a, G, grid, s);
 }
 
@@ -60,6 +66,8 @@ void attn_decode(const AttnDecodeArgs& a, hipStream_t s) {
   }
   if (a.qkv_raw && (a.batch < 1 || !a.ss || a.qkv_ld % 2 || a.k_off % 2 || a.v_off % 2 || touch))
     throw std::runtime_error("attn_decode: split-K Q|K|V arguments");
+  if (a.qkv_bias && (!a.qkv_raw || !a.rope_freq))
+    throw std::runtime_error("attn_decode: Q|K|V biases need the raw sums with the RoPE deferred");
   if (a.done) throw std::runtime_error("attn_decode: done counters are attn_wo1's (gemv.hip)");
   // z: the rows (batched) or one; the weight-touch plane, if any, is the next z index
   dim3 grid(a.n_kv_head, (a.n_ctx + CH - 1) / CH, (a.batch > 0 ? a.batch : 1) + (touch ? 1 : 0));
@@ -198,7 +206,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(AttnPrefillArgs 
   int T = a.T, pos0 = a.pos0, hz = blockIdx.z;
   size_t row0 = 0, cache0 = 0;
   if (a.n_pieces > 0) {
-    const int HZ = G / HB, pc = blockIdx.z / HZ;
+    const int HZ = (G + HB - 1) / HB, pc = blockIdx.z / HZ;
     hz = blockIdx.z - pc * HZ;
     T = a.pc_n[pc];
     pos0 = a.pc_pos[pc];
@@ -206,7 +214,11 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(AttnPrefillArgs 
     cache0 = (size_t)a.pc_slot[pc] * a.slot_stride;
     if (qblk * QTB * 32 >= T) return;  // a shorter piece's missing tiles: whole block, no barrier yet
   }
-  const int head = kvh * G + hz * HB + wave % HB;
+  // a group that is no multiple of HB (G = 3, 5, 6, 7): the waves past the last head load a real
+  // head's q (clamped), take part in every barrier and store nothing
+  const int hl = hz * HB + wave % HB;
+  const bool hreal = hl < G;
+  const int head = kvh * G + min(hl, G - 1);
   const int tq = (qblk * QTB + wave / HB) * 32;
   const int nkeys = pos0 + min(T, (qblk + 1) * QTB * 32);  // keys the block needs
   const int wkeys = pos0 + min(T, tq + 32);                 // keys this wave needs
@@ -327,7 +339,7 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(AttnPrefillArgs 
   }
   l += __shfl_xor(l, 32);
   const float inv = 1.f / l;
-  if (t < T) {
+  if (t < T && hreal) {
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
@@ -352,13 +364,15 @@ __global__ __launch_bounds__(256) void attn_prefill_mfma_kernel(AttnPrefillArgs 
 
 template <int HD>
 static void launch_attn_prefill_mfma(const AttnPrefillArgs& a, int G, hipStream_t s) {
-  const int HB = std::min(G, 4), QTB = 4 / HB;
+  // heads per block: min(G, 4) for the power-of-two groups; 4 otherwise, the last block of a kv
+  // head padded with waves that store nothing
+  const int HB = (G & (G - 1)) == 0 ? std::min(G, 4) : 4, QTB = 4 / HB;
   int tmax = a.T;
   if (a.n_pieces > 0) {
     tmax = 0;
     for (int i = 0; i < a.n_pieces; ++i) tmax = std::max(tmax, a.pc_n[i]);
   }
-  dim3 grid(a.n_kv_head, (tmax + 32 * QTB - 1) / (32 * QTB), (G / HB) * std::max(1, a.n_pieces));
+  dim3 grid(a.n_kv_head, (tmax + 32 * QTB - 1) / (32 * QTB), ((G + HB - 1) / HB) * std::max(1, a.n_pieces));
   if (a.out_h) hipLaunchKernelGGL((attn_prefill_mfma_kernel<HD, 2>), grid, dim3(256), 0, s, a, HB);
   else if (a.out_bf16) hipLaunchKernelGGL((attn_prefill_mfma_kernel<HD, 1>), grid, dim3(256), 0, s, a, HB);
   else hipLaunchKernelGGL((attn_prefill_mfma_kernel<HD, 0>), grid, dim3(256), 0, s, a, HB);
@@ -377,8 +391,11 @@ void attn_prefill(const AttnPrefillArgs& a, hipStream_t s) {
   if (a.head_dim != 128 && a.head_dim != 64) throw std::runtime_error("attn_prefill: head_dim must be 64 or 128");
   if (a.n_pieces == 0 && a.pos0 + a.T > a.n_ctx) throw std::runtime_error("attn_prefill: pos0 + T > n_ctx");
   const int G = a.n_head / a.n_kv_head;
-  if (a.n_pieces > 0 && !((G & (G - 1)) == 0 && G <= 16)) throw std::runtime_error("attn_prefill: pieces need the MFMA path");
-  if ((G & (G - 1)) == 0 && G <= 16) {  // GQA group a power of two (every Llama/Mixtral)
+  if (a.n_pieces > 0 && G > 16) throw std::runtime_error("attn_prefill: pieces need the MFMA path");
+  // MFMA: every power-of-two group; the other groups (qwen2: 5, 6, 7) in the forms the engine uses -
+  // bf16 / f16 output, packed pieces. Their plain f32 form keeps the scalar kernel below.
+  const bool pow2 = (G & (G - 1)) == 0;
+  if (G <= 16 && (pow2 || a.out_bf16 || a.out_h || a.n_pieces > 0)) {
     if (a.head_dim == 128) launch_attn_prefill_mfma<128>(a, G, s);
     else launch_attn_prefill_mfma<64>(a, G, s);
     return;

@@ -87,7 +87,9 @@ __device__ __forceinline__ float rows_sum(float v) {
 //   4. single split: normalise and store. Otherwise the partial goes out with
 //      sc1 stores and the last-arriving block of the kv head merges all splits
 //      (sc1 loads; no cache-maintenance fences).
-template <int HD, int G, bool TL>
+// BIAS: the split-K raw sums carry Q|K|V biases (AttnDecodeArgs::qkv_bias, qwen2) - a kernel of its
+// own, so that the code of the unbiased models is exactly what it was without them.
+template <int HD, int G, bool TL, bool BIAS = false>
 __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
   constexpr int DPL = HD / 4;   // dims per lane in QK
   constexpr int NLD = DPL / 8;  // 16-B loads per lane per K (or V) row
@@ -107,7 +109,7 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
                "s"(a.part), "s"(a.counters), "s"(a.out), "s"(a.debug_stop), "s"(a.batch), "s"(a.slots),
                "s"(a.slot_stride), "s"(a.q_stride), "s"(a.out_stride), "s"(a.part_stride), "s"(a.out_h),
                "s"(a.out_h_stride), "s"(a.done), "s"(a.qkv_raw), "s"(a.qkv_ld), "s"(a.k_off), "s"(a.v_off), "s"(a.ss),
-               "s"(a.inv_k), "s"(a.eps), "s"(a.rope_freq));
+               "s"(a.inv_k), "s"(a.eps), "s"(a.rope_freq), "s"(a.qkv_bias));
   if ((int)blockIdx.z == (a.batch > 0 ? a.batch : 1)) {  // weight-touch plane (see AttnDecodeArgs::pf)
     const int nb = gridDim.x * gridDim.y, b = blockIdx.y * gridDim.x + blockIdx.x;
     uint32_t acc = 0;
@@ -171,11 +173,22 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
   // deferred, the pairs' frequencies - all issued unconditionally (from q when unused) and before
   // K / V, so that waiting for them never waits for the K / V rows
   const bool raw = a.qkv_raw != nullptr, drope = raw && a.rope_freq != nullptr;
+  // Q|K|V biases of the raw sums (the launcher guarantees raw sums and the deferred RoPE): loaded
+  // here, beside q and the new key / value and before the K / V rows
+  float2 bq[BIAS ? QPT : 1];
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int j = 0; j < QPT; ++j)
+      bq[j] = reinterpret_cast<const float2*>(a.qkv_bias + (size_t)kvh * G * HD)[min(tid + 256 * j, G * HD / 2 - 1)];
+  }
   const float ssv = __hip_atomic_load(const_cast<float*>(raw ? a.ss + (a.batch > 0 ? blockIdx.z : 0) : a.q),
                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int kvsel = tid / (HD / 2), pr = tid % (HD / 2);
   const float2 nv = reinterpret_cast<const float2*>(
       raw && tid < HD ? a.qkv_raw + (kvsel ? a.v_off : a.k_off) + (size_t)kvh * HD : a.q)[raw && tid < HD ? pr : 0];
+  float2 bn = make_float2(0.f, 0.f);
+  if constexpr (BIAS)
+    bn = reinterpret_cast<const float2*>(a.qkv_bias + (tid < HD && kvsel ? a.v_off : a.k_off) + (size_t)kvh * HD)[tid < HD ? pr : 0];
   float fq[QPT];
 #pragma unroll
   for (int j = 0; j < QPT; ++j) fq[j] = (drope ? a.rope_freq : a.q)[drope ? min(tid + 256 * j, G * HD / 2 - 1) % (HD / 2) : 0];
@@ -195,15 +208,32 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
     sincosf(pf * f, &sn, &cs);
     return make_float2(v.x * cs - v.y * sn, v.x * sn + v.y * cs);
   };
+  if constexpr (BIAS) {
+    // with biases the row scale applies to the sum BEFORE the bias and the rotation,
+    // so it cannot be folded into the softmax scale as below: rot(q rs + bq) scale, rot(k rs + bk),
+    // v rs + bv
 #pragma unroll
-  for (int j = 0; j < QPT; ++j) {
-    const int i = tid + 256 * j;
-    const float2 q2 = rot(qv[j], fq[j]);
-    if (i < G * HD / 2) qs[i / (HD / 2)][i % (HD / 2)] = h2v{(_Float16)(q2.x * qscale), (_Float16)(q2.y * qscale)};
-  }
-  if (raw && tid < HD) {
-    const float2 n2 = tid < HD / 2 ? rot(nv, fq[0]) : nv;  // (fq[0]: pair tid % (HD / 2) = tid here)
-    kvn[tid / (HD / 2)][tid % (HD / 2)] = h2v{(_Float16)(n2.x * rs), (_Float16)(n2.y * rs)};
+    for (int j = 0; j < QPT; ++j) {
+      const int i = tid + 256 * j;
+      const float2 q2 = rot(make_float2(qv[j].x * rs + bq[j].x, qv[j].y * rs + bq[j].y), fq[j]);
+      if (i < G * HD / 2) qs[i / (HD / 2)][i % (HD / 2)] = h2v{(_Float16)(q2.x * a.scale), (_Float16)(q2.y * a.scale)};
+    }
+    if (tid < HD) {
+      const float2 nb = make_float2(nv.x * rs + bn.x, nv.y * rs + bn.y);
+      const float2 n2 = tid < HD / 2 ? rot(nb, fq[0]) : nb;
+      kvn[tid / (HD / 2)][tid % (HD / 2)] = h2v{(_Float16)n2.x, (_Float16)n2.y};
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < QPT; ++j) {
+      const int i = tid + 256 * j;
+      const float2 q2 = rot(qv[j], fq[j]);
+      if (i < G * HD / 2) qs[i / (HD / 2)][i % (HD / 2)] = h2v{(_Float16)(q2.x * qscale), (_Float16)(q2.y * qscale)};
+    }
+    if (raw && tid < HD) {
+      const float2 n2 = tid < HD / 2 ? rot(nv, fq[0]) : nv;  // (fq[0]: pair tid % (HD / 2) = tid here)
+      kvn[tid / (HD / 2)][tid % (HD / 2)] = h2v{(_Float16)(n2.x * rs), (_Float16)(n2.y * rs)};
+    }
   }
   const int L = min(*a.pos + 1, a.n_ctx);
   LFK_STAMP(0);
@@ -391,8 +421,11 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
   // once per thread, not once per element: 64 instead of 96 VGPRs of loads at G = 4,
   // which keeps the kernel at 4 waves per SIMD (a B = 6 grid of 768 blocks then fits
   // the chip in one dispatch round instead of leaving a third of it for a second one).
-  constexpr int EPT = (G * HD + 255) / 256;
-  static_assert(HD % EPT == 0, "a thread's elements must share one head");
+  // (rounded up to a power of two: a thread's elements share one head and whole 4-groups at the
+  // group sizes 5 and 6, where G HD / 256 is 2.5 and 3)
+  constexpr int EPTR = (G * HD + 255) / 256;
+  constexpr int EPT = EPTR <= 1 ? 1 : EPTR <= 2 ? 2 : EPTR <= 4 ? 4 : 8;
+  static_assert(HD % EPT == 0 && (G * HD) % EPT == 0, "a thread's elements must share one head");
   constexpr int NSB = 16;
   const int e0 = min(tid * EPT, G * HD - EPT);
   const int h = kvh * G + e0 / HD, d0 = e0 % HD;

@@ -629,12 +629,20 @@ __device__ __forceinline__ void bmm_stage_x(const BmmArgs& a, __half* xs, float*
 // Q|K|V epilogue of one reduced 16-row tile (lane: rows 4kq .. 4kq+3, column r16): RoPE on the
 // adjacent pairs (0,1), (2,3) this lane holds for Q and K, Q rows to q_out, K / V rows as f16
 // into the row's KV slot at its position (the batched rope_kv_prefill folded in)
-__device__ __forceinline__ void qkv_epilogue(const BmmArgs& a, int sg, int tile, int n_out, const f4_t& acc, int r16,
+// BIAS: the segments carry Q|K|V biases (qwen2), added before the rotation - its own instantiation
+template <bool BIAS>
+__device__ __forceinline__ void qkv_epilogue(const BmmArgs& a, int sg, int tile, int n_out, const f4_t& acc0, int r16,
                                              int kq) {
   const auto& q = a.qkv;
   const int kind = sg == 0 ? q.kind[0] : sg == 1 ? q.kind[1] : q.kind[2], b = r16, hd = q.head_dim;
   const int pos = min(max(q.pos[b], 0), q.n_ctx - 1);
   const size_t so = (size_t)q.slots[b] * q.slot_stride;
+  f4_t acc = acc0;
+  if constexpr (BIAS) {  // rows 4 kq .. 4 kq + 3 of the tile (the last tile's reads clamped to the segment's rows)
+    const float* bias = sg == 0 ? q.bias[0] : sg == 1 ? q.bias[1] : q.bias[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] += bias[min(tile * 16 + 4 * kq + i, n_out - 1)];
+  }
 #pragma unroll
   for (int i = 0; i < 4; i += 2) {
     const int row = tile * 16 + 4 * kq + i;
@@ -856,7 +864,8 @@ __device__ __attribute__((always_inline)) inline void bmm_body(const BmmArgs* __
           *reinterpret_cast<uint2*>(a.h_out + (size_t)r16 * a.ldh_out + f0) = make_uint2(as_u(p0), as_u(p1));
         }
       } else if (col_ok && a.qkv_epi) {
-        qkv_epilogue(a, sg, tile, n_out, acc, r16, kq);
+        if (a.qkv.bias[0]) qkv_epilogue<true>(a, sg, tile, n_out, acc, r16, kq);  // (launch-uniform)
+        else qkv_epilogue<false>(a, sg, tile, n_out, acc, r16, kq);
       } else if (col_ok) {
         float* o = out + (size_t)r16 * a.ldo;
 #pragma unroll

@@ -622,6 +622,7 @@ struct QkvSeg {
   Planes P;
   int rows;
   int kind;  // 0 = Q, 1 = K, 2 = V
+  const float* bias;  // optional f32 bias of the segment's rows (null: none)
 };
 struct QkvLaunch {
   QkvSeg seg[3];
@@ -652,7 +653,10 @@ __device__ __forceinline__ void qkv_item(const QkvLaunch& a, int s_lo, int s_hi,
   for (int r = 0; r < NR; ++r) R[r] = row_ptr(sg.base, sg.P, (unsigned)(r0 + r));
 }
 
-template <int QT, int NR, int U, int BLOCK>
+// BIAS: the segments carry Q|K|V biases (qwen2). A separate instantiation, chosen once per block
+// (inlined into the same kernel), so that the arithmetic of the unbiased models is compiled from
+// the source it was compiled from without them.
+template <int QT, int NR, int U, int BLOCK, bool BIAS>
 __device__ __forceinline__ void qkv_run(const QkvLaunch& a, int s_lo, int s_hi, int blk, int nblk, int pos,
                                         XPrologue<true, BLOCK>& xp, int8_t* xq, float* xd, float* red) {
   const int wave = wave_id(), lane = threadIdx.x & 63;
@@ -678,11 +682,15 @@ __device__ __forceinline__ void qkv_run(const QkvLaunch& a, int s_lo, int s_hi, 
   int si = s_lo, r0 = 0;
   WStream<QT, NR, U> ws;
   float2 cs = make_float2(1.f, 0.f);
+  float bs = 0.f;  // the row's bias (lanes < NR), loaded with the item's weights like (cos, sin)
   auto rope_of = [&](int r) { return a.rope[(size_t)pos * (hd >> 1) + ((r % hd) >> 1)]; };
   {  // unconditional (clamped item): no control-flow join between these loads and finish()'s x wait
     qkv_item<QT, NR>(a, s_lo, s_hi, min(item, total - 1), R, si, r0);
     ws.load(R, 0, nchunks, lane);
     if (lane < NR && a.seg[si].kind < 2) cs = rope_of(r0 + lane);
+    if constexpr (BIAS) {
+      if (lane < NR) bs = a.seg[si].bias[r0 + lane];
+    }
   }
   const float xs = xp.finish(a.x, a.norm_w, a.eps, a.K, xq, xd, red);
   while (item < item_end) {
@@ -692,15 +700,20 @@ __device__ __forceinline__ void qkv_run(const QkvLaunch& a, int s_lo, int s_hi, 
     ws.finish_rows(R, nchunks, xq, xd, acc, lane);
     const int csi = si, cr0 = r0;
     const float2 ccs = cs;
+    const float cbs = bs;
     const int next = item + stride;
     if (next < item_end) {
       qkv_item<QT, NR>(a, s_lo, s_hi, next, R, si, r0);
       ws.load(R, 0, nchunks, lane);
       if (lane < NR && a.seg[si].kind < 2) cs = rope_of(r0 + lane);
+      if constexpr (BIAS) {
+        if (lane < NR) bs = a.seg[si].bias[r0 + lane];
+      }
     }
 #pragma unroll
     for (int r = 0; r < NR; ++r) acc[r] *= xs;
     float v = reduce_rows<NR>(acc, lane);
+    if constexpr (BIAS) v += cbs;  // the row's bias, before the rotation
     const float partner = __shfl_xor(v, 1);
     const int kind = a.seg[csi].kind;
     if (lane < NR) {
@@ -731,11 +744,20 @@ __global__ __launch_bounds__(BLOCK) void gemv_qkv_kernel(QkvLaunch a) {
   const int pos = *a.pos;
   XPrologue<true, BLOCK> xp;   // QKV always follows the attention RMSNorm
   xp.load(a.x, a.norm_w, a.K);
+  if (a.seg[0].bias) {  // (launch-uniform: every segment has a bias or none does, gemv_qkv checks)
+    if (!TWO || (int)blockIdx.x < a.blocks0) {
+      qkv_run<QT0, NR0, U0, BLOCK, true>(a, 0, a.g1, blockIdx.x, TWO ? a.blocks0 : gridDim.x, pos, xp, xq, xd, red);
+    } else if constexpr (TWO) {
+      qkv_run<QT1, NR1, U1, BLOCK, true>(a, a.g1, a.nseg, blockIdx.x - a.blocks0, gridDim.x - a.blocks0, pos, xp, xq,
+                                         xd, red);
+    }
+    return;
+  }
   if (!TWO || (int)blockIdx.x < a.blocks0) {
-    qkv_run<QT0, NR0, U0, BLOCK>(a, 0, a.g1, blockIdx.x, TWO ? a.blocks0 : gridDim.x, pos, xp, xq, xd, red);
+    qkv_run<QT0, NR0, U0, BLOCK, false>(a, 0, a.g1, blockIdx.x, TWO ? a.blocks0 : gridDim.x, pos, xp, xq, xd, red);
   } else if constexpr (TWO) {
-    qkv_run<QT1, NR1, U1, BLOCK>(a, a.g1, a.nseg, blockIdx.x - a.blocks0, gridDim.x - a.blocks0, pos, xp, xq, xd,
-                                 red);
+    qkv_run<QT1, NR1, U1, BLOCK, false>(a, a.g1, a.nseg, blockIdx.x - a.blocks0, gridDim.x - a.blocks0, pos, xp, xq,
+                                        xd, red);
   }
 }
 
@@ -803,6 +825,8 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
   const int K = a.wq.K;
   if (K % 32 || a.wk.K != K || a.wv.K != K) throw std::runtime_error("gemv_qkv: K mismatch");
   if (!a.norm_w) throw std::runtime_error("gemv_qkv: the attention RMSNorm weight is required");
+  if ((a.bq != nullptr) != (a.bk != nullptr) || (a.bq != nullptr) != (a.bv != nullptr))
+    throw std::runtime_error("gemv_qkv: biases on all of Q, K and V, or on none");
   if (a.wq.rows % 4 || a.wk.rows % 4 || a.wv.rows % 4) throw std::runtime_error("gemv_qkv: rows must be multiples of 4");
   const QMat* m[3] = {&a.wq, &a.wk, &a.wv};
   QkvLaunch L{};
@@ -813,7 +837,8 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
   for (int i = 0; i < 3; ++i) {
     if (i == 0 || m[i]->type != m[i - 1]->type) { run_start[nrun] = i; run_type[nrun] = m[i]->type; ++nrun; }
   }
-  for (int i = 0; i < 3; ++i) L.seg[i] = QkvSeg{m[i]->base, m[i]->P, m[i]->rows, i};
+  const float* bias[3] = {a.bq, a.bk, a.bv};
+  for (int i = 0; i < 3; ++i) L.seg[i] = QkvSeg{m[i]->base, m[i]->P, m[i]->rows, i, bias[i]};
   L.nseg = 3;
   auto rows_of = [&](int lo, int hi) { int r = 0; for (int i = lo; i < hi; ++i) r += m[i]->rows; return r; };
   if (nrun == 1) {

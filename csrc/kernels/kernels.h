@@ -166,6 +166,9 @@ struct BmmArgs {
     const int* pos = nullptr;      // [B] position of each row
     const int* slots = nullptr;    // [B] KV slot of each row
     const float2* rope = nullptr;  // [n_ctx][head_dim / 2]
+    // optional f32 bias of each SEGMENT's rows (indexed like seg_base; null: none), added to
+    // the finished sum before the RoPE (qwen2)
+    const float* bias[3] = {nullptr, nullptr, nullptr};
   } qkv;
   bool qkv_epi = false;
   // SwiGLU epilogue (gate/up, one K part, see bmm_qkv_fits): the tile16 copy is the SwiGLU
@@ -285,6 +288,11 @@ struct QkvArgs {
   int head_dim = 0;
   const int* pos = nullptr;        // device scalar: position of this token
   const float2* rope = nullptr;    // [n_ctx][head_dim/2] (cos, sin)
+  // optional f32 biases of the Q / K / V rows (null: none), added to the normalised
+  // projection before the RoPE (qwen2)
+  const float* bq = nullptr;
+  const float* bk = nullptr;
+  const float* bv = nullptr;
 };
 void gemv_qkv(const QkvArgs& a, hipStream_t s);
 
@@ -383,6 +391,10 @@ struct AttnDecodeArgs {
   // split-K Q|K|V with its RoPE deferred (bmm_qkv_sk_defers_rope): q and the new key are rotated
   // here by pos * rope_freq[pair] (fp32; null: the sums arrive RoPE'd)
   const float* rope_freq = nullptr;
+  // split-K Q|K|V of a model with Q|K|V biases (qwen2): one f32 vector laid out as a qkv_raw row
+  // (q at 0, k at k_off, v at v_off). Needs rope_freq (the deferred RoPE): the kernel computes
+  // rot(q rs + bq) scale, rot(k rs + bk) and v rs + bv. Null: none
+  const float* qkv_bias = nullptr;
   static constexpr int kTouchRanges = 6;
   const uint8_t* pf[kTouchRanges] = {};
   size_t pf_bytes[kTouchRanges] = {};
@@ -496,7 +508,8 @@ void to_bf16(const float* x, int n, __hip_bfloat16* y, hipStream_t s);
 // slot_arr[t], whose caches start slot_arr[t] * slot_stride halves after k_cache / v_cache.
 void rope_kv_prefill(const float* qkv, int T, int pos0, int n_q, int n_kv, int head_dim, int n_ctx,
                      const float2* rope, float* q_out, __half* k_cache, __half* v_cache, hipStream_t s,
-                     const int* pos_arr = nullptr, const int* slot_arr = nullptr, size_t slot_stride = 0);
+                     const int* pos_arr = nullptr, const int* slot_arr = nullptr, size_t slot_stride = 0,
+                     const float* bias = nullptr);  // bias: optional [n_q + 2 n_kv] f32 added before the RoPE
 // batched decode: tok[b] / pos[b] = the current token / position of KV slot slots[b]
 // (+ zero zero[i * zero_stride], i < zero_n: the step's in-launch chain counters)
 void batch_gather(const int* slots, int B, const int* state, int* tok, int* pos, hipStream_t s, int* zero = nullptr,

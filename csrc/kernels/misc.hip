@@ -94,10 +94,13 @@ void to_bf16(const float* x, int n, __hip_bfloat16* y, hipStream_t s) {
   hipLaunchKernelGGL(to_bf16_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, n, y);
 }
 
+// BIAS: Q|K|V biases [n_q + 2 n_kv] added before the rotation (qwen2; its own instantiation)
+template <bool BIAS>
 __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const float* qkv, int pos0, int n_q, int n_kv, int hd,
                                                               int n_ctx, const float2* rope, float* q_out,
                                                               __half* kc, __half* vc, const int* pos_arr,
-                                                              const int* slot_arr, size_t slot_stride) {
+                                                              const int* slot_arr, size_t slot_stride,
+                                                              const float* bias) {
   const int t = blockIdx.x;
   const int pos = pos_arr ? min(max(pos_arr[t], 0), n_ctx - 1) : pos0 + t;
   if (slot_arr) {
@@ -109,6 +112,10 @@ __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const float* qkv, 
   for (int p = threadIdx.x; p < ncol / 2; p += blockDim.x) {
     int c = 2 * p;
     float a0 = row[c], a1 = row[c + 1];
+    if constexpr (BIAS) {
+      a0 += bias[c];
+      a1 += bias[c + 1];
+    }
     if (c < n_q + n_kv) {
       const int dd = (c < n_q ? c : c - n_q) % hd;
       const float2 cs = rope[(size_t)pos * (hd >> 1) + (dd >> 1)];
@@ -132,11 +139,15 @@ __global__ __launch_bounds__(256) void rope_kv_prefill_kernel(const float* qkv, 
 
 void rope_kv_prefill(const float* qkv, int T, int pos0, int n_q, int n_kv, int head_dim, int n_ctx, const float2* rope,
                      float* q_out, __half* k_cache, __half* v_cache, hipStream_t s, const int* pos_arr,
-                     const int* slot_arr, size_t slot_stride) {
+                     const int* slot_arr, size_t slot_stride, const float* bias) {
   if (T <= 0) return;
   if ((pos_arr == nullptr) != (slot_arr == nullptr)) throw std::runtime_error("rope_kv_prefill: pos/slot arrays");
-  hipLaunchKernelGGL(rope_kv_prefill_kernel, dim3(T), dim3(256), 0, s, qkv, pos0, n_q, n_kv, head_dim, n_ctx, rope,
-                     q_out, k_cache, v_cache, pos_arr, slot_arr, slot_stride);
+  if (bias)
+    hipLaunchKernelGGL(rope_kv_prefill_kernel<true>, dim3(T), dim3(256), 0, s, qkv, pos0, n_q, n_kv, head_dim, n_ctx,
+                       rope, q_out, k_cache, v_cache, pos_arr, slot_arr, slot_stride, bias);
+  else
+    hipLaunchKernelGGL(rope_kv_prefill_kernel<false>, dim3(T), dim3(256), 0, s, qkv, pos0, n_q, n_kv, head_dim, n_ctx,
+                       rope, q_out, k_cache, v_cache, pos_arr, slot_arr, slot_stride, bias);
 }
 
 __global__ void batch_gather_kernel(const int* slots, int B, const int* state, int* tok, int* pos, int* zero,

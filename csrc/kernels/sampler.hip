@@ -500,7 +500,10 @@ void sample_stage2(const SamplerArgs& a, hipStream_t s) {
   if (a.dbg_clk && ncand <= 256 * 32) hipLaunchKernelGGL((sample_stage2_kernel<32, true>), dim3(1), dim3(256), 0, s, a, nb_l);
   else if (ncand <= 256 * 8) hipLaunchKernelGGL((sample_stage2_kernel<8, false>), dim3(rows), dim3(256), 0, s, a, nb_l);
   else if (ncand <= 256 * 32) hipLaunchKernelGGL((sample_stage2_kernel<32, false>), dim3(rows), dim3(256), 0, s, a, nb_l);
-  else throw std::runtime_error("GPU sampler: vocabulary too large (max 8192 candidate slots)");
+  // vocabularies past 131072 (Qwen2.5: 152064 = 149 slices): 64 candidates per thread. (Bound (b)
+  // then uses the first 128 slices' maxima only - still a lower bound of the K-th largest value.)
+  else if (ncand <= 256 * 64) hipLaunchKernelGGL((sample_stage2_kernel<64, false>), dim3(rows), dim3(256), 0, s, a, nb_l);
+  else throw std::runtime_error("GPU sampler: vocabulary too large (max 16384 candidate slots)");
 }
 
 void sample(const SamplerArgs& a, hipStream_t s) {

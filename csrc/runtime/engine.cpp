@@ -26,29 +26,6 @@ static double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-HParams read_hparams(const GGUFFile& f) {
-  HParams h;
-  std::string arch = f.get_str("general.architecture", "llama");
-  if (arch != "llama" && arch != "mistral" && arch != "mixtral")
-    throw std::runtime_error("unsupported architecture " + arch);
-  auto gi = [&](const char* k, int64_t d) { return (int)f.get_int(arch + "." + k, d); };
-  h.n_embd = gi("embedding_length", 0);
-  h.n_layer = gi("block_count", 0);
-  h.n_head = gi("attention.head_count", 0);
-  h.n_head_kv = gi("attention.head_count_kv", h.n_head);
-  h.head_dim = gi("rope.dimension_count", h.n_head ? h.n_embd / h.n_head : 0);
-  h.n_ff = gi("feed_forward_length", 0);
-  h.n_expert = gi("expert_count", 0);
-  h.n_expert_used = gi("expert_used_count", 0);
-  h.n_ctx_train = gi("context_length", 2048);
-  h.rope_base = (float)f.get_float(arch + ".rope.freq_base", 10000.0);
-  h.rms_eps = (float)f.get_float(arch + ".attention.layer_norm_rms_epsilon", 1e-5);
-  const GGUFTensor* emb = f.find("token_embd.weight");
-  if (!emb) throw std::runtime_error("missing token_embd.weight");
-  h.n_vocab = (int)emb->ne[1];
-  return h;
-}
-
 void Engine::check(hipError_t e, const char* what) {
   if (e != hipSuccess) {
     healthy_ = false;
@@ -216,7 +193,7 @@ Engine::~Engine() {
 
 // ------------------------------------------------------------------------ loading
 QMat Engine::upload_matrix(const GGUFFile& f, const std::string& name, size_t r0, size_t R, size_t c0, size_t K,
-                           int n_expert) {
+                           int n_expert, size_t neox_hd) {
   const GGUFTensor* t = f.find(name);
   if (!t) throw std::runtime_error("missing tensor " + name);
   if (n_expert > 0) check_expert_type(name, t->type);
@@ -231,7 +208,7 @@ QMat Engine::upload_matrix(const GGUFFile& f, const std::string& name, size_t r0
   for (int e = 0; e < E; ++e) {
     const size_t rows_avail = r0 < R_src ? std::min(R, R_src - r0) : 0;
     if (rows_avail < R) std::memset(host + one * e, 0, one);
-    repack_planar(t->type, f.data(*t) + src_expert * e, K_src, r0, rows_avail, c0, K, host + one * e, R, 0, 0);
+    repack_planar(t->type, f.data(*t) + src_expert * e, K_src, r0, rows_avail, c0, K, host + one * e, R, 0, 0, neox_hd);
   }
   void* d = dalloc(one * E);
   stage_commit(d, one * E);
@@ -273,6 +250,27 @@ float* Engine::upload_f32(const GGUFFile& f, const std::string& name) {
   return d;
 }
 
+// the layer's Q|K|V biases as one vector [nq | nkvd | nkvd] of this rank's rows, the q and k
+// entries in the same (NeoX -> adjacent pair) order as the rows of their projections
+float* Engine::upload_qkv_bias(const GGUFFile& f, const std::string& p) {
+  const size_t n = (size_t)nq_ + 2 * (size_t)nkvd_, hd = (size_t)hp_.head_dim;
+  float* d = static_cast<float*>(dalloc(n * sizeof(float)));
+  float* h = reinterpret_cast<float*>(stage_acquire(n * sizeof(float)));
+  const char* names[3] = {"attn_q.bias", "attn_k.bias", "attn_v.bias"};
+  const size_t r0[3] = {q0_, kv0_, kv0_}, R[3] = {(size_t)nq_, (size_t)nkvd_, (size_t)nkvd_};
+  size_t o = 0;
+  for (int i = 0; i < 3; ++i) {
+    const GGUFTensor* t = f.find(p + names[i]);
+    if (!t) throw std::runtime_error("missing tensor " + p + names[i]);
+    if (t->type != T_F32 || (size_t)t->n_elements() < r0[i] + R[i]) throw std::runtime_error(p + names[i] + ": expected F32 of the projection's rows");
+    const float* src = reinterpret_cast<const float*>(f.data(*t)) + r0[i];
+    for (size_t r = 0; r < R[i]; ++r) h[o + r] = src[i < 2 && hp_.rope_neox ? neox_src_row(r, hd) : r];
+    o += R[i];
+  }
+  stage_commit(d, n * sizeof(float));
+  return d;
+}
+
 void Engine::load(const GGUFFile& f) {
   const int r = opt_.tp_rank;
   const int d = hp_.n_embd, hd = hp_.head_dim;
@@ -290,8 +288,12 @@ void Engine::load(const GGUFFile& f) {
     Layer& L = layers_[l];
     L.attn_norm = upload_f32(f, p + "attn_norm.weight");
     L.ffn_norm = upload_f32(f, p + "ffn_norm.weight");
-    L.wq = upload_matrix(f, p + "attn_q.weight", q0_, nq_, 0, d);
-    L.wk = upload_matrix(f, p + "attn_k.weight", kv0_, nkvd_, 0, d);
+    // NeoX RoPE (qwen2): the q / k rows of each head permuted so that the kernels' adjacent pairs
+    // are the model's (i, i + hd / 2) pairs - before the planar repack, which the tile16 copies follow
+    const size_t neox = hp_.rope_neox ? (size_t)hd : 0;
+    L.wq = upload_matrix(f, p + "attn_q.weight", q0_, nq_, 0, d, 0, neox);
+    L.wk = upload_matrix(f, p + "attn_k.weight", kv0_, nkvd_, 0, d, 0, neox);
+    if (hp_.qkv_bias) L.bqkv = upload_qkv_bias(f, p);
     L.wv = upload_matrix(f, p + "attn_v.weight", kv0_, nkvd_, 0, d);
     L.wo = upload_matrix(f, p + "attn_output.weight", 0, d, q0_, nq_);
     if (hp_.n_expert > 0) {
@@ -303,7 +305,6 @@ void Engine::load(const GGUFFile& f) {
       L.w_gu = upload_gate_up(f, p + "ffn_gate.weight", p + "ffn_up.weight", f0_, F_l_);
       L.w_down = upload_matrix(f, p + "ffn_down.weight", 0, d, f0_, F_l_);
     }
-    (void)hd;
   }
 }
 
@@ -737,6 +738,7 @@ void Engine::enqueue_layer_decode(int l, hipStream_t s) {
   qa.n_ctx = opt_.n_ctx; qa.head_dim = hd;
   qa.pos = st + S_POS;
   qa.rope = rope_;
+  if (L.bqkv) { qa.bq = L.bqkv; qa.bk = L.bqkv + nq_; qa.bv = L.bqkv + nq_ + nkvd_; }
   gemv_qkv(qa, s);
 
   AttnDecodeArgs aa;
@@ -914,12 +916,12 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
     if (!batched && segs_) {  // packed prompts: per-row slot / position, attention per piece
       __half* kcl = kc_ + kv_layer * (l - opt_.layer_begin);  // slot 0's layer l; + slot * slot_stride_
       __half* vcl = vc_ + kv_layer * (l - opt_.layer_begin);
-      rope_kv_prefill(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, rpos_, rslots_, slot_stride_);
+      rope_kv_prefill(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, rpos_, rslots_, slot_stride_, L.bqkv);
       // every piece in one launch (up to 16 per launch; grid z = pieces): the pieces of a joint
       // admission ran one launch each, ~100 blocks apiece on a 256-CU chip
       const std::vector<PrefillSeg>& sg = *segs_;
       const int G = nh_l_ / std::max(1, nkv_l_);
-      const bool mfma = (G & (G - 1)) == 0 && G <= 16;
+      const bool mfma = G <= 16;  // (bf16 / f16 outputs: attn_prefill's MFMA kernel at every group size)
       for (size_t i0 = 0; i0 < sg.size();) {
         AttnPrefillArgs pa;
         pa.q = q_; pa.k_cache = kcl; pa.v_cache = vcl; pa.n_ctx = opt_.n_ctx;
@@ -950,7 +952,7 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
     } else if (!batched) {
       __half* kcl = kc_ + slot_stride_ * kv_slot_ + kv_layer * (l - opt_.layer_begin);
       __half* vcl = vc_ + slot_stride_ * kv_slot_ + kv_layer * (l - opt_.layer_begin);
-      rope_kv_prefill(qkv_, T, pos0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s);
+      rope_kv_prefill(qkv_, T, pos0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, nullptr, nullptr, 0, L.bqkv);
       AttnPrefillArgs pa;
       pa.q = q_; pa.k_cache = kcl; pa.v_cache = vcl; pa.T = T; pa.pos0 = pos0; pa.n_ctx = opt_.n_ctx;
       pa.n_head = nh_l_; pa.n_kv_head = nkv_l_; pa.head_dim = hd; pa.scale = 1.f / std::sqrt((float)hd);
@@ -961,7 +963,8 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
     } else {  // T decode rows, each of its own KV slot and position
       __half* kcl = kc_ + kv_layer * (l - opt_.layer_begin);  // slot 0's layer l; the kernels add slot * slot_stride_
       __half* vcl = vc_ + kv_layer * (l - opt_.layer_begin);
-      rope_kv_prefill(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, bpos_, bslots_, slot_stride_);
+      rope_kv_prefill(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, bpos_, bslots_, slot_stride_,
+                      L.bqkv);
       AttnDecodeArgs aa;
       aa.q = q_; aa.k_cache = kcl; aa.v_cache = vcl; aa.pos = bpos_;
       aa.n_ctx = opt_.n_ctx; aa.n_head = nh_l_; aa.n_kv_head = nkv_l_; aa.head_dim = hd;
@@ -1237,7 +1240,10 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
   const bool fnorm = fused && bmm_norm_fits(d, B);
   // Q|K|V split over K (the default at B <= 8): RoPE'd partial sums into qkv_b_, normalised and
   // appended to the caches by the attention
-  const bool sk = qkv_sk_ && bmm_qkv_sk_supported(L.t_wq.type, L.t_wk.type, L.t_wv.type, d, B);
+  // (Q|K|V biases: only with the RoPE deferred to the attention, which adds them to the normalised
+  // sums before rotating; the form with rotated partials takes the one-part / unfused path)
+  const bool sk = qkv_sk_ && bmm_qkv_sk_supported(L.t_wq.type, L.t_wk.type, L.t_wv.type, d, B) &&
+                  (!L.bqkv || bmm_qkv_sk_defers_rope());
   // FFN paths without the down projection's zero side job: a memset node re-zeroes qkv_b_ / ss_b_
   auto zero_qkv = [&]() {
     if (sk) HIPCHK(hipMemsetAsync(qkv_b_, 0, sizeof(float) * qkv_b_zero_n(), s));
@@ -1287,6 +1293,10 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
           a.qkv.k_cache = kcl; a.qkv.v_cache = vcl; a.qkv.slot_stride = slot_stride_;
           a.qkv.n_ctx = opt_.n_ctx; a.qkv.head_dim = hd;
           a.qkv.pos = bpos_ + b0; a.qkv.slots = bslots_ + b0; a.qkv.rope = rope_;
+          if (L.bqkv) {
+            const float* bias[3] = {L.bqkv, L.bqkv + nq_, L.bqkv + nq_ + nkvd_};
+            for (int k = 0; k < a.nseg; ++k) a.qkv.bias[k] = bias[i + k];
+          }
         }
         rl.push_back(a);
       }
@@ -1296,7 +1306,8 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     if (!(rl.size() == 2 && B <= kBmmMaxRows && bmm_qkv2(rl[0], rl[1], s)))
       for (const BmmArgs& a : rl) bmm(a, s);
     if (!fused)
-      rope_kv_prefill(qkv_, B, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, bpos_, bslots_, slot_stride_);
+      rope_kv_prefill(qkv_, B, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, bpos_, bslots_, slot_stride_,
+                      L.bqkv);
   }
   AttnDecodeArgs aa;
   aa.q = q_; aa.k_cache = kcl; aa.v_cache = vcl; aa.pos = bpos_;
@@ -1312,6 +1323,7 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     aa.qkv_raw = qkv_b_; aa.qkv_ld = ncol; aa.k_off = nq_; aa.v_off = nq_ + nkvd_;
     aa.ss = ss_b_; aa.inv_k = 1.f / (float)d; aa.eps = hp_.rms_eps;
     if (bmm_qkv_sk_defers_rope()) aa.rope_freq = rope_freq_;
+    aa.qkv_bias = L.bqkv;
   }
   aa.dbg_clk = clk_of(l, 1);
   // (the batched Wo stays its own launch: in one launch with the attention - Wo planes streaming

@@ -26,12 +26,7 @@
 
 namespace lfk {
 
-struct HParams {
-  int n_vocab = 0, n_embd = 0, n_layer = 0, n_head = 0, n_head_kv = 0, head_dim = 0, n_ff = 0;
-  int n_expert = 0, n_expert_used = 0, n_ctx_train = 0;
-  float rope_base = 10000.f, rms_eps = 1e-5f;
-};
-HParams read_hparams(const GGUFFile& f);
+// (HParams / read_hparams: gguf.h, shared with the CPU backend)
 
 struct EngineOptions {
   int n_ctx = 1024;
@@ -73,6 +68,7 @@ struct Layer {
   float* attn_norm = nullptr;
   float* ffn_norm = nullptr;
   QMat wq, wk, wv, wo;
+  float* bqkv = nullptr;             // Q|K|V biases [nq | nkvd | nkvd] (qwen2; null: none)
   QMat w_gu, w_down;                 // dense FFN (gate/up interleaved in 32-row groups)
   QMat router, gu_exps, down_exps;   // MoE
   // batched decode (bmm.hip): tile16 copies of the projections (base = the copy)
@@ -217,7 +213,8 @@ class Engine : public SlotBackend {
   void stage_commit(void* dev, size_t bytes);    // async copy of it to dev; flips buffers
   void stage_release();                          // waits for the copies, frees the buffers
   QMat upload_matrix(const GGUFFile& f, const std::string& name, size_t r0, size_t R, size_t c0, size_t K,
-                     int n_expert = 0);
+                     int n_expert = 0, size_t neox_hd = 0);
+  float* upload_qkv_bias(const GGUFFile& f, const std::string& layer_prefix);
   QMat upload_gate_up(const GGUFFile& f, const std::string& gate, const std::string& up, size_t f0, size_t F,
                       int n_expert = 0);
   float* upload_f32(const GGUFFile& f, const std::string& name);

@@ -213,4 +213,53 @@ void GGUFFile::prefetch(const GGUFTensor& t) const {
   madvise(const_cast<uint8_t*>(base_) + start, t.offset + t.nbytes - start, MADV_WILLNEED);
 }
 
+HParams read_hparams(const GGUFFile& f) {
+  HParams h;
+  const std::string arch = f.get_str("general.architecture", "llama");
+  if (arch != "llama" && arch != "mistral" && arch != "mixtral" && arch != "qwen2")
+    throw std::runtime_error("unsupported architecture " + arch);
+  h.arch = arch;
+  auto gi = [&](const char* k, int64_t d) { return (int)f.get_int(arch + "." + k, d); };
+  h.n_embd = gi("embedding_length", 0);
+  h.n_layer = gi("block_count", 0);
+  h.n_head = gi("attention.head_count", 0);
+  h.n_head_kv = gi("attention.head_count_kv", h.n_head);
+  h.head_dim = gi("rope.dimension_count", h.n_head ? h.n_embd / h.n_head : 0);
+  h.n_ff = gi("feed_forward_length", 0);
+  h.n_expert = gi("expert_count", 0);
+  h.n_expert_used = gi("expert_used_count", 0);
+  h.n_ctx_train = gi("context_length", 2048);
+  h.rope_base = (float)f.get_float(arch + ".rope.freq_base", 10000.0);
+  h.rms_eps = (float)f.get_float(arch + ".attention.layer_norm_rms_epsilon", 1e-5);
+  const GGUFTensor* emb = f.find("token_embd.weight");
+  if (!emb) throw std::runtime_error("missing token_embd.weight");
+  h.n_vocab = (int)emb->ne[1];
+  if (arch == "qwen2") {
+    h.rope_neox = true;
+    const std::string key = arch + ".rope.scaling.type";
+    if (f.has(key) && f.get_str(key, "") != "none")
+      throw std::runtime_error(key + " = " + f.get_str(key, "?") + ": RoPE scaling is not supported");
+    if (h.head_dim % 2) throw std::runtime_error("qwen2: head_dim must be even");
+    // the Q|K|V biases: all three of every layer, or none anywhere
+    int with = 0;
+    for (int l = 0; l < h.n_layer; ++l) {
+      const std::string p = "blk." + std::to_string(l) + ".attn_";
+      const char* names[3] = {"q.bias", "k.bias", "v.bias"};
+      int n = 0;
+      for (const char* nm : names) n += f.find(p + nm) != nullptr;
+      for (const char* nm : names) {
+        const GGUFTensor* t = f.find(p + nm);
+        if (n > 0 && !t) throw std::runtime_error("missing tensor " + p + nm + " (the layer has other Q|K|V biases)");
+        if (t && t->type != T_F32) throw std::runtime_error(p + nm + ": expected F32");
+      }
+      with += n == 3;
+    }
+    if (with != 0 && with != h.n_layer)
+      throw std::runtime_error("blk.N.attn_q.bias: present in " + std::to_string(with) + " of " +
+                               std::to_string(h.n_layer) + " layers");
+    h.qkv_bias = with > 0;
+  }
+  return h;
+}
+
 }  // namespace lfk

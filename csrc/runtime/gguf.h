@@ -67,4 +67,26 @@ class GGUFFile {
   std::map<std::string, size_t> index_;
 };
 
+// Model hyper-parameters as the GPU engine and the CPU backend read them from the metadata
+// (general.architecture llama / mistral / mixtral / qwen2; anything else is refused).
+struct HParams {
+  int n_vocab = 0, n_embd = 0, n_layer = 0, n_head = 0, n_head_kv = 0, head_dim = 0, n_ff = 0;
+  int n_expert = 0, n_expert_used = 0, n_ctx_train = 0;
+  float rope_base = 10000.f, rms_eps = 1e-5f;
+  std::string arch = "llama";
+  // NeoX RoPE pairs (i, i + head_dim / 2): the loaders permute the rows of attn_q / attn_k inside
+  // each head (neox_src_row) so that every kernel keeps rotating adjacent pairs
+  bool rope_neox = false;
+  // blk.N.attn_{q,k,v}.bias (F32) are present: added to the projections before RoPE
+  bool qkv_bias = false;
+};
+HParams read_hparams(const GGUFFile& f);
+
+// NeoX -> adjacent-pair row order inside a head: row 2i of the permuted projection is row i of
+// the file's, row 2i + 1 is row i + hd / 2 (`r` any row index of a matrix of whole heads)
+inline size_t neox_src_row(size_t r, size_t hd) {
+  const size_t j = r % hd;
+  return r - j + (j >> 1) + ((j & 1) ? hd / 2 : 0);
+}
+
 }  // namespace lfk

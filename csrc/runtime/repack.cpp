@@ -4,15 +4,17 @@
 #include <stdexcept>
 
 #include "../common.h"
+#include "gguf.h"
 
 namespace lfk {
 
 void repack_planar(int type, const uint8_t* src, size_t K_src, size_t r0, size_t R, size_t c0, size_t K,
-                   uint8_t* dst, size_t R_dst, int G, int off) {
+                   uint8_t* dst, size_t R_dst, int G, int off, size_t neox_hd) {
   const TypeInfo ti = type_info(type);
   if (K % ti.block || c0 % ti.block || K_src % ti.block) throw std::runtime_error("repack: unaligned column slice");
   const size_t nb_src = K_src / ti.block, nb = K / ti.block, b0 = c0 / ti.block;
   const Planes P = planes_of(type, R_dst, K);
+  if (neox_hd && (neox_hd % 2 || r0 % neox_hd || R % neox_hd)) throw std::runtime_error("repack: NeoX rows must be whole heads");
   switch (type) {
     case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_Q8_0: case T_F16: case T_BF16: case T_F32: break;
     case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: break;
@@ -22,7 +24,7 @@ void repack_planar(int type, const uint8_t* src, size_t K_src, size_t r0, size_t
   for (long long ii = 0; ii < (long long)R; ++ii) {
     const size_t i = (size_t)ii;
     const size_t dr = G > 0 ? (i / G) * 2 * G + off + i % G : off + i;
-    const uint8_t* srow = src + ((r0 + i) * nb_src + b0) * ti.bytes;
+    const uint8_t* srow = src + ((r0 + (neox_hd ? neox_src_row(i, neox_hd) : i)) * nb_src + b0) * ti.bytes;
     switch (type) {
       case T_Q4_K:
         for (size_t b = 0; b < nb; ++b) {

@@ -121,7 +121,11 @@ def guess_chat_format(metadata: dict) -> Optional[str]:
     tmpl = metadata.get("tokenizer.chat_template")
     if tmpl is None:
         return None
-    return KNOWN_TEMPLATES.get(tmpl)
+    known = KNOWN_TEMPLATES.get(tmpl)
+    # a Qwen2 / Qwen2.5 template (ChatML behind a long tool-calling preamble) matches none exactly
+    if known is None and metadata.get("general.architecture") == "qwen2":
+        return "chatml"
+    return known
 
 
 def get_formatter(metadata: dict, chat_format: Optional[str], bos_token: str, eos_token: str):

@@ -24,6 +24,9 @@ from ..gguf.constants import (TOKEN_TYPE_BYTE, TOKEN_TYPE_CONTROL, TOKEN_TYPE_NO
 
 LLAMA3_PRETOKENIZE = (r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}|"
                       r" ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+")
+# Qwen2: the contractions by case class (no (?i:...)), digits one at a time
+QWEN2_PRETOKENIZE = (r"(?:'[sS]|'[tT]|'[rR][eE]|'[vV][eE]|'[mM]|'[lL][lL]|'[dD])|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}|"
+                     r" ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+")
 GPT2_PRETOKENIZE = r"""'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"""
 
 
@@ -46,6 +49,7 @@ class _Base:
     types: List[int]
     bos_id: int
     eos_id: int
+    add_bos_token: bool = True   # tokenizer.ggml.add_bos_token: False = encode(add_bos=True) adds none
 
     def _init_specials(self):
         self.token_to_id: Dict[str, int] = {t: i for i, t in enumerate(self.tokens)}
@@ -78,7 +82,7 @@ class _Base:
             yield False, text[pos:]
 
     def encode(self, text: str, add_bos: bool = True, special: bool = True) -> List[int]:
-        out: List[int] = [self.bos_id] if (add_bos and self.bos_id >= 0) else []
+        out: List[int] = [self.bos_id] if (add_bos and self.add_bos_token and self.bos_id >= 0) else []
         first = True
         for is_special, seg in self._split_special(text, special):
             if is_special:
@@ -94,8 +98,10 @@ class _Base:
 
 class BPETokenizer(_Base):
     def __init__(self, tokens: List[str], merges: List[str], types: Optional[List[int]] = None,
-                 bos_id: int = -1, eos_id: int = -1, eot_id: int = -1, pre: str = "llama-bpe"):
+                 bos_id: int = -1, eos_id: int = -1, eot_id: int = -1, pre: str = "llama-bpe",
+                 add_bos_token: bool = True):
         self.tokens = tokens
+        self.add_bos_token = bool(add_bos_token)
         self.types = list(types) if types is not None else [TOKEN_TYPE_NORMAL] * len(tokens)
         self.bos_id, self.eos_id = bos_id, eos_id
         self.eog_ids = {t for t in (eos_id, eot_id) if t >= 0}
@@ -106,7 +112,9 @@ class BPETokenizer(_Base):
         self.byte_encoder = bytes_to_unicode()
         self.byte_decoder = {v: k for k, v in self.byte_encoder.items()}
         self.pre_re = regex.compile(LLAMA3_PRETOKENIZE if pre in ("llama-bpe", "llama3", "default")
-                                    else GPT2_PRETOKENIZE)
+                                    else QWEN2_PRETOKENIZE if pre == "qwen2" else GPT2_PRETOKENIZE)
+        if pre == "qwen2":  # two end-of-generation tokens beside the file's eos
+            self.eog_ids |= {tokens.index(t) for t in ("<|im_end|>", "<|endoftext|>") if t in tokens}
         self._cache: Dict[str, List[int]] = {}
         self._init_specials()
 
@@ -160,8 +168,10 @@ class SPMTokenizer(_Base):
     SPACE = "▁"
 
     def __init__(self, pieces: List[str], scores: List[float], types: List[int],
-                 bos_id: int = 1, eos_id: int = 2, unk_id: int = 0, add_space_prefix: bool = True):
+                 bos_id: int = 1, eos_id: int = 2, unk_id: int = 0, add_space_prefix: bool = True,
+                 add_bos_token: bool = True):
         self.tokens = pieces
+        self.add_bos_token = bool(add_bos_token)
         self.scores = scores
         self.types = list(types)
         self.bos_id, self.eos_id, self.unk_id = bos_id, eos_id, unk_id
@@ -251,10 +261,13 @@ def tokenizer_from_metadata(md: dict):
             if name in tokens:
                 eot = tokens.index(name)
                 break
-        return BPETokenizer(tokens, md.get("tokenizer.ggml.merges", []), types, bos, eos, eot,
-                            md.get("tokenizer.ggml.pre", "llama-bpe"))
+        pre = md.get("tokenizer.ggml.pre", "llama-bpe")
+        # (Qwen2 files say add_bos_token = false; for that pre-tokenizer an absent key means the same)
+        add_bos = bool(md.get("tokenizer.ggml.add_bos_token", pre != "qwen2"))
+        return BPETokenizer(tokens, md.get("tokenizer.ggml.merges", []), types, bos, eos, eot, pre, add_bos)
     if model == "llama":
         return SPMTokenizer(tokens, md.get("tokenizer.ggml.scores", [0.0] * len(tokens)), types, bos, eos,
                             int(md.get("tokenizer.ggml.unknown_token_id", 0)),
-                            bool(md.get("tokenizer.ggml.add_space_prefix", True)))
+                            bool(md.get("tokenizer.ggml.add_space_prefix", True)),
+                            bool(md.get("tokenizer.ggml.add_bos_token", True)))
     raise NotImplementedError(f"tokenizer model {model!r}")

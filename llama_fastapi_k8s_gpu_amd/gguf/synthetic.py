@@ -50,6 +50,12 @@ MISTRAL_CHAT_TEMPLATE = (
     "{{ message['content'] + eos_token}}{% else %}{{ raise_exception('Only user and assistant "
     "roles are supported!') }}{% endif %}{% endfor %}")
 
+CHATML_CHAT_TEMPLATE = (
+    "{% for message in messages %}{{'<|im_start|>' + message['role'] + '\n' + message['content'] + "
+    "'<|im_end|>' + '\n'}}{% endfor %}{% if add_generation_prompt %}{{ '<|im_start|>assistant\n' }}"
+    "{% endif %}")
+
+QWEN2_SPECIALS = {0: "<|endoftext|>", 1: "<|im_start|>", 2: "<|im_end|>"}
 LLAMA3_SPECIALS = {0: "<|begin_of_text|>", 1: "<|end_of_text|>", 6: "<|start_header_id|>",
                    7: "<|end_header_id|>", 9: "<|eot_id|>"}
 
@@ -73,6 +79,9 @@ class ModelSpec:
     size_class: str = "8B"    # "8B" | "70B" (affects the Q4_K_M attn_v rule)
     weight_std: float = 0.02
     chat_template: Optional[str] = None
+    arch: str = "llama"       # general.architecture: "llama" | "qwen2" (keys under it; NeoX RoPE, no BOS)
+    qkv_bias: bool = False    # F32 blk.N.attn_{q,k,v}.bias (Qwen2)
+    tied_output: bool = False  # no output.weight: the head is token_embd.weight
 
     @property
     def head_dim(self) -> int:
@@ -151,6 +160,26 @@ SPECS: Dict[str, ModelSpec] = {
                                  n_ctx_train=512),
 }
 
+# Qwen2 / Qwen2.5: Q|K|V biases, NeoX RoPE, GQA groups that are no power of two (7, 6, 5), no BOS
+def _qwen2(name, d, n_layer, n_head, n_kv, n_ff, quant, n_vocab=0, **kw):
+    return ModelSpec(name, d, n_layer, n_head, n_kv, n_ff, n_vocab, 1e6, "bpe", quant, n_ctx_train=1024,
+                     rms_eps=1e-6, arch="qwen2", qkv_bias=True, **kw)
+
+
+SPECS.update({
+    "tiny-qwen2-g7": _qwen2("tiny-qwen2-g7", 1792, 2, 14, 2, 512, "q4_k_m"),
+    "tiny-qwen2-g6-hd64": _qwen2("tiny-qwen2-g6-hd64", 768, 2, 12, 2, 512, "q4_k_m", tied_output=True),
+    "tiny-qwen2-g5": _qwen2("tiny-qwen2-g5", 1280, 2, 10, 2, 512, "mixed-test"),
+    # the 0.5B geometry: K = 896 is no multiple of 256 (no K-quants, no tile16 copies)
+    "tiny-qwen2-d896": _qwen2("tiny-qwen2-d896", 896, 2, 14, 2, 512, "q8_0"),
+    # TP = 2 at G = 7: kv heads move in pairs (2 x 7 x 128 q columns = whole 256-wide superblocks),
+    # so 4 kv heads is the smallest split shard.h accepts
+    "tiny-qwen2-tp": _qwen2("tiny-qwen2-tp", 3584, 2, 28, 4, 512, "q4_k_m"),
+    # Qwen2.5-7B-Instruct's shape (for measuring, not for tests)
+    "qwen2.5-7b-q4_k_m": replace(_qwen2("Qwen2.5-7B", 3584, 28, 28, 4, 18944, "q4_k_m", n_vocab=152064),
+                                 n_ctx_train=32768),
+})
+
 # the legacy 32-weight block formats (Q4_0 / Q4_1 / Q5_0 / Q5_1) over existing shapes
 SPECS.update({
     "tiny-llama3-q4_0": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama3-q4_0", quant="q4_0"),
@@ -228,10 +257,19 @@ def build_vocab(spec: ModelSpec) -> Tuple[Dict, int]:
                 tokens.append(cand)
         base = len(tokens)
         types = [TOKEN_TYPE_NORMAL] * base
+        qwen2 = spec.arch == "qwen2"
         for k in range(256):
-            name = LLAMA3_SPECIALS.get(k, f"<|reserved_special_token_{k}|>")
+            name = (QWEN2_SPECIALS if qwen2 else LLAMA3_SPECIALS).get(k, f"<|reserved_special_token_{k}|>")
             tokens.append(name)
             types.append(TOKEN_TYPE_CONTROL)
+        if qwen2:  # no BOS, eos = <|im_end|>, ChatML
+            md = {"tokenizer.ggml.model": "gpt2", "tokenizer.ggml.pre": "qwen2",
+                  "tokenizer.ggml.tokens": tokens, "tokenizer.ggml.token_type": types,
+                  "tokenizer.ggml.merges": v["merges"],
+                  "tokenizer.ggml.bos_token_id": base + 0, "tokenizer.ggml.eos_token_id": base + 2,
+                  "tokenizer.ggml.padding_token_id": base + 0, "tokenizer.ggml.add_bos_token": False,
+                  "tokenizer.chat_template": spec.chat_template or CHATML_CHAT_TEMPLATE}
+            return md, len(tokens)
         md = {"tokenizer.ggml.model": "gpt2", "tokenizer.ggml.pre": "llama-bpe",
               "tokenizer.ggml.tokens": tokens, "tokenizer.ggml.token_type": types,
               "tokenizer.ggml.merges": v["merges"],
@@ -282,6 +320,9 @@ def tensor_plan(spec: ModelSpec, n_vocab: int) -> List[Tuple[str, GGMLType, Tupl
                  (p + "attn_v.weight", tt["attn_v"], (d, dkv)),
                  (p + "attn_output.weight", tt["attn_output"], (d, d)),
                  (p + "ffn_norm.weight", GGMLType.F32, (d,))]
+        if spec.qkv_bias:
+            plan += [(p + "attn_q.bias", GGMLType.F32, (d,)), (p + "attn_k.bias", GGMLType.F32, (dkv,)),
+                     (p + "attn_v.bias", GGMLType.F32, (dkv,))]
         if spec.n_expert:
             E = spec.n_expert
             plan += [(p + "ffn_gate_inp.weight", GGMLType.F32, (d, E)),
@@ -292,12 +333,14 @@ def tensor_plan(spec: ModelSpec, n_vocab: int) -> List[Tuple[str, GGMLType, Tupl
             plan += [(p + "ffn_gate.weight", tt["ffn_gate"], (d, f)),
                      (p + "ffn_down.weight", tt["ffn_down"], (f, d)),
                      (p + "ffn_up.weight", tt["ffn_up"], (d, f))]
-    plan += [("output_norm.weight", GGMLType.F32, (d,)), ("output.weight", out_t, (d, n_vocab))]
+    plan += [("output_norm.weight", GGMLType.F32, (d,))]
+    if not spec.tied_output:
+        plan += [("output.weight", out_t, (d, n_vocab))]
     return plan
 
 
 def hparams_metadata(spec: ModelSpec, n_vocab: int) -> Dict:
-    a = "llama"
+    a = spec.arch
     if spec.quant in LEGACY_QUANTS:
         ftype = LEGACY_QUANTS[spec.quant][1]
     else:
@@ -313,11 +356,22 @@ def hparams_metadata(spec: ModelSpec, n_vocab: int) -> Dict:
     if spec.n_expert:
         md[f"{a}.expert_count"] = spec.n_expert
         md[f"{a}.expert_used_count"] = spec.n_expert_used
+    if a == "qwen2":  # (Qwen2 files carry no rope.dimension_count: head_dim = n_embd / n_head)
+        del md[f"{a}.rope.dimension_count"]
     return md
 
 
-def write_synthetic_gguf(spec, path: str, seed: int = 0, log=None) -> str:
-    """Stream a random-init GGUF for ``spec`` (a ModelSpec or a SPECS key) to ``path``."""
+def qkv_bias_std(spec: ModelSpec) -> float:
+    return 4.0 * spec.weight_std * float(np.sqrt(spec.n_embd))
+
+
+def write_synthetic_gguf(spec, path: str, seed: int = 0, log=None, extra_metadata: Optional[Dict] = None,
+                         skip_tensors: Tuple[str, ...] = (), untie_output: bool = False) -> str:
+    """Stream a random-init GGUF for ``spec`` (a ModelSpec or a SPECS key) to ``path``.
+
+    For loader tests: ``extra_metadata`` adds keys, ``skip_tensors`` leaves tensors out (the other
+    tensors keep the values they have in the full file), and ``untie_output`` writes a
+    ``tied_output`` spec's head as an explicit ``output.weight`` holding token_embd's own blocks."""
     if isinstance(spec, str):
         spec = SPECS[spec]
     rng = np.random.default_rng(seed)
@@ -335,19 +389,36 @@ def write_synthetic_gguf(spec, path: str, seed: int = 0, log=None) -> str:
             w.add(k, int(v), GGUFValueType.UINT32)
         else:
             w.add(k, v)
+    for k, v in (extra_metadata or {}).items():
+        w.add(k, v)
     plan = tensor_plan(spec, n_vocab)
+    if untie_output and spec.tied_output:
+        plan.append(("output.weight", plan[0][1], plan[0][2]))
     for name, t, shape in plan:
-        w.declare_tensor(name, t, shape)
+        if name not in skip_tensors:
+            w.declare_tensor(name, t, shape)
     w.begin()
+    embd = None
     for name, t, shape in plan:
         n = int(np.prod(shape))
+        if name == "output.weight" and untie_output and spec.tied_output:
+            w.write_tensor_data(embd)
+            continue
         if name.endswith("norm.weight"):
             data = (1.0 + 0.1 * rng.standard_normal(n)).astype(np.float32)
+        elif name.endswith(".bias"):
+            # four times the standard deviation of the projection's own output on a normed input
+            # (weight_std * sqrt(d)): real Qwen2 biases are large, and a dropped one must show
+            data = (qkv_bias_std(spec) * rng.standard_normal(n)).astype(np.float32)
         else:
             std = spec.weight_std
             if name == "token_embd.weight":
                 std = 1.0  # keeps the first RMSNorm well conditioned
             data = random_blocks(t, n, rng, std=std)
+        if name == "token_embd.weight" and untie_output:
+            embd = data
+        if name in skip_tensors:
+            continue
         w.write_tensor_data(data)
         if log:
             log(name)

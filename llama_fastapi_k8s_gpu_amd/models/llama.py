@@ -12,6 +12,11 @@ runs the upstream ``llm_build_llama`` op sequence in float32:
                x += Wdown(silu(Wgate h) * Wup h)          (dense)
                x += sum_e w_e Wdown_e(silu(Wgate_e h)*Wup_e h)  (MoE, top-k, renorm)
     logits = Wout rms(x)*w
+
+``general.architecture = qwen2`` (Qwen2 / Qwen2.5) is the same decoder with F32 biases on the Q, K
+and V projections (added before RoPE) and NeoX RoPE pairs (i, i + head_dim/2). The reference
+rotates those pairs on the file's own weight rows - the native backends instead permute the rows
+and keep rotating adjacent pairs, so this forward is an independent check of that.
 """
 from __future__ import annotations
 
@@ -35,6 +40,9 @@ class LlamaHParams:
     rope_base: float
     rms_eps: float
     n_ctx_train: int
+    arch: str = "llama"
+    rope_neox: bool = False      # RoPE pairs (i, i + head_dim/2) instead of (2i, 2i+1)
+    qkv_bias: bool = False       # blk.N.attn_{q,k,v}.bias present (set by the loaders from the tensors)
 
     @property
     def n_embd_kv(self) -> int:
@@ -47,9 +55,12 @@ class LlamaHParams:
     @classmethod
     def from_metadata(cls, md: Dict) -> "LlamaHParams":
         arch = md.get("general.architecture", "llama")
-        if arch not in ("llama", "mistral", "mixtral"):
+        if arch not in ("llama", "mistral", "mixtral", "qwen2"):
             raise NotImplementedError(f"architecture {arch!r} is not supported")
         g = lambda k, d=None: md.get(f"{arch}.{k}", d)
+        if arch == "qwen2" and g("rope.scaling.type", "none") not in (None, "none"):
+            raise NotImplementedError(f"{arch}.rope.scaling.type = {g('rope.scaling.type')!r}: RoPE scaling "
+                                      "is not supported")
         n_embd = int(g("embedding_length"))
         n_head = int(g("attention.head_count"))
         n_vocab = int(g("vocab_size", 0) or len(md.get("tokenizer.ggml.tokens", [])))
@@ -60,7 +71,7 @@ class LlamaHParams:
                    n_expert_used=int(g("expert_used_count", 0) or 0),
                    rope_base=float(g("rope.freq_base", 10000.0)),
                    rms_eps=float(g("attention.layer_norm_rms_epsilon", 1e-5)),
-                   n_ctx_train=int(g("context_length", 2048)))
+                   n_ctx_train=int(g("context_length", 2048)), arch=arch, rope_neox=arch == "qwen2")
 
 
 def rope_tables(hp: LlamaHParams, n_pos: int):
@@ -96,7 +107,10 @@ class ReferenceLlama:
     fp32 model.
     """
 
-    def __init__(self, reader, n_ctx: int = 512, device: str = "cpu"):
+    def __init__(self, reader, n_ctx: int = 512, device: str = "cpu", rope_neox: Optional[bool] = None,
+                 qkv_bias: bool = True):
+        """``rope_neox`` overrides the architecture's RoPE pairing and ``qkv_bias=False`` drops the
+        Q|K|V biases: deliberately wrong models, for tests that show a check would catch them."""
         import torch
         self.torch = torch
         self.reader = reader
@@ -106,6 +120,8 @@ class ReferenceLlama:
         hp = self.hp
         if not hp.n_vocab:
             hp.n_vocab = reader.tensors["token_embd.weight"].shape[1]
+        if rope_neox is not None:
+            hp.rope_neox = bool(rope_neox)
         self.n_ctx = n_ctx
         t = lambda name: torch.from_numpy(np.ascontiguousarray(reader.dequant(name))).to(device)
         self.tok_embd = t("token_embd.weight")
@@ -123,6 +139,13 @@ class ReferenceLlama:
             else:
                 for k in ("ffn_gate", "ffn_up", "ffn_down"):
                     L[k] = t(p + k + ".weight")
+            have = [k for k in ("attn_q", "attn_k", "attn_v") if p + k + ".bias" in reader.tensors]
+            if have and len(have) != 3:
+                raise ValueError(f"{p}{have[0]}.bias without the other Q|K|V biases of the layer")
+            if have and qkv_bias:
+                hp.qkv_bias = True
+                for k in have:
+                    L[k + "_b"] = t(p + k + ".bias")
             L["_prefix"] = p
             self.layers.append(L)
         cos, sin = rope_tables(hp, n_ctx)
@@ -201,9 +224,13 @@ class ReferenceLlama:
         return {"prefill": "bf16", "batch": "f16", "prefill16": "f16"}.get(path, "f32")
 
     def _rope(self, x, pos):
-        # x [T, H, D]; adjacent pairs (2i, 2i+1)
+        # x [T, H, D]; adjacent pairs (2i, 2i+1), or NeoX pairs (i, i + D/2): rotate-half
         c = self.cos[pos][:, None, :]
         s = self.sin[pos][:, None, :]
+        if self.hp.rope_neox:
+            half = x.shape[-1] // 2
+            x0, x1 = x[..., :half], x[..., half:]
+            return self.torch.cat([x0 * c - x1 * s, x0 * s + x1 * c], dim=-1)
         x0, x1 = x[..., 0::2], x[..., 1::2]
         out = self.torch.empty_like(x)
         out[..., 0::2] = x0 * c - x1 * s
@@ -310,9 +337,12 @@ class ReferenceLlama:
         wk = self._wkind(path)
         for li, L in enumerate(self.layers):
             h = self._normed_input(x, L["attn_norm"], path, attn=True)
-            q = (h @ self._weight("attn_q", L, wk).T).view(T, hp.n_head, hp.head_dim)
-            k = (h @ self._weight("attn_k", L, wk).T).view(T, hp.n_head_kv, hp.head_dim)
-            v = (h @ self._weight("attn_v", L, wk).T).view(T, hp.n_head_kv, hp.head_dim)
+            q, k, v = (h @ self._weight(n, L, wk).T for n in ("attn_q", "attn_k", "attn_v"))
+            if "attn_q_b" in L:   # qwen2: biases on the projections, before RoPE
+                q, k, v = q + L["attn_q_b"], k + L["attn_k_b"], v + L["attn_v_b"]
+            q = q.view(T, hp.n_head, hp.head_dim)
+            k = k.view(T, hp.n_head_kv, hp.head_dim)
+            v = v.view(T, hp.n_head_kv, hp.head_dim)
             q, k = self._rope(q, pos), self._rope(k, pos)
             if path is not None:   # the engine's KV cache is f16
                 k, v = self._f16(k), self._f16(v)
