@@ -264,6 +264,14 @@ PYBIND11_MODULE(_cpu, m) {
     return dst;
   });
 
+  // tensor name -> ggml type as the C++ GGUF reader (runtime/gguf.cpp) sees the file
+  m.def("gguf_tensor_types", [](const std::string& path) {
+    GGUFFile f(path);
+    py::dict d;
+    for (const GGUFTensor& t : f.tensors()) d[py::str(t.name)] = t.type;
+    return d;
+  });
+
   py::class_<FakeSlotEngine>(m, "FakeSlotEngine")
       .def(py::init<int, int, int, int, int>(), py::arg("n_slots"), py::arg("max_batch"), py::arg("n_ctx"),
            py::arg("vocab") = 1000, py::arg("step_us") = 0)

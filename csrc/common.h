@@ -16,6 +16,14 @@
 //   Q5_1 : qs[R][K/32][16]   | qh[R][K/32] (u32) | dm[R][K/32][2] (f16 d, m)
 //          (legacy 32-weight blocks: byte j of a block's qs holds weight j in its low
 //           nibble and weight j + 16 in its high nibble; bit j of qh is weight j's 5th bit)
+//   Q2_K : qs[R][K/256][64]  | sc[R][K/256][16] | dm[R][K/256][2] (f16 d, dmin)
+//   Q3_K : qs[R][K/256][64]  | hmask[R][K/256][32] | sc[R][K/256][12] | d[R][K/256] (f16)
+//          (2- and 3-bit K-quants: the fields keep their GGUF byte order. Byte 32n + l of a
+//           block's qs holds the low two bits of weights 128n + 32j + l, j = 0..3, at bit 2j; bit
+//           4n + j of hmask[l] is Q3_K's third bit of the same weight; sc holds Q2_K's sixteen
+//           (scale | min << 4) bytes or Q3_K's sixteen packed 6-bit scales. Q3_K's 12-byte scale
+//           rows are 4-byte aligned, and its sc / d planes start 16-byte aligned when R * K / 256
+//           is a multiple of 4 (4-byte aligned otherwise): they are read as dwords / halves.)
 //   F16 / F32 : [R][K] unchanged
 //
 // Total bytes are identical to the GGUF tensor (no padding), so 4.6 GB of
@@ -36,6 +44,8 @@ enum QType : int {
   T_Q5_0 = 6,
   T_Q5_1 = 7,
   T_Q8_0 = 8,
+  T_Q2_K = 10,
+  T_Q3_K = 11,
   T_Q4_K = 12,
   T_Q5_K = 13,
   T_Q6_K = 14,
@@ -57,6 +67,8 @@ inline TypeInfo type_info(int t) {
     case T_Q5_0: return {32, 22};
     case T_Q5_1: return {32, 24};
     case T_Q8_0: return {32, 34};
+    case T_Q2_K: return {256, 84};
+    case T_Q3_K: return {256, 110};
     case T_Q4_K: return {256, 144};
     case T_Q5_K: return {256, 176};
     case T_Q6_K: return {256, 210};
@@ -68,15 +80,18 @@ inline bool is_legacy_block_type(int t) { return t == T_Q4_0 || t == T_Q4_1 || t
 
 // MoE expert tensors of the legacy 32-weight block types are not supported (attention, router
 // and embeddings of such a file are): refuse the model at load, naming the tensor.
+// The same holds for the 2- and 3-bit K-quants Q2_K and Q3_K.
 inline void check_expert_type(const std::string& tensor, int t) {
-  if (!is_legacy_block_type(t)) return;
-  const char* n = t == T_Q4_0 ? "Q4_0" : t == T_Q4_1 ? "Q4_1" : t == T_Q5_0 ? "Q5_0" : "Q5_1";
+  if (!is_legacy_block_type(t) && t != T_Q2_K && t != T_Q3_K) return;
+  const char* n = t == T_Q4_0 ? "Q4_0" : t == T_Q4_1 ? "Q4_1" : t == T_Q5_0 ? "Q5_0" : t == T_Q5_1 ? "Q5_1"
+                  : t == T_Q2_K ? "Q2_K" : "Q3_K";
   throw std::runtime_error("unsupported expert tensor " + tensor + ": type " + n +
                            " (MoE experts must be Q4_K, Q5_K, Q6_K, Q8_0, F16 or F32)");
 }
 
 inline size_t qbytes(int t, size_t rows, size_t K) {
   TypeInfo ti = type_info(t);
+  if (K % ti.block) throw std::runtime_error("qbytes: K must be a multiple of the type's block size");
   return rows * (K / ti.block) * ti.bytes;
 }
 
@@ -106,6 +121,14 @@ LFK_HD Planes planes_of(int t, size_t R, size_t K) {
       break;
     case T_Q6_K:
       p.s0 = nsb * 128; p.s1 = nsb * 64; p.s2 = nsb * 16; p.s3 = nsb * 2;
+      p.p0 = 0; p.p1 = R * p.s0; p.p2 = p.p1 + R * p.s1; p.p3 = p.p2 + R * p.s2;
+      break;
+    case T_Q2_K:
+      p.s0 = nsb * 64; p.s1 = nsb * 16; p.s2 = nsb * 4;
+      p.p0 = 0; p.p1 = R * p.s0; p.p2 = p.p1 + R * p.s1;
+      break;
+    case T_Q3_K:
+      p.s0 = nsb * 64; p.s1 = nsb * 32; p.s2 = nsb * 12; p.s3 = nsb * 2;
       p.p0 = 0; p.p1 = R * p.s0; p.p2 = p.p1 + R * p.s1; p.p3 = p.p2 + R * p.s2;
       break;
     case T_Q8_0:

@@ -138,6 +138,12 @@ inline void scale_min_k4(int j, const uint8_t* q, int& sc, int& m) {
   else { sc = (q[j + 4] & 0xF) | ((q[j - 4] >> 6) << 4); m = (q[j + 4] >> 4) | ((q[j] >> 6) << 4); }
 }
 
+// Q3_K's 6-bit scale s (0..15) from the 12 packed bytes (before the -32)
+inline int q3k_scale(const uint8_t* q, int s) {
+  const int low = s < 8 ? (q[s] & 0xF) : (q[s - 8] >> 4);
+  return low | (((q[8 + (s & 3)] >> (2 * (s >> 2))) & 3) << 4);
+}
+
 inline float hf(const uint8_t* p) { uint16_t h; std::memcpy(&h, p, 2); return h2f(h); }
 
 void decode_chunk(const CpuMat& W, const uint8_t* base, size_t row, int c, Chunk& ch) {
@@ -216,6 +222,39 @@ void decode_chunk(const CpuMat& W, const uint8_t* base, size_t row, int c, Chunk
       ch.m_lo = ch.m_hi = has_m ? -hf(sp + 4 * c + 2) : (five ? 16.f : 8.f) * d;
       break;
     }
+    case T_Q2_K:
+    case T_Q3_K: {
+      // chunk j = (g, h) as Q4_K's: low run at 64 g + 16 h (sub-block 4 g + h), high run 32 further
+      // (sub-block + 2); both come from qs bytes 32 (g >> 1) + 16 h .. + 15 at bit 4 (g & 1) / + 2
+      const int g = j >> 1, h = j & 1, n = g >> 1, e = g & 1, s = 4 * g + h;
+      const uint8_t* qs = base + P.p0 + row * P.s0 + 64 * sb + 32 * n + 16 * h;
+      ch.off_lo = sb * 256 + 64 * g + 16 * h;
+      ch.off_hi = ch.off_lo + 32;
+      if (W.type == T_Q2_K) {
+        const uint8_t* sc = base + P.p1 + row * P.s1 + 16 * sb;
+        const uint8_t* dm = base + P.p2 + row * P.s2 + 4 * sb;
+        const float d = hf(dm), dmin = hf(dm + 2);
+        for (int i = 0; i < 16; ++i) {
+          ch.w[i] = (int8_t)((qs[i] >> (4 * e)) & 3);
+          ch.w[16 + i] = (int8_t)((qs[i] >> (4 * e + 2)) & 3);
+        }
+        ch.s_lo = d * (sc[s] & 0xF); ch.m_lo = dmin * (sc[s] >> 4);
+        ch.s_hi = d * (sc[s + 2] & 0xF); ch.m_hi = dmin * (sc[s + 2] >> 4);
+      } else {
+        const uint8_t* hm = base + P.p1 + row * P.s1 + 32 * sb + 16 * h;
+        const uint8_t* sc = base + P.p2 + row * P.s2 + 12 * sb;
+        const float d = hf(base + P.p3 + row * P.s3 + 2 * sb);
+        const int b = 4 * n + 2 * e;
+        for (int i = 0; i < 16; ++i) {
+          ch.w[i] = (int8_t)(((qs[i] >> (4 * e)) & 3) | (((hm[i] >> b) & 1) << 2));
+          ch.w[16 + i] = (int8_t)(((qs[i] >> (4 * e + 2)) & 3) | (((hm[i] >> (b + 1)) & 1) << 2));
+        }
+        // w = d (sc - 32) (q - 4): the -4 as the m term
+        ch.s_lo = d * (float)(q3k_scale(sc, s) - 32); ch.m_lo = 4.f * ch.s_lo;
+        ch.s_hi = d * (float)(q3k_scale(sc, s + 2) - 32); ch.m_hi = 4.f * ch.s_hi;
+      }
+      break;
+    }
     case T_F32:
     case T_F16: {
       ch.is_float = true;
@@ -279,6 +318,32 @@ inline __m256i chunk_w(const CpuMat& W, const uint8_t* base, size_t row, int c, 
     s_hi = d * sc[si + 4]; m_hi = 32.f * s_hi;
     off_lo = sb * 256 + 128 * n + o;
     off_hi = off_lo + 64;
+    return _mm256_set_m128i(hi, lo);
+  } else if constexpr (QT == T_Q2_K || QT == T_Q3_K) {
+    const int g = j >> 1, h = j & 1, n = g >> 1, e = g & 1, s = 4 * g + h;  // as decode_chunk
+    const __m128i m3 = _mm_set1_epi8(3);
+    const __m128i q = _mm_loadu_si128(reinterpret_cast<const __m128i*>(base + P.p0 + row * P.s0 + 64 * sb + 32 * n + 16 * h));
+    __m128i lo = _mm_and_si128(_mm_srl_epi16(q, _mm_cvtsi32_si128(4 * e)), m3);
+    __m128i hi = _mm_and_si128(_mm_srl_epi16(q, _mm_cvtsi32_si128(4 * e + 2)), m3);
+    if constexpr (QT == T_Q2_K) {
+      const uint8_t* sc = base + P.p1 + row * P.s1 + 16 * sb;
+      const uint8_t* dm = base + P.p2 + row * P.s2 + 4 * sb;
+      const float d = hf(dm), dmin = hf(dm + 2);
+      s_lo = d * (sc[s] & 0xF); m_lo = dmin * (sc[s] >> 4);
+      s_hi = d * (sc[s + 2] & 0xF); m_hi = dmin * (sc[s + 2] >> 4);
+    } else {
+      const __m128i hm = _mm_loadu_si128(reinterpret_cast<const __m128i*>(base + P.p1 + row * P.s1 + 32 * sb + 16 * h));
+      const __m128i one = _mm_set1_epi8(1);
+      const int b = 4 * n + 2 * e;
+      lo = _mm_or_si128(lo, _mm_slli_epi16(_mm_and_si128(_mm_srl_epi16(hm, _mm_cvtsi32_si128(b)), one), 2));
+      hi = _mm_or_si128(hi, _mm_slli_epi16(_mm_and_si128(_mm_srl_epi16(hm, _mm_cvtsi32_si128(b + 1)), one), 2));
+      const uint8_t* sc = base + P.p2 + row * P.s2 + 12 * sb;
+      const float d = hf(base + P.p3 + row * P.s3 + 2 * sb);
+      s_lo = d * (float)(q3k_scale(sc, s) - 32); m_lo = 4.f * s_lo;
+      s_hi = d * (float)(q3k_scale(sc, s + 2) - 32); m_hi = 4.f * s_hi;
+    }
+    off_lo = sb * 256 + 64 * g + 16 * h;
+    off_hi = off_lo + 32;
     return _mm256_set_m128i(hi, lo);
   } else if constexpr (QT == T_Q4_0 || QT == T_Q4_1 || QT == T_Q5_0 || QT == T_Q5_1) {
     constexpr bool five = QT == T_Q5_0 || QT == T_Q5_1, has_m = QT == T_Q4_1 || QT == T_Q5_1;
@@ -370,6 +435,8 @@ void gemm_rows(const CpuMat& W, const uint8_t* base, const Q8& xq, int T, float*
     case T_Q4_1: return gemm_rows_avx2<T_Q4_1>(W, base, xq, T, y, ldy, add);
     case T_Q5_0: return gemm_rows_avx2<T_Q5_0>(W, base, xq, T, y, ldy, add);
     case T_Q5_1: return gemm_rows_avx2<T_Q5_1>(W, base, xq, T, y, ldy, add);
+    case T_Q2_K: return gemm_rows_avx2<T_Q2_K>(W, base, xq, T, y, ldy, add);
+    case T_Q3_K: return gemm_rows_avx2<T_Q3_K>(W, base, xq, T, y, ldy, add);
     default: return gemm_rows_scalar(W, base, xq, T, y, ldy, add);
   }
 }

@@ -1,6 +1,6 @@
 // Batched decode projection on MFMA (continuous batching, 1-16 activation rows):
 //   out[b][row] += sum_k W[row][k] * x[b][k]
-// W block-quantised (Q4_K / Q5_K / Q6_K / Q8_0, and Q4_0 / Q4_1 / Q5_0 / Q5_1 as Q4_K / Q5_K) read from a tile-ordered copy (tile16, below);
+// W block-quantised (Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / Q8_0, and Q4_0 / Q4_1 / Q5_0 / Q5_1 as Q4_K / Q5_K) read from a tile-ordered copy (tile16, below);
 // x f16 rows in a 4-group swizzled k order, staged per block in LDS - from xh (written by
 // bprep or by the attention kernel) or, for Q|K|V and gate/up, straight from the fp32
 // residual with the RMSNorm folded in.
@@ -91,6 +91,14 @@ struct Q5Raw {
   uint2 m;
 };
 template <> struct BRaw<T_Q5_K> { using type = Q5Raw; };
+// Q2_K / Q3_K: one 16-byte record per lane and chunk holds everything (tile16 layout below) -
+// two dwords of 2-bit fields, then Q2_K's two (d*sc, -dmin*m) f16 pairs or Q3_K's dword of high
+// bits and its (d*sc_lo, d*sc_hi) f16 pair
+struct K23TRaw {
+  int4 v;
+};
+template <> struct BRaw<T_Q2_K> { using type = K23TRaw; };
+template <> struct BRaw<T_Q3_K> { using type = K23TRaw; };
 template <int T> using BRawT = typename BRaw<T>::type;
 
 // chunk c of one row (raw loads in WRaw) -> the four A fragments
@@ -162,7 +170,39 @@ __device__ __forceinline__ void dequant_frags(const BRawT<T>& w, int c, HFrag& F
       F.w[4 * i + 3] = deq_pair(bytes13(hi), bias, ahi, zero);
     }
     (void)j;
+  } else if constexpr (T == T_Q2_K || T == T_Q3_K) {
+    // field dword D[i >> 1] holds quant dword i of the low run at bit 2 (i & 1) of every byte and
+    // of the high run at bit 4 + 2 (i & 1): one shift and one mask each
+    const unsigned D[2] = {(unsigned)w.v.x, (unsigned)w.v.y};
+    const h2_t pa = as_h2((unsigned)w.v.z), pb = as_h2((unsigned)w.v.w);
+    h2_t alo, ahi, mlo, mhi, bias;
+    if constexpr (T == T_Q2_K) {  // (d*sc, -dmin*m) of the low run, of the high run
+      alo = h2_t{pa[0], pa[0]}; mlo = h2_t{pa[1], pa[1]};
+      ahi = h2_t{pb[0], pb[0]}; mhi = h2_t{pb[1], pb[1]};
+      bias = h2_t{(_Float16)1024.f, (_Float16)1024.f};
+    } else {                      // (d*sc_lo, d*sc_hi); 1024 + 4: (q - 4) exactly
+      alo = h2_t{pb[0], pb[0]}; ahi = h2_t{pb[1], pb[1]};
+      mlo = mhi = h2_t{(_Float16)0.f, (_Float16)0.f};
+      bias = h2_t{(_Float16)1028.f, (_Float16)1028.f};
+    }
+    const unsigned H = (unsigned)w.v.z;  // Q3_K: bit i of a byte = high bit of low-run dword i, bit 4 + i of the high run's
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      unsigned lo = (D[i >> 1] >> (2 * (i & 1))) & 0x03030303u;
+      unsigned hi = (D[i >> 1] >> (4 + 2 * (i & 1))) & 0x03030303u;
+      if constexpr (T == T_Q3_K) {  // the high bit lands on bit 2 of its byte (neighbouring bytes' bits fall outside the mask)
+        constexpr int kL[4] = {2, 1, 0, 0}, kR[4] = {0, 0, 0, 1};
+        lo |= ((H << kL[i]) >> kR[i]) & 0x04040404u;
+        hi |= (H >> (2 + i)) & 0x04040404u;
+      }
+      F.w[4 * i + 0] = deq_pair(bytes02(lo), bias, alo, mlo);
+      F.w[4 * i + 1] = deq_pair(bytes13(lo), bias, alo, mlo);
+      F.w[4 * i + 2] = deq_pair(bytes02(hi), bias, ahi, mhi);
+      F.w[4 * i + 3] = deq_pair(bytes13(hi), bias, ahi, mhi);
+    }
+    (void)j;
   } else {  // Q8_0: signed bytes, flipped to unsigned for the magic, one scale
+    static_assert(T == T_Q8_0, "dequant_frags: unsupported type");
     const float d = h2f(w.d & 0xFFFF);
     const h2_t a = {(_Float16)d, (_Float16)d};
     const h2_t zero = {(_Float16)0.f, (_Float16)0.f};
@@ -184,7 +224,7 @@ __device__ __forceinline__ void dequant_frags(const BRawT<T>& w, int c, HFrag& F
 template <int T>
 __device__ __forceinline__ void chunk_runs(int c, int& off_lo, int& off_hi) {
   const int sb = c >> 3, j = c & 7;
-  if constexpr (T == T_Q4_K || T == T_Q5_K) {
+  if constexpr (T == T_Q4_K || T == T_Q5_K || T == T_Q2_K || T == T_Q3_K) {
     off_lo = sb * 256 + 64 * (j >> 1) + 16 * (j & 1);
     off_hi = off_lo + 32;
   } else if constexpr (T == T_Q6_K) {
@@ -209,6 +249,15 @@ __device__ __forceinline__ void chunk_runs(int c, int& off_lo, int& off_hi) {
 //         (qx: the chunk's 2-bit high fields regrouped per lane - see dequant_frags)
 //   Q8_0: qs[h][a|b][l][16] | d[h][l][2]                                        4352 B
 //   Q4_0 / Q4_1: the Q4_K step, Q5_0 / Q5_1: the Q5_K step (re-expressed exactly, below)
+//   Q2_K: rec[h][l][16] = D0 | D1 | (d*sc, -dmin*m) f16 of the low run | of the high run   2048 B
+//   Q3_K: rec[h][l][16] = D0 | D1 | H | (d*sc_lo, d*sc_hi) f16                            2048 B
+//         (chunk j = 4h + kq has the x map of Q4_K: g = j >> 1, low run at 64g + 16 (j & 1) =
+//          sub-block 4g + (j & 1), high run 32 further = sub-block + 2. With ql[k] / qh[k] the
+//          2-bit fields of weight k of the low / high run: byte b of D0 = ql[b] | ql[4+b] << 2 |
+//          qh[b] << 4 | qh[4+b] << 6, of D1 the same for weights 8+b, 12+b; bit i of byte b of H
+//          = third bit of low-run weight 4i + b, bit 4 + i that of the high run's. One 16-byte
+//          load per lane and chunk carries the quants AND their pre-decoded scales: both steps
+//          are 2 x 1 KB, each read by one load instruction.)
 // Rows past the matrix are zero.
 //
 // The legacy 32-weight blocks have no MFMA decode of their own. Two neighbouring blocks A, B
@@ -223,7 +272,8 @@ __host__ __device__ constexpr int t16_kernel_type(int t) {
 }
 __host__ __device__ constexpr int t16_step_bytes(int t) {
   const int k = t16_kernel_type(t);
-  return k == T_Q4_K ? 2560 : k == T_Q5_K ? 3072 : k == T_Q6_K ? 3584 : k == T_Q8_0 ? 4352 : 0;
+  return k == T_Q2_K ? 2048 : k == T_Q3_K ? 2048 : k == T_Q4_K ? 2560 : k == T_Q5_K ? 3072 : k == T_Q6_K ? 3584
+         : k == T_Q8_0 ? 4352 : 0;
 }
 
 int t16_format(int type) { return t16_kernel_type(type); }
@@ -397,6 +447,67 @@ __global__ __launch_bounds__(64) void t16_repack_legacy_kernel(QMat w, uint8_t* 
   }
 }
 
+// Q2_K / Q3_K -> their 16-byte-record steps (see the layout comment above); every lane writes
+// the records of its own two chunks
+template <int T>
+__global__ __launch_bounds__(64) void t16_repack_k23_kernel(QMat w, uint8_t* dst, int swiglu) {
+  static_assert(is_k23_v<T>, "Q2_K / Q3_K only");
+  const int s = blockIdx.x, t = blockIdx.y, steps = gridDim.x;
+  const int l = threadIdx.x, r16 = l & 15, kq = l >> 4;
+  int row = t * 16 + r16;
+  bool ok = row < w.rows;
+  if (swiglu) {  // as t16_repack_kernel
+    const int f = 8 * t + (r16 & 7);
+    row = 64 * (f >> 5) + (r16 >= 8 ? 32 : 0) + (f & 31);
+    ok = f < w.rows / 2;
+  }
+  const size_t r = ok ? (size_t)row : 0;
+  uint8_t* blk = dst + ((size_t)t * steps + s) * t16_step_bytes(T);
+  const Planes& P = w.P;
+  const uint8_t* p0 = w.base + P.p0 + r * P.s0 + 64 * s;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int j = 4 * h + kq, g = j >> 1, hh = j & 1, sh = 4 * (g & 1), sub = 4 * g + hh;
+    const uint4 q = *reinterpret_cast<const uint4*>(p0 + 32 * (g >> 1) + 16 * hh);
+    const unsigned S[4] = {q.x, q.y, q.z, q.w};
+    unsigned L[4], Hh[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      L[i] = (S[i] >> sh) & 0x03030303u;
+      Hh[i] = (S[i] >> (sh + 2)) & 0x03030303u;
+    }
+    uint4 rec;
+    rec.x = L[0] | (L[1] << 2) | (Hh[0] << 4) | (Hh[1] << 6);
+    rec.y = L[2] | (L[3] << 2) | (Hh[2] << 4) | (Hh[3] << 6);
+    if constexpr (T == T_Q2_K) {
+      const uint8_t* sc = w.base + P.p1 + r * P.s1 + 16 * s;
+      const unsigned dm = *reinterpret_cast<const unsigned*>(w.base + P.p2 + r * P.s2 + 4 * s);
+      const float d = h2f(dm & 0xFFFF), dmin = h2f(dm >> 16);
+      // f32 products, one rounding to f16 (as Q4_K's pre-decoded pairs)
+      const h2_t plo = {(_Float16)(d * (float)(sc[sub] & 0xF)), (_Float16)(-dmin * (float)(sc[sub] >> 4))};
+      const h2_t phi = {(_Float16)(d * (float)(sc[sub + 2] & 0xF)), (_Float16)(-dmin * (float)(sc[sub + 2] >> 4))};
+      rec.z = as_u(plo);
+      rec.w = as_u(phi);
+    } else {
+      const uint4 hm = *reinterpret_cast<const uint4*>(w.base + P.p1 + r * P.s1 + 32 * s + 16 * hh);
+      const unsigned M[4] = {hm.x, hm.y, hm.z, hm.w};
+      unsigned H = 0u;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {  // hmask bit 4n + 2e = 2g: the low run's third bit; 2g + 1: the high run's
+        H |= ((M[i] >> (2 * g)) & 0x01010101u) << i;
+        H |= ((M[i] >> (2 * g + 1)) & 0x01010101u) << (4 + i);
+      }
+      const unsigned* sp = reinterpret_cast<const unsigned*>(w.base + P.p2 + r * P.s2 + 12 * s);
+      const float d = h2f(*reinterpret_cast<const unsigned short*>(w.base + P.p3 + r * P.s3 + 2 * s));
+      const h2_t pr = {(_Float16)(d * (float)q3k_sc(sp[0], sp[1], sp[2], sub)),
+                       (_Float16)(d * (float)q3k_sc(sp[0], sp[1], sp[2], sub + 2))};
+      rec.z = H;
+      rec.w = as_u(pr);
+    }
+    *reinterpret_cast<uint4*>(blk + h * 1024 + l * 16) = ok ? rec : make_uint4(0, 0, 0, 0);
+  }
+}
+
 void t16_repack(const QMat& w, uint8_t* dst, hipStream_t st, bool swiglu) {
   if (!bmm_supported(w.type, w.K)) throw std::runtime_error("t16_repack: unsupported type / K");
   if (swiglu && w.rows % 64) throw std::runtime_error("t16_repack: SwiGLU copy needs 32-row gate / up groups");
@@ -411,6 +522,8 @@ void t16_repack(const QMat& w, uint8_t* dst, hipStream_t st, bool swiglu) {
     case T_Q4_1: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q4_1>, grid, dim3(64), 0, st, w, dst, sw); break;
     case T_Q5_0: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q5_0>, grid, dim3(64), 0, st, w, dst, sw); break;
     case T_Q5_1: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q5_1>, grid, dim3(64), 0, st, w, dst, sw); break;
+    case T_Q2_K: hipLaunchKernelGGL(t16_repack_k23_kernel<T_Q2_K>, grid, dim3(64), 0, st, w, dst, sw); break;
+    case T_Q3_K: hipLaunchKernelGGL(t16_repack_k23_kernel<T_Q3_K>, grid, dim3(64), 0, st, w, dst, sw); break;
     default: throw std::runtime_error("t16_repack: unsupported type");
   }
 }
@@ -437,7 +550,10 @@ __device__ __forceinline__ void tload(BRawT<T>& w, const uint8_t* blk, int h, in
     w.l = ld_q16<T, NT>(blk + h * 1024 + l * 16);
     w.x = *reinterpret_cast<const uint2*>(blk + 2048 + h * 512 + l * 8);
     w.s = *reinterpret_cast<const unsigned*>(blk + 3072 + r16 * 32 + (4 * h + kq) * 4);
+  } else if constexpr (T == T_Q2_K || T == T_Q3_K) {
+    w.v = ld_q16<T, NT>(blk + h * 1024 + l * 16);
   } else {
+    static_assert(T == T_Q8_0, "tload: unsupported type");
     w.a = ld_q16<T, NT>(blk + h * 2048 + l * 16);
     w.b = ld_q16<T, NT>(blk + h * 2048 + 1024 + l * 16);
     w.d = *reinterpret_cast<const unsigned short*>(blk + 4096 + h * 128 + l * 2);
@@ -475,7 +591,10 @@ __device__ __forceinline__ void tload_rs(BRawT<T>& w, __amdgpu_buffer_rsrc_t rs,
     w.l = b128(l * 16, h * 1024);
     w.x = b64(l * 8, 2048 + h * 512);
     w.s = __builtin_amdgcn_raw_buffer_load_b32(rs, r16 * 32 + kq * 4, so + 3072 + 16 * h, 0);
+  } else if constexpr (T == T_Q2_K || T == T_Q3_K) {
+    w.v = b128(l * 16, h * 1024);
   } else {
+    static_assert(T == T_Q8_0, "tload_rs: unsupported type");
     w.a = b128(l * 16, h * 2048);
     w.b = b128(l * 16, h * 2048 + 1024);
     w.d = __builtin_amdgcn_raw_buffer_load_b16(rs, l * 2, so + 4096 + h * 128, 0);
@@ -486,6 +605,7 @@ template <int T>
 __device__ __forceinline__ int raw_word(const BRawT<T>& w) {
   if constexpr (T == T_Q4_K || T == T_Q5_K) return w.q.x;
   else if constexpr (T == T_Q6_K) return w.l.x;
+  else if constexpr (T == T_Q2_K || T == T_Q3_K) return w.v.x;
   else return w.a.x;
 }
 
@@ -1794,7 +1914,7 @@ bool bmm_norm_fits(int K, int B) { return bmm_qkv_fits(K, B) && K == 4096 && B <
 
 bool bmm_supported(int type, int K) {
   const int k = t16_kernel_type(type);  // the legacy 32-block types run as Q4_K / Q5_K
-  if (k != T_Q4_K && k != T_Q5_K && k != T_Q6_K && k != T_Q8_0) return false;
+  if (k != T_Q4_K && k != T_Q5_K && k != T_Q6_K && k != T_Q8_0 && k != T_Q2_K && k != T_Q3_K) return false;
   return K % 256 == 0;  // 256 k per step
 }
 
@@ -2045,6 +2165,8 @@ void bmm(const BmmArgs& a0, hipStream_t s) {
     else if (a.w.type == T_Q5_K) launch_qkv_sk<T_Q5_K, 0>(a, s);
     else if (a.w.type == T_Q6_K) launch_qkv_sk<T_Q6_K, 0>(a, s);
     else if (a.w.type == T_Q8_0) launch_qkv_sk<T_Q8_0, 0>(a, s);
+    else if (a.w.type == T_Q2_K) launch_qkv_sk<T_Q2_K, 0>(a, s);
+    else if (a.w.type == T_Q3_K) launch_qkv_sk<T_Q3_K, 0>(a, s);
     else throw std::runtime_error("bmm: unsupported weight type");
     return;
   }
@@ -2053,6 +2175,8 @@ void bmm(const BmmArgs& a0, hipStream_t s) {
     case T_Q5_K: launch_bmm<T_Q5_K>(a, s); break;
     case T_Q6_K: launch_bmm<T_Q6_K>(a, s); break;
     case T_Q8_0: launch_bmm<T_Q8_0>(a, s); break;
+    case T_Q2_K: launch_bmm<T_Q2_K>(a, s); break;
+    case T_Q3_K: launch_bmm<T_Q3_K>(a, s); break;
     default: throw std::runtime_error("bmm: unsupported weight type");
   }
 }
@@ -2486,6 +2610,8 @@ void gemm_t16(const GemmT16Args& a, int epi, hipStream_t s) {
     case T_Q5_K: gemm_t16_epi<T_Q5_K>(a, epi, s); break;
     case T_Q6_K: gemm_t16_epi<T_Q6_K>(a, epi, s); break;
     case T_Q8_0: gemm_t16_epi<T_Q8_0>(a, epi, s); break;
+    case T_Q2_K: gemm_t16_epi<T_Q2_K>(a, epi, s); break;
+    case T_Q3_K: gemm_t16_epi<T_Q3_K>(a, epi, s); break;
     default: throw std::runtime_error("gemm_t16: unsupported weight type");
   }
 }

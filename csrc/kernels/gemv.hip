@@ -403,6 +403,12 @@ static GemvCfg pick_cfg(int qt, int rows, int nchunks, int min_nr) {
   // measured on MI355X with weights streamed from HBM (tools/gemv_sweep.sh):
   //   K > 4096 (FFN down)         : one row per wave, 4 passes (Q6_K: 2) in flight
   //   >= 16384 rows (gate/up, head): 4 rows per wave, 1 pass
+  if (qt == T_Q3_K) {
+    // a Q3_K chunk holds 12 raw dwords (quants, hmask, packed scales): only NR * U <= 2 stays
+    // under 128 VGPRs (88-109; (4, 1) and (2, 2) spill to scratch in the 1024-thread blocks)
+    const int nr = (min_nr >= 2 || rows / 2 >= 2048) ? 2 : 1;
+    return {nr, nr == 2 ? 1 : std::min(2, std::max(1, (nchunks + 63) / 64))};
+  }
   if (qt != T_F32 && qt != T_F16) {
     if (nchunks > 128) {  // long rows run on 1024-thread blocks: NR * U <= 4 (128 VGPRs)
       const int nr = std::max(1, min_nr);
@@ -556,7 +562,9 @@ static void launch_gemv_splitk(const GemvArgs& a, hipStream_t s) {
 
 template <int QT, int EPI>
 static void launch_gemv(const GemvArgs& a, hipStream_t s) {
-  if constexpr (EPI == EPI_ADD && (QT == T_Q4_K || QT == T_Q5_K || QT == T_Q6_K || QT == T_Q8_0 || is_legacy_v<QT>)) {
+  if constexpr (EPI == EPI_ADD && (QT == T_Q4_K || QT == T_Q5_K || QT == T_Q6_K || QT == T_Q8_0 || is_legacy_v<QT> || is_k23_v<QT>)) {
+    // (Q3_K too: its 4-row items spill in the 1024-thread form, yet one row per wave without the
+    // K split measured slower - llama3-8b-q2_k 2.09 against 1.90 ms per token)
     if (!a.dbg_clk && a.w.K >= 4096 && !a.debug) return launch_gemv_splitk<QT>(a, s);
   }
   if (a.dbg_clk) {
@@ -586,6 +594,8 @@ void gemv_legacy(const GemvArgs& a, int epi, hipStream_t s) {
     case T_Q4_1: gemv_t<T_Q4_1>(a, epi, s); break;
     case T_Q5_0: gemv_t<T_Q5_0>(a, epi, s); break;
     case T_Q5_1: gemv_t<T_Q5_1>(a, epi, s); break;
+    case T_Q2_K: gemv_t<T_Q2_K>(a, epi, s); break;
+    case T_Q3_K: gemv_t<T_Q3_K>(a, epi, s); break;
     default: throw std::runtime_error("gemv: unsupported weight type");
   }
 }
@@ -601,7 +611,7 @@ void gemv(const GemvArgs& a, int epi, hipStream_t s) {
     case T_Q5_K: gemv_t<T_Q5_K>(a, epi, s); break;
     case T_Q6_K: gemv_t<T_Q6_K>(a, epi, s); break;
     case T_Q8_0: gemv_t<T_Q8_0>(a, epi, s); break;
-    case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: gemv_legacy(a, epi, s); break;
+    case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: gemv_legacy(a, epi, s); break;
     case T_F16: gemv_t<T_F16>(a, epi, s); break;
     case T_F32: gemv_t<T_F32>(a, epi, s); break;
     default: throw std::runtime_error("gemv: unsupported weight type");
@@ -794,6 +804,8 @@ void gemv_qkv1_legacy(const QkvLaunch& L, int type, int rows, hipStream_t s) {
     case T_Q4_1: launch_qkv1<T_Q4_1>(L, rows, s); break;
     case T_Q5_0: launch_qkv1<T_Q5_0>(L, rows, s); break;
     case T_Q5_1: launch_qkv1<T_Q5_1>(L, rows, s); break;
+    case T_Q2_K: launch_qkv1<T_Q2_K>(L, rows, s); break;
+    case T_Q3_K: launch_qkv1<T_Q3_K>(L, rows, s); break;
     default: throw std::runtime_error("gemv_qkv: unsupported type");
   }
 }
@@ -847,7 +859,8 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
       case T_Q5_K: launch_qkv1<T_Q5_K>(L, rows_of(0, 3), s); return;
       case T_Q6_K: launch_qkv1<T_Q6_K>(L, rows_of(0, 3), s); return;
       case T_Q8_0: launch_qkv1<T_Q8_0>(L, rows_of(0, 3), s); return;
-      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: gemv_qkv1_legacy(L, run_type[0], rows_of(0, 3), s); return;
+      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K:
+        gemv_qkv1_legacy(L, run_type[0], rows_of(0, 3), s); return;
       case T_F16: launch_qkv1<T_F16>(L, rows_of(0, 3), s); return;
       case T_F32: launch_qkv1<T_F32>(L, rows_of(0, 3), s); return;
       default: throw std::runtime_error("gemv_qkv: unsupported type");
@@ -873,7 +886,8 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
       case T_Q5_K: launch_qkv1<T_Q5_K>(Li, m[i]->rows, s); break;
       case T_Q6_K: launch_qkv1<T_Q6_K>(Li, m[i]->rows, s); break;
       case T_Q8_0: launch_qkv1<T_Q8_0>(Li, m[i]->rows, s); break;
-      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: gemv_qkv1_legacy(Li, m[i]->type, m[i]->rows, s); break;
+      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K:
+        gemv_qkv1_legacy(Li, m[i]->type, m[i]->rows, s); break;
       case T_F16: launch_qkv1<T_F16>(Li, m[i]->rows, s); break;
       case T_F32: launch_qkv1<T_F32>(Li, m[i]->rows, s); break;
       default: throw std::runtime_error("gemv_qkv: unsupported type");

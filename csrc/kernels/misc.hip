@@ -245,6 +245,15 @@ __global__ void fix_scales_kernel(uint8_t* base, int type, size_t nblocks, Plane
         reinterpret_cast<__half*>(sp)[2 * b] = d;
         reinterpret_cast<__half*>(sp)[2 * b + 1] = __float2half(-__half2float(d) * nmax * 0.5f);
       }
+    } else if (type == T_Q2_K) {
+      // sc, m uniform in [0, 15], q in [0, 3], dmin = 1.5 d centres the weights (random_blocks)
+      const float var = (15.f * 31.f / 6.f) * 3.5f - (7.5f * 1.5f) * (7.5f * 1.5f) + 2.25f * (16.f * 16.f - 1.f) / 12.f;
+      const float d = std / sqrtf(var) * jit;
+      reinterpret_cast<__half*>(base + P.p2)[2 * b] = __float2half(d);
+      reinterpret_cast<__half*>(base + P.p2)[2 * b + 1] = __float2half(d * 1.5f);
+    } else if (type == T_Q3_K) {
+      // sc - 32 uniform in [-32, 31] (mean square 341.5), q - 4 in [-4, 3] (mean square 5.5)
+      reinterpret_cast<__half*>(base + P.p3)[b] = __float2half(std / sqrtf(341.5f * 5.5f) * jit);
     } else if (type == T_F32) {
       // uniform in [-sqrt(3) std, sqrt(3) std]
       const float u = u01(mix64(seed ^ (b * 0x9E37ull)));
@@ -262,7 +271,7 @@ void fill_random_planar(uint8_t* base, int type, size_t rows, size_t K, float st
   const Planes P = planes_of(type, rows, K);
   hipLaunchKernelGGL(fill_bytes_kernel, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t*>(base), bytes / 4, seed);
   size_t nblocks;
-  if (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K) nblocks = rows * (K / 256);
+  if (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q2_K || type == T_Q3_K) nblocks = rows * (K / 256);
   else if (type == T_Q8_0 || type == T_Q4_0 || type == T_Q4_1 || type == T_Q5_0 || type == T_Q5_1)
     nblocks = rows * (K / 32);
   else if (type == T_F16 || type == T_BF16 || type == T_F32) nblocks = rows * K;

@@ -14,6 +14,14 @@
 //   Q8_0/F16/F32: 32 contiguous @ 32c
 //   Q4_0/Q4_1/Q5_0/Q5_1: chunk c = block c, 32 contiguous @ 32c like Q8_0: the low nibbles
 //                        are weights 32c .. 32c+15, the high nibbles 32c+16 .. 32c+31
+//   Q2_K/Q3_K : the x map of Q4_K: j=c&7, g=j>>1, h=j&1 : lo 16 @ sb*256+64g+16h (sub-block 4g+h),
+//               hi 16 @ +32 (sub-block 4g+h+2). A 16-byte quant load of these formats carries 64
+//               weights - the 16-runs at +0, +32, +64, +96 of half n = g>>1, in bit pairs 0..3 of
+//               bytes 32n+16h .. +15 - so chunks g = 2n and 2n+1 of one h read the SAME 16 bytes
+//               and take bit pairs (0, 1) and (2, 3): one shift by 4(g&1) / 4(g&1)+2 and a
+//               0x03030303 mask per dword. The two lanes' loads fall in one 64-byte line of one
+//               load instruction, so HBM streams every byte once; Q3_K's hmask bytes 16h .. +15
+//               (bit 4n+2(g&1) / +1) are shared by four chunks the same way.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -103,7 +111,7 @@ template <int T>
 __device__ __forceinline__ void load_x(XChunk& X, const int8_t* xq, const float* xd, int c) {
   const int sb = c >> 3, j = c & 7;
   int off_lo, off_hi, blo, bhi;
-  if constexpr (T == T_Q4_K || T == T_Q5_K) {
+  if constexpr (T == T_Q4_K || T == T_Q5_K || T == T_Q2_K || T == T_Q3_K) {
     const int g = j >> 1, h = j & 1;
     off_lo = sb * 256 + 64 * g + 16 * h;
     off_hi = off_lo + 32;
@@ -213,6 +221,138 @@ __device__ __forceinline__ void legacy_decode(const LegacyRaw& w, float* out) {
   }
 }
 
+// ---- 2- and 3-bit K-quants (Q2_K / Q3_K): 16 sub-blocks of 16 weights, so each 16-run of a chunk
+// has its own scale. Q2_K: w = d (sc & 15) q - dmin (sc >> 4), q in 0..3. Q3_K: w = d (sc6 - 32)
+// (q - 4), q = 2 low bits | hmask bit << 2. The min and the -4 go through the x sums.
+template <int T> inline constexpr bool is_k23_v = (T == T_Q2_K || T == T_Q3_K);
+
+// Q3_K's 6-bit scale of sub-block s, minus 32, from the 12 packed bytes as three dwords
+__device__ __forceinline__ int q3k_sc(unsigned s0, unsigned s1, unsigned s2, int s) {
+  const unsigned v = (s & 4) ? s1 : s0;
+  const unsigned low = (v >> (8 * (s & 3) + 4 * (s >> 3))) & 0xFu;
+  const unsigned top = (s2 >> (8 * (s & 3) + 2 * (s >> 2))) & 3u;
+  return (int)(low | (top << 4)) - 32;
+}
+
+// one chunk's raw fields (GEMV)
+struct K23Raw {
+  int4 q;               // qs bytes 32n + 16h .. +15 of the block
+  int4 h;               // Q3_K: hmask bytes 16h .. +15
+  unsigned s0, s1, s2;  // Q2_K: the scale bytes of the low / high run (s2 unused); Q3_K: the 12 packed bytes
+  unsigned d;           // Q2_K: d | dmin << 16; Q3_K: d
+};
+
+template <int T, bool NT>
+__device__ __forceinline__ void k23_load(K23Raw& w, const uint8_t* p0, const uint8_t* p1, const uint8_t* p2,
+                                         const uint8_t* p3, int c) {
+  const int sb = c >> 3, j = c & 7, g = j >> 1, hh = j & 1;
+  const uint8_t* qp = p0 + 64 * sb + 32 * (g >> 1) + 16 * hh;
+  if constexpr (NT) w.q = ld_nt16(qp);
+  else w.q = *reinterpret_cast<const int4*>(qp);
+  if constexpr (T == T_Q2_K) {
+    const uint8_t* sp = p1 + 16 * sb + 4 * g + hh;
+    w.s0 = sp[0];
+    w.s1 = sp[2];
+    w.d = *reinterpret_cast<const unsigned*>(p2 + 4 * sb);
+  } else {
+    w.h = *reinterpret_cast<const int4*>(p1 + 32 * sb + 16 * hh);
+    const unsigned* sp = reinterpret_cast<const unsigned*>(p2 + 12 * sb);
+    w.s0 = sp[0];
+    w.s1 = sp[1];
+    w.s2 = sp[2];
+    w.d = *reinterpret_cast<const unsigned short*>(p3 + 2 * sb);
+  }
+}
+
+template <int T>
+__device__ __forceinline__ float k23_dot(const K23Raw& w, const XChunk& X, int c) {
+  const int j = c & 7, g = j >> 1, hh = j & 1, sh = 4 * (g & 1);
+  const int qv[4] = {w.q.x, w.q.y, w.q.z, w.q.w};
+  int dl = 0, dh = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    int lo = (qv[i] >> sh) & 0x03030303;
+    int hi = (qv[i] >> (sh + 2)) & 0x03030303;
+    if constexpr (T == T_Q3_K) {
+      const int hv = (i == 0 ? w.h.x : i == 1 ? w.h.y : i == 2 ? w.h.z : w.h.w);
+      const int b = 2 * g;  // bit 4n + 2e of the hmask byte = bit 2g
+      lo |= ((hv >> b) & 0x01010101) << 2;
+      hi |= ((hv >> (b + 1)) & 0x01010101) << 2;
+    }
+    dl = dot4(lo, X.lo[i], dl);
+    dh = dot4(hi, X.hi[i], dh);
+  }
+  if constexpr (T == T_Q2_K) {
+    const float d = h2f(w.d & 0xFFFF), dmin = h2f(w.d >> 16);
+    return d * ((float)(w.s0 & 0xF) * X.dlo * (float)dl + (float)(w.s1 & 0xF) * X.dhi * (float)dh) -
+           dmin * ((float)(w.s0 >> 4) * X.slo + (float)(w.s1 >> 4) * X.shi);
+  } else {
+    const int s = 4 * g + hh;
+    const float sc_lo = (float)q3k_sc(w.s0, w.s1, w.s2, s), sc_hi = (float)q3k_sc(w.s0, w.s1, w.s2, s + 2);
+    // sum((q - 4) x) = dot - 4 sum(x)
+    return h2f(w.d & 0xFFFF) * (sc_lo * (X.dlo * (float)dl - 4.f * X.slo) + sc_hi * (X.dhi * (float)dh - 4.f * X.shi));
+  }
+}
+
+// 32 contiguous weights (run r = q & 7 of a block: half n = r >> 2, bit pair r & 3, sub-blocks 2r, 2r + 1)
+struct K23Dq {
+  int4 a, b;            // qs bytes 32n .. +31
+  int4 ha, hb;          // Q3_K: hmask[32]
+  unsigned s0, s1, s2;  // Q2_K: s0 = the two scale bytes of sub-blocks 2r, 2r + 1; Q3_K: the 12 packed bytes
+  unsigned d;
+};
+
+template <int T>
+__device__ __forceinline__ void k23_dq_load(K23Dq& w, const uint8_t* __restrict__ base, const Planes& P, size_t row,
+                                            int q) {
+  const int sb = q >> 3, r = q & 7;
+  const int4* qs = reinterpret_cast<const int4*>(base + P.p0 + row * P.s0 + 64 * sb + 32 * (r >> 2));
+  w.a = qs[0];
+  w.b = qs[1];
+  if constexpr (T == T_Q2_K) {
+    w.s0 = *reinterpret_cast<const unsigned short*>(base + P.p1 + row * P.s1 + 16 * sb + 2 * r);
+    w.d = *reinterpret_cast<const unsigned*>(base + P.p2 + row * P.s2 + 4 * sb);
+  } else {
+    const int4* hm = reinterpret_cast<const int4*>(base + P.p1 + row * P.s1 + 32 * sb);
+    w.ha = hm[0];
+    w.hb = hm[1];
+    const unsigned* sp = reinterpret_cast<const unsigned*>(base + P.p2 + row * P.s2 + 12 * sb);
+    w.s0 = sp[0];
+    w.s1 = sp[1];
+    w.s2 = sp[2];
+    w.d = *reinterpret_cast<const unsigned short*>(base + P.p3 + row * P.s3 + 2 * sb);
+  }
+}
+
+template <int T>
+__device__ __forceinline__ void k23_dq_decode(const K23Dq& w, int q, float* out) {
+  const int r = q & 7, sh = 2 * (r & 3);
+  const int qv[8] = {w.a.x, w.a.y, w.a.z, w.a.w, w.b.x, w.b.y, w.b.z, w.b.w};
+  float a0, a1, m0, m1;
+  if constexpr (T == T_Q2_K) {
+    const float d = h2f(w.d & 0xFFFF), dmin = h2f(w.d >> 16);
+    a0 = d * (float)(w.s0 & 0xF); m0 = dmin * (float)((w.s0 >> 4) & 0xF);
+    a1 = d * (float)((w.s0 >> 8) & 0xF); m1 = dmin * (float)(w.s0 >> 12);
+  } else {
+    const float d = h2f(w.d & 0xFFFF);
+    a0 = d * (float)q3k_sc(w.s0, w.s1, w.s2, 2 * r);
+    a1 = d * (float)q3k_sc(w.s0, w.s1, w.s2, 2 * r + 1);
+    m0 = m1 = 0.f;
+  }
+  const int hv[8] = {w.ha.x, w.ha.y, w.ha.z, w.ha.w, w.hb.x, w.hb.y, w.hb.z, w.hb.w};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    int v = (qv[i] >> sh) & 0x03030303;
+    if constexpr (T == T_Q3_K) v |= ((hv[i] >> r) & 0x01010101) << 2;  // bit 4n + j of the byte = bit r
+#pragma unroll
+    for (int b8 = 0; b8 < 4; ++b8) {
+      const int qq = (v >> (8 * b8)) & 0xFF;
+      if constexpr (T == T_Q2_K) out[4 * i + b8] = (i < 4 ? a0 : a1) * (float)qq - (i < 4 ? m0 : m1);
+      else out[4 * i + b8] = (i < 4 ? a0 : a1) * (float)(qq - 4);
+    }
+  }
+}
+
 // 6-bit (sc, m) pair for sub-blocks 2g and 2g+1 from the 12 packed scale bytes (ggml get_scale_min_k4).
 __device__ __forceinline__ void scale_min_pair(int g, unsigned y, unsigned z, unsigned w, float& sc_lo, float& m_lo,
                                                float& sc_hi, float& m_hi) {
@@ -308,7 +448,13 @@ __device__ __forceinline__ float chunk_dot(const uint8_t* __restrict__ base, con
     LegacyRaw w;
     legacy_load<T, true>(w, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, base + P.p2 + row * P.s2, c);
     return legacy_dot<T>(w, X);
+  } else if constexpr (is_k23_v<T>) {
+    K23Raw w;
+    k23_load<T, true>(w, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, base + P.p2 + row * P.s2,
+                      base + P.p3 + row * P.s3, c);
+    return k23_dot<T>(w, X, c);
   } else {  // F32 / F16 weights: dequantised x
+    static_assert(T == T_F32 || T == T_F16, "chunk_dot: unsupported type");
     float s = 0.f;
     const int xv[8] = {X.lo[0], X.lo[1], X.lo[2], X.lo[3], X.hi[0], X.hi[1], X.hi[2], X.hi[3]};
     if constexpr (T == T_F32) {
@@ -347,6 +493,8 @@ template <> struct WRaw<T_Q4_0> : LegacyRaw {};
 template <> struct WRaw<T_Q4_1> : LegacyRaw {};
 template <> struct WRaw<T_Q5_0> : LegacyRaw {};
 template <> struct WRaw<T_Q5_1> : LegacyRaw {};
+template <> struct WRaw<T_Q2_K> : K23Raw {};
+template <> struct WRaw<T_Q3_K> : K23Raw {};
 template <> struct WRaw<T_F16> { uint4 w[4]; };
 template <> struct WRaw<T_F32> { float4 w[8]; };
 
@@ -391,6 +539,8 @@ __device__ __forceinline__ void wload(WRaw<T>& w, const RowPtr& R, int c) {
     w.d = *reinterpret_cast<const unsigned short*>(R.p1 + 2 * c);
   } else if constexpr (is_legacy_v<T>) {
     legacy_load<T, true>(w, R.p0, R.p1, R.p2, c);
+  } else if constexpr (is_k23_v<T>) {
+    k23_load<T, true>(w, R.p0, R.p1, R.p2, R.p3, c);
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) w.w[i] = reinterpret_cast<const uint4*>(R.p0 + 64 * c)[i];
@@ -452,7 +602,10 @@ __device__ __forceinline__ float wdot(const WRaw<T>& w, const XChunk& X, int c) 
     return h2f(w.d & 0xFFFF) * X.dlo * (float)acc;
   } else if constexpr (is_legacy_v<T>) {
     return legacy_dot<T>(w, X);
+  } else if constexpr (is_k23_v<T>) {
+    return k23_dot<T>(w, X, c);
   } else {
+    static_assert(T == T_F32 || T == T_F16, "wdot: unsupported type");
     const int xv[8] = {X.lo[0], X.lo[1], X.lo[2], X.lo[3], X.hi[0], X.hi[1], X.hi[2], X.hi[3]};
     float s = 0.f;
 #pragma unroll
@@ -540,6 +693,10 @@ __device__ __forceinline__ void dequant32(const uint8_t* __restrict__ base, cons
     LegacyRaw w;
     legacy_load<T, false>(w, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, base + P.p2 + row * P.s2, q);
     legacy_decode<T>(w, out);
+  } else if constexpr (is_k23_v<T>) {
+    K23Dq w;
+    k23_dq_load<T>(w, base, P, row, q);
+    k23_dq_decode<T>(w, q, out);
   } else if constexpr (T == T_F32) {
     const float4* wp = reinterpret_cast<const float4*>(base + row * P.s0 + 128 * q);
 #pragma unroll
@@ -571,6 +728,8 @@ template <> struct DqRaw<T_Q4_0> : LegacyRaw {};
 template <> struct DqRaw<T_Q4_1> : LegacyRaw {};
 template <> struct DqRaw<T_Q5_0> : LegacyRaw {};
 template <> struct DqRaw<T_Q5_1> : LegacyRaw {};
+template <> struct DqRaw<T_Q2_K> : K23Dq {};
+template <> struct DqRaw<T_Q3_K> : K23Dq {};
 template <> struct DqRaw<T_F16> { uint4 w[4]; };
 template <> struct DqRaw<T_F32> { float4 w[8]; };
 
@@ -605,6 +764,8 @@ __device__ __forceinline__ void dq_load(DqRaw<T>& r, const uint8_t* __restrict__
     r.d = *reinterpret_cast<const unsigned short*>(base + P.p1 + row * P.s1 + 2 * q);
   } else if constexpr (is_legacy_v<T>) {
     legacy_load<T, false>(r, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, base + P.p2 + row * P.s2, q);
+  } else if constexpr (is_k23_v<T>) {
+    k23_dq_load<T>(r, base, P, row, q);
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) r.w[i] = reinterpret_cast<const uint4*>(base + row * P.s0 + 64 * q)[i];
@@ -664,6 +825,8 @@ __device__ __forceinline__ void dq_decode(const DqRaw<T>& r, int q, float* out) 
       for (int b8 = 0; b8 < 4; ++b8) out[4 * i + b8] = d * (float)(signed char)((qv[i] >> (8 * b8)) & 0xFF);
   } else if constexpr (is_legacy_v<T>) {
     legacy_decode<T>(r, out);
+  } else if constexpr (is_k23_v<T>) {
+    k23_dq_decode<T>(r, q, out);
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -686,7 +849,7 @@ __device__ __forceinline__ void dq_decode(const DqRaw<T>& r, int q, float* out) 
 // outside the list runs nothing: host launchers check with dispatchable_type() and throw.
 LFK_HD bool dispatchable_type(int t) {
   return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0 || t == T_Q4_0 || t == T_Q4_1 || t == T_Q5_0 ||
-         t == T_Q5_1 || t == T_F16 || t == T_F32;
+         t == T_Q5_1 || t == T_Q2_K || t == T_Q3_K || t == T_F16 || t == T_F32;
 }
 #define LFK_DISPATCH_TYPE(t, ...)                          \
   switch (t) {                                             \
@@ -698,6 +861,8 @@ LFK_HD bool dispatchable_type(int t) {
     case T_Q4_1: { constexpr int QT = T_Q4_1; __VA_ARGS__; } break; \
     case T_Q5_0: { constexpr int QT = T_Q5_0; __VA_ARGS__; } break; \
     case T_Q5_1: { constexpr int QT = T_Q5_1; __VA_ARGS__; } break; \
+    case T_Q2_K: { constexpr int QT = T_Q2_K; __VA_ARGS__; } break; \
+    case T_Q3_K: { constexpr int QT = T_Q3_K; __VA_ARGS__; } break; \
     case T_F16: { constexpr int QT = T_F16; __VA_ARGS__; } break;   \
     case T_F32: { constexpr int QT = T_F32; __VA_ARGS__; } break;   \
     default: break;                                                 \

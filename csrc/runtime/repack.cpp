@@ -18,6 +18,7 @@ void repack_planar(int type, const uint8_t* src, size_t K_src, size_t r0, size_t
   switch (type) {
     case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_Q8_0: case T_F16: case T_BF16: case T_F32: break;
     case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: break;
+    case T_Q2_K: case T_Q3_K: break;
     default: throw std::runtime_error("repack: unsupported type");
   }
 #pragma omp parallel for schedule(static)
@@ -48,6 +49,23 @@ void repack_planar(int type, const uint8_t* src, size_t K_src, size_t r0, size_t
           std::memcpy(dst + P.p1 + dr * P.s1 + b * 64, blk + 128, 64);
           std::memcpy(dst + P.p2 + dr * P.s2 + b * 16, blk + 192, 16);
           std::memcpy(dst + P.p3 + dr * P.s3 + b * 2, blk + 208, 2);
+        }
+        break;
+      case T_Q2_K:
+        for (size_t b = 0; b < nb; ++b) {
+          const uint8_t* blk = srow + b * 84;
+          std::memcpy(dst + P.p1 + dr * P.s1 + b * 16, blk, 16);
+          std::memcpy(dst + P.p0 + dr * P.s0 + b * 64, blk + 16, 64);
+          std::memcpy(dst + P.p2 + dr * P.s2 + b * 4, blk + 80, 4);
+        }
+        break;
+      case T_Q3_K:
+        for (size_t b = 0; b < nb; ++b) {
+          const uint8_t* blk = srow + b * 110;
+          std::memcpy(dst + P.p1 + dr * P.s1 + b * 32, blk, 32);
+          std::memcpy(dst + P.p0 + dr * P.s0 + b * 64, blk + 32, 64);
+          std::memcpy(dst + P.p2 + dr * P.s2 + b * 12, blk + 96, 12);
+          std::memcpy(dst + P.p3 + dr * P.s3 + b * 2, blk + 108, 2);
         }
         break;
       case T_Q8_0:

@@ -55,6 +55,8 @@ GGML_BLOCK = {
     GGMLType.Q5_0: (32, 22),
     GGMLType.Q5_1: (32, 24),
     GGMLType.Q8_0: (32, 34),
+    GGMLType.Q2_K: (256, 84),
+    GGMLType.Q3_K: (256, 110),
     GGMLType.Q4_K: (256, 144),
     GGMLType.Q5_K: (256, 176),
     GGMLType.Q6_K: (256, 210),
@@ -70,6 +72,10 @@ FTYPE_MOSTLY_Q4_1 = 3
 FTYPE_MOSTLY_Q8_0 = 7
 FTYPE_MOSTLY_Q5_0 = 8
 FTYPE_MOSTLY_Q5_1 = 9
+FTYPE_MOSTLY_Q2_K = 10
+FTYPE_MOSTLY_Q3_K_S = 11
+FTYPE_MOSTLY_Q3_K_M = 12
+FTYPE_MOSTLY_Q3_K_L = 13
 FTYPE_MOSTLY_Q4_K_M = 15
 FTYPE_MOSTLY_Q5_K_M = 17
 FTYPE_MOSTLY_Q6_K = 18

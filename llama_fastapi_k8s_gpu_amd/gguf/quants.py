@@ -1,6 +1,6 @@
 """NumPy reference implementation of the ggml block formats used by Q4_K_M /
 Q8_0 and the legacy Q4_0 / Q4_1 / Q5_0 / Q5_1 GGUF files: Q4_K, Q5_K, Q6_K, Q8_0,
-Q4_0, Q4_1, Q5_0, Q5_1 (+ F16/BF16/F32).
+Q4_0, Q4_1, Q5_0, Q5_1, and the 2- and 3-bit K-quants Q2_K, Q3_K (+ F16/BF16/F32).
 
 This is the *reference* every native path is tested against (T1 in SURVEY
 §4.3): the C++ CPU backend, the GPU repack and the HIP kernels must reproduce
@@ -18,6 +18,13 @@ Block layouts:
                       w = d*sc_j*q - dmin*m_j ; 6-bit (sc,m) packed, get_scale_min_k4
   Q5_K 176 B / 256 w: d | dmin | scales[12] | qh[32] | qs[128]  (5th bit from qh)
   Q6_K 210 B / 256 w: ql[128] | qh[64] | scales int8[16] | d f16  w = d*sc*(q-32)
+  Q2_K  84 B / 256 w: scales[16] | qs[64] | d f16 | dmin f16
+                      weight i: n = i//128, j = (i%128)//32, l = i%32, sub-block s = i//16
+                      q = (qs[32n+l] >> 2j) & 3 ; w = d*(scales[s]&0xF)*q - dmin*(scales[s]>>4)
+  Q3_K 110 B / 256 w: hmask[32] | qs[64] | scales[12] | d f16
+                      q = ((qs[32n+l] >> 2j) & 3) + 4*((hmask[l] >> (4n+j)) & 1) - 4
+                      sc[s] = 6 bits: low nibble scales[s]&0xF (s<8) / scales[s-8]>>4,
+                      top two bits (scales[8+s%4] >> 2*(s//4)) & 3 ; w = d*(sc[s]-32)*q
 
 The quantisers are simple (min/max per sub-block, no iterative search) - they
 produce valid blocks with bounded error, which is all the synthetic-model and
@@ -97,6 +104,65 @@ def _legacy_fields(b: np.ndarray, t):
 def _legacy_offset(t) -> int:
     return 8 if t == GGMLType.Q4_0 else 16
 
+
+K23_TYPES = (GGMLType.Q2_K, GGMLType.Q3_K)
+
+
+def _unpack_q3k_scales(scales: np.ndarray) -> np.ndarray:
+    """scales: uint8 [nb, 12] -> the sixteen 6-bit scales, uint8 [nb, 16] (0..63, before the -32)."""
+    s = scales.astype(np.uint8)
+    low = np.concatenate([s[:, 0:8] & 0xF, s[:, 0:8] >> 4], axis=1)
+    idx = np.arange(16)
+    top = (s[:, 8 + idx % 4] >> (2 * (idx // 4)).astype(np.uint8)) & 3
+    return (low | (top << 4)).astype(np.uint8)
+
+
+def _pack_q3k_scales(sc: np.ndarray) -> np.ndarray:
+    """Inverse of _unpack_q3k_scales; sc uint8 [nb, 16] with values < 64."""
+    sc = sc.astype(np.uint8)
+    out = np.zeros((sc.shape[0], 12), np.uint8)
+    out[:, 0:8] = (sc[:, 0:8] & 0xF) | ((sc[:, 8:16] & 0xF) << 4)
+    for s in range(16):
+        out[:, 8 + s % 4] |= ((sc[:, s] >> 4) & 3) << (2 * (s // 4))
+    return out
+
+
+def _unpack_2bit(qs: np.ndarray) -> np.ndarray:
+    """qs uint8 [nb, 64] -> the 2-bit fields in weight order, uint8 [nb, 256]."""
+    out = np.empty((qs.shape[0], 256), np.uint8)
+    for n in range(2):
+        for j in range(4):
+            out[:, 128 * n + 32 * j:128 * n + 32 * j + 32] = (qs[:, 32 * n:32 * n + 32] >> (2 * j)) & 3
+    return out
+
+
+def _pack_2bit(q: np.ndarray) -> np.ndarray:
+    qs = np.zeros((q.shape[0], 64), np.uint8)
+    for n in range(2):
+        for j in range(4):
+            qs[:, 32 * n:32 * n + 32] |= (q[:, 128 * n + 32 * j:128 * n + 32 * j + 32] & 3).astype(np.uint8) << (2 * j)
+    return qs
+
+
+def _k23_fields(b: np.ndarray, t):
+    """Blocks uint8 [nb, bytes] of Q2_K / Q3_K -> (q int16 [nb, 256], sc int16 [nb, 16],
+    m int16 [nb, 16] or None, d f16 [nb], dmin f16 [nb] or None): w = d*sc[i//16]*q - dmin*m[i//16]."""
+    if t == GGMLType.Q2_K:
+        scales = b[:, 0:16]
+        q = _unpack_2bit(b[:, 16:80]).astype(np.int16)
+        d = b[:, 80:82].copy().view(np.float16)[:, 0]
+        dmin = b[:, 82:84].copy().view(np.float16)[:, 0]
+        return q, (scales & 0xF).astype(np.int16), (scales >> 4).astype(np.int16), d, dmin
+    hmask = b[:, 0:32]
+    q = _unpack_2bit(b[:, 32:96]).astype(np.int16)
+    for n in range(2):
+        for j in range(4):
+            q[:, 128 * n + 32 * j:128 * n + 32 * j + 32] += 4 * ((hmask >> (4 * n + j)) & 1).astype(np.int16)
+    q -= 4
+    sc = _unpack_q3k_scales(b[:, 96:108]).astype(np.int16) - 32
+    d = b[:, 108:110].copy().view(np.float16)[:, 0]
+    return q, sc, None, d, None
+
 # ------------------------------------------------------------- dequantise
 
 
@@ -106,9 +172,11 @@ def dequantize(data, ggml_type, n_elements: int | None = None, arith: str = "f32
     ``arith="f16"`` reproduces the batched decode projection's dequantisation bit for bit
     (kernels/bmm.hip on its tile16 copy): the per-sub-block scale d*sc and offset -dmin*m are
     rounded to f16 once, and every weight is ONE f16 rounding of q*scale + offset (a fused
-    v_pk_fma_f16). Returned as float32 (exact f16 values)."""
+    v_pk_fma_f16). Q2_K: scale f16(d*(scales[s]&0xF)), offset f16(-dmin*(scales[s]>>4)), products
+    taken in f32, q in 0..3. Q3_K: scale f16(d*(sc[s]-32)), no offset, q in -4..3 (the -4 is
+    removed exactly before the multiply). Returned as float32 (exact f16 values)."""
     t = GGMLType(ggml_type)
-    if arith == "f16" and t in (GGMLType.Q8_0, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K) + LEGACY_TYPES:
+    if arith == "f16" and t in (GGMLType.Q8_0, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K) + LEGACY_TYPES + K23_TYPES:
         return _dequantize_f16(data, t, n_elements)
     if t == GGMLType.F32:
         return np.frombuffer(bytes(data) if not isinstance(data, np.ndarray) else data.tobytes(),
@@ -131,6 +199,12 @@ def dequantize(data, ggml_type, n_elements: int | None = None, arith: str = "f32
             out = d * (q.astype(np.float32) - np.float32(_legacy_offset(t)))
         else:
             out = d * q.astype(np.float32) + m.astype(np.float32)[:, None]
+    elif t in K23_TYPES:
+        q, sc, m, d, dmin = _k23_fields(b, t)
+        a = np.repeat(d.astype(np.float32)[:, None] * sc.astype(np.float32), 16, axis=1)
+        out = a * q.astype(np.float32)
+        if m is not None:
+            out -= np.repeat(dmin.astype(np.float32)[:, None] * m.astype(np.float32), 16, axis=1)
     elif t in (GGMLType.Q4_K, GGMLType.Q5_K):
         d = b[:, 0:2].copy().view(np.float16).astype(np.float32)
         dmin = b[:, 2:4].copy().view(np.float16).astype(np.float32)
@@ -195,6 +269,13 @@ def _dequantize_f16(data, t, n_elements):
         a = d.astype(np.float64)
         off = h(-_legacy_offset(t) * a) if m is None else m.astype(np.float64)
         out = h(q.astype(np.float64) * a[:, None] + off[:, None])
+    elif t in K23_TYPES:
+        # the tile16 copy stores f16(d*sc) (f32 product) and, for Q2_K, f16(-dmin*m) per sub-block
+        q, sc, m, d, dmin = _k23_fields(b, t)
+        f32 = lambda v: np.asarray(v, np.float32)  # noqa: E731
+        a = np.repeat(h(f32(d)[:, None] * f32(sc)), 16, axis=1)
+        off = 0.0 if m is None else np.repeat(h(-f32(dmin)[:, None] * f32(m)), 16, axis=1)
+        out = h(q.astype(np.float64) * a + off)
     elif t in (GGMLType.Q4_K, GGMLType.Q5_K):
         d = b[:, 0:2].copy().view(np.float16).astype(np.float64)[:, 0]
         dmin = b[:, 2:4].copy().view(np.float16).astype(np.float64)[:, 0]
@@ -322,6 +403,44 @@ def quantize(x: np.ndarray, ggml_type) -> np.ndarray:
         for j in range(8):
             qh |= ((q[:, j] >> 4) & 1).astype(np.uint8) << j
         return np.concatenate([head, packed, qh, qs], axis=1).reshape(-1)
+    if t == GGMLType.Q2_K:
+        # per 16-weight sub-block min/max; 4-bit scale and min against the block's d / dmin
+        xb = x.reshape(-1, 16, 16)
+        mn = np.minimum(xb.min(axis=2), 0.0)
+        scale = (xb.max(axis=2) - mn) / 3.0
+        minv = -mn
+        d16 = _f16(scale.max(axis=1) / 15.0)
+        dm16 = _f16(minv.max(axis=1) / 15.0)
+        df, dmf = d16.astype(np.float32), dm16.astype(np.float32)
+        sc = np.clip(np.rint(np.where(df[:, None] > 0, scale / np.where(df > 0, df, 1)[:, None], 0)), 0, 15)
+        m = np.clip(np.rint(np.where(dmf[:, None] > 0, minv / np.where(dmf > 0, dmf, 1)[:, None], 0)), 0, 15)
+        eff_s = df[:, None] * sc
+        eff_m = dmf[:, None] * m
+        q = np.where(eff_s[:, :, None] > 0,
+                     np.rint((xb + eff_m[:, :, None]) / np.where(eff_s > 0, eff_s, 1)[:, :, None]), 0)
+        q = np.clip(q, 0, 3).astype(np.uint8).reshape(-1, 256)
+        scales = (sc.astype(np.uint8) | (m.astype(np.uint8) << 4))
+        return np.concatenate([scales, _pack_2bit(q), d16.reshape(-1, 1).view(np.uint8),
+                               dm16.reshape(-1, 1).view(np.uint8)], axis=1).reshape(-1)
+    if t == GGMLType.Q3_K:
+        # per 16-weight sub-block absmax (signed, as Q6_K: the extreme value maps to -4); 6-bit scales
+        xb = x.reshape(-1, 16, 16)
+        vmax = np.take_along_axis(xb, np.argmax(np.abs(xb), axis=2)[:, :, None], axis=2)[:, :, 0]
+        scale = -vmax / 4.0
+        smax = np.take_along_axis(scale, np.argmax(np.abs(scale), axis=1)[:, None], axis=1)[:, 0]
+        iscale = np.where(smax != 0, -32.0 / np.where(smax != 0, smax, 1), 0)
+        d = np.where(iscale != 0, 1.0 / np.where(iscale != 0, iscale, 1), 0)
+        d16 = _f16(d)
+        sc = np.clip(np.rint(iscale[:, None] * scale), -32, 31).astype(np.int16)
+        eff = d16.astype(np.float32)[:, None] * sc.astype(np.float32)
+        q = np.where(eff[:, :, None] != 0, np.rint(xb / np.where(eff != 0, eff, 1)[:, :, None]), 0)
+        q = (np.clip(q, -4, 3) + 4).astype(np.uint8).reshape(-1, 256)
+        hmask = np.zeros((q.shape[0], 32), np.uint8)
+        for n in range(2):
+            for j in range(4):
+                hmask |= ((q[:, 128 * n + 32 * j:128 * n + 32 * j + 32] >> 2) & 1).astype(np.uint8) << (4 * n + j)
+        return np.concatenate([hmask, _pack_2bit(q), _pack_q3k_scales((sc + 32).astype(np.uint8)),
+                               d16.reshape(-1, 1).view(np.uint8)], axis=1).reshape(-1)
     if t == GGMLType.Q6_K:
         xb = x.reshape(-1, 16, 16)
         amax_idx = np.argmax(np.abs(xb), axis=2)
@@ -386,6 +505,17 @@ def random_blocks(ggml_type, n_elements: int, rng: np.random.Generator, std: flo
         raw[:, 0:2] = _f16(d).reshape(-1, 1).view(np.uint8)
         if t in (GGMLType.Q4_1, GGMLType.Q5_1):
             raw[:, 2:4] = _f16(-d * nmax / 2).reshape(-1, 1).view(np.uint8)
+    elif t == GGMLType.Q2_K:
+        # sc, m uniform in [0,15]; q uniform in [0,3]; dmin = 1.5 d centres w:
+        # var = E[sc^2] E[q^2] - (E[sc] E[q])^2 + 1.5^2 var(m)
+        var = (15 * 31 / 6) * 3.5 - (7.5 * 1.5) ** 2 + 2.25 * (16 ** 2 - 1) / 12
+        d = np.full(nb, std / np.sqrt(var), np.float32) * rng.uniform(0.5, 1.5, nb).astype(np.float32)
+        raw[:, 80:82] = _f16(d).reshape(-1, 1).view(np.uint8)
+        raw[:, 82:84] = _f16(d * 1.5).reshape(-1, 1).view(np.uint8)
+    elif t == GGMLType.Q3_K:
+        # sc - 32 uniform in [-32,31] (mean square 341.5); q uniform in [-4,3] (mean square 5.5)
+        d = np.full(nb, std / np.sqrt(341.5 * 5.5), np.float32) * rng.uniform(0.5, 1.5, nb).astype(np.float32)
+        raw[:, 108:110] = _f16(d).reshape(-1, 1).view(np.uint8)
     elif t == GGMLType.Q6_K:
         # scales int8 uniform [-128,127] (rms ~73.9); q-32 uniform [-32,31] (rms ~18.5)
         d = np.full(nb, std / (73.9 * 18.5), np.float32) * rng.uniform(0.5, 1.5, nb).astype(np.float32)

@@ -12,6 +12,8 @@ follow the upstream Q4_K_M mix rule::
 
 The legacy file types ("q4_0", "q4_1", "q5_0", "q5_1") are uniform: every 2-D tensor,
 token_embd included, has the file's type and output.weight is Q6_K, as llama.cpp writes them.
+
+The 2- and 3-bit K-quant files ("q2_k", "q3_k_s", "q3_k_m") follow the rule in ``tensor_types``.
 """
 from __future__ import annotations
 
@@ -22,8 +24,8 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .constants import (FTYPE_MOSTLY_Q4_0, FTYPE_MOSTLY_Q4_1, FTYPE_MOSTLY_Q4_K_M, FTYPE_MOSTLY_Q5_0,
-                        FTYPE_MOSTLY_Q5_1, FTYPE_MOSTLY_Q8_0, GGMLType, GGUFValueType,
+from .constants import (FTYPE_MOSTLY_Q2_K, FTYPE_MOSTLY_Q3_K_M, FTYPE_MOSTLY_Q3_K_S, FTYPE_MOSTLY_Q4_0,
+                        FTYPE_MOSTLY_Q4_1, FTYPE_MOSTLY_Q4_K_M, FTYPE_MOSTLY_Q5_0, FTYPE_MOSTLY_Q5_1, FTYPE_MOSTLY_Q8_0, GGMLType, GGUFValueType,
                         TOKEN_TYPE_BYTE, TOKEN_TYPE_CONTROL, TOKEN_TYPE_NORMAL)
 from .quants import random_blocks
 from .writer import GGUFWriter
@@ -72,6 +74,7 @@ class ModelSpec:
     rope_base: float
     tokenizer: str            # "bpe" | "spm"
     quant: str                # "q4_k_m" | "q8_0" | "f32" | "mixed-test" | LEGACY_QUANTS | "legacy-mixed-test"
+    #                           | K23_QUANTS | "kmixed-test"
     n_expert: int = 0
     n_expert_used: int = 0
     n_ctx_train: int = 8192
@@ -94,6 +97,13 @@ LEGACY_QUANTS = {
     "q4_1": (GGMLType.Q4_1, FTYPE_MOSTLY_Q4_1),
     "q5_0": (GGMLType.Q5_0, FTYPE_MOSTLY_Q5_0),
     "q5_1": (GGMLType.Q5_1, FTYPE_MOSTLY_Q5_1),
+}
+
+# the 2- and 3-bit K-quant file types: quant name -> (base tensor type, general.file_type)
+K23_QUANTS = {
+    "q2_k": (GGMLType.Q2_K, FTYPE_MOSTLY_Q2_K),
+    "q3_k_s": (GGMLType.Q3_K, FTYPE_MOSTLY_Q3_K_S),
+    "q3_k_m": (GGMLType.Q3_K, FTYPE_MOSTLY_Q3_K_M),
 }
 
 SPECS: Dict[str, ModelSpec] = {
@@ -194,13 +204,58 @@ SPECS.update({
 })
 
 
+# the 2- and 3-bit K-quants (Q2_K / Q3_K) over existing shapes
+SPECS.update({
+    "tiny-llama3-q2_k": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama3-q2_k", quant="q2_k"),
+    "tiny-llama3-q3_k_s": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama3-q3_k_s", quant="q3_k_s"),
+    "tiny-llama3-q3_k_m": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama3-q3_k_m", quant="q3_k_m"),
+    # one layer holding Q2_K, Q3_K, Q4_K and Q6_K
+    "tiny-kmixed-1l": replace(SPECS["tiny-mixed-1l"], name="tiny-kmixed-1l", quant="kmixed-test"),
+    # Q|K|V biases and the NeoX row permutation on a Q3_K attn_q; the tied head is a Q3_K GEMV
+    "tiny-qwen2-q3_k_m": replace(SPECS["tiny-qwen2-g6-hd64"], name="tiny-qwen2-q3_k_m", quant="q3_k_m"),
+    "llama3-8b-q3_k_m": replace(SPECS["llama3-8b-q4_k_m"], name="Llama-3-8B-Q3_K_M", quant="q3_k_m"),
+    "llama3-8b-q2_k": replace(SPECS["llama3-8b-q4_k_m"], name="Llama-3-8B-Q2_K", quant="q2_k"),
+})
+
+
 def use_more_bits(i: int, n: int) -> bool:
     return i < n // 8 or i >= 7 * n // 8 or (i - n // 8) % 3 == 2
 
 
 def tensor_types(spec: ModelSpec, layer: int) -> Dict[str, GGMLType]:
-    """Per-layer ggml types of the 2-D weights for the spec's quant mix."""
+    """Per-layer ggml types of the 2-D weights for the spec's quant mix.
+
+    The 2- and 3-bit K-quant files follow llama.cpp's llama_tensor_get_type for dense models
+    (token_embd has the base type and output.weight is Q6_K, see ``tensor_plan``):
+
+      q3_k_s: every matrix Q3_K.
+      q3_k_m: base Q3_K; attn_v Q5_K in the first two layers, Q4_K after; attn_output Q4_K;
+              ffn_down Q5_K in the first n_layer/16 layers, Q4_K after.
+      q2_k:   base Q2_K; attn_v Q4_K when the GQA group is >= 4, else Q3_K; attn_output Q3_K;
+              ffn_down Q3_K.
+    8-expert models keep attn_k / attn_v at Q8_0 as in the Q4_K_M rule."""
     q = spec.quant
+    if q in K23_QUANTS:
+        base = K23_QUANTS[q][0]
+        out = {k: base for k in ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")}
+        if q == "q3_k_m":
+            out["attn_v"] = GGMLType.Q5_K if layer < 2 else GGMLType.Q4_K
+            out["attn_output"] = GGMLType.Q4_K
+            out["ffn_down"] = GGMLType.Q5_K if layer < spec.n_layer // 16 else GGMLType.Q4_K
+        elif q == "q2_k":
+            out["attn_v"] = GGMLType.Q4_K if spec.n_head // spec.n_head_kv >= 4 else GGMLType.Q3_K
+            out["attn_output"] = GGMLType.Q3_K
+            out["ffn_down"] = GGMLType.Q3_K
+        if spec.n_expert == 8:
+            out["attn_k"] = GGMLType.Q8_0
+            out["attn_v"] = GGMLType.Q8_0
+        return out
+    if q == "kmixed-test":  # Q2_K and Q3_K beside Q4_K and Q6_K in one model
+        cyc = [GGMLType.Q2_K, GGMLType.Q3_K, GGMLType.Q4_K, GGMLType.Q6_K]
+        names = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_down")
+        out = {k: cyc[(layer + j) % 4] for j, k in enumerate(names)}
+        out["ffn_up"] = out["ffn_gate"]
+        return out
     if q == "q8_0":
         t = GGMLType.Q8_0
         return {k: t for k in ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")}
@@ -308,6 +363,10 @@ def tensor_plan(spec: ModelSpec, n_vocab: int) -> List[Tuple[str, GGMLType, Tupl
         emb_t, out_t = LEGACY_QUANTS[spec.quant][0], GGMLType.Q6_K
     elif spec.quant == "legacy-mixed-test":
         emb_t, out_t = GGMLType.Q5_0, GGMLType.Q6_K
+    elif spec.quant in K23_QUANTS:
+        emb_t, out_t = K23_QUANTS[spec.quant][0], GGMLType.Q6_K
+    elif spec.quant == "kmixed-test":
+        emb_t, out_t = GGMLType.Q2_K, GGMLType.Q6_K
     else:
         emb_t, out_t = GGMLType.Q4_K, GGMLType.Q6_K
     plan = [("token_embd.weight", emb_t, (d, n_vocab))]
@@ -343,6 +402,8 @@ def hparams_metadata(spec: ModelSpec, n_vocab: int) -> Dict:
     a = spec.arch
     if spec.quant in LEGACY_QUANTS:
         ftype = LEGACY_QUANTS[spec.quant][1]
+    elif spec.quant in K23_QUANTS:
+        ftype = K23_QUANTS[spec.quant][1]
     else:
         ftype = FTYPE_MOSTLY_Q8_0 if spec.quant == "q8_0" else FTYPE_MOSTLY_Q4_K_M
     md = {"general.architecture": a, "general.name": spec.name + " (synthetic random-init)",
