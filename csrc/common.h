@@ -24,6 +24,14 @@
 //           (scale | min << 4) bytes or Q3_K's sixteen packed 6-bit scales. Q3_K's 12-byte scale
 //           rows are 4-byte aligned, and its sc / d planes start 16-byte aligned when R * K / 256
 //           is a multiple of 4 (4-byte aligned otherwise): they are read as dwords / halves.)
+//   IQ4_NL : qs[R][K/32][16]  | d[R][K/32] (f16)                     (Q4_0's layout)
+//   IQ4_XS : qs[R][K/256][128] | sc[R][K/256][8]
+//          (the non-linear 4-bit pair: a nibble indexes the 16-entry int8 codebook kIQ4Values.
+//           Every 32-weight chunk is contiguous with Q4_0's nibble order - byte j of chunk c's 16
+//           holds weight 32c + j low and weight 32c + 16 + j high. IQ4_XS's sc keeps the GGUF
+//           fields as they stand: f16 d | u16 scales_h | u8 scales_l[4], one aligned 8-byte load
+//           per superblock; sub-block ib has the 6-bit scale ls = low nibble ib of scales_l |
+//           bit pair ib of scales_h << 4 and the weight is d * (ls - 32) * codebook[nibble].)
 //   F16 / F32 : [R][K] unchanged
 //
 // Total bytes are identical to the GGUF tensor (no padding), so 4.6 GB of
@@ -49,6 +57,8 @@ enum QType : int {
   T_Q4_K = 12,
   T_Q5_K = 13,
   T_Q6_K = 14,
+  T_IQ4_NL = 20,
+  T_IQ4_XS = 23,
   T_BF16 = 30,
 };
 
@@ -72,19 +82,24 @@ inline TypeInfo type_info(int t) {
     case T_Q4_K: return {256, 144};
     case T_Q5_K: return {256, 176};
     case T_Q6_K: return {256, 210};
+    case T_IQ4_NL: return {32, 18};
+    case T_IQ4_XS: return {256, 136};
   }
   throw std::runtime_error("unsupported ggml type " + std::to_string(t));
 }
+
+// the non-linear 4-bit codebook shared by IQ4_NL and IQ4_XS
+constexpr int8_t kIQ4Values[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
 
 inline bool is_legacy_block_type(int t) { return t == T_Q4_0 || t == T_Q4_1 || t == T_Q5_0 || t == T_Q5_1; }
 
 // MoE expert tensors of the legacy 32-weight block types are not supported (attention, router
 // and embeddings of such a file are): refuse the model at load, naming the tensor.
-// The same holds for the 2- and 3-bit K-quants Q2_K and Q3_K.
+// The same holds for the 2- and 3-bit K-quants Q2_K and Q3_K and for IQ4_NL and IQ4_XS.
 inline void check_expert_type(const std::string& tensor, int t) {
-  if (!is_legacy_block_type(t) && t != T_Q2_K && t != T_Q3_K) return;
+  if (!is_legacy_block_type(t) && t != T_Q2_K && t != T_Q3_K && t != T_IQ4_NL && t != T_IQ4_XS) return;
   const char* n = t == T_Q4_0 ? "Q4_0" : t == T_Q4_1 ? "Q4_1" : t == T_Q5_0 ? "Q5_0" : t == T_Q5_1 ? "Q5_1"
-                  : t == T_Q2_K ? "Q2_K" : "Q3_K";
+                  : t == T_Q2_K ? "Q2_K" : t == T_Q3_K ? "Q3_K" : t == T_IQ4_NL ? "IQ4_NL" : "IQ4_XS";
   throw std::runtime_error("unsupported expert tensor " + tensor + ": type " + n +
                            " (MoE experts must be Q4_K, Q5_K, Q6_K, Q8_0, F16 or F32)");
 }
@@ -135,8 +150,12 @@ LFK_HD Planes planes_of(int t, size_t R, size_t K) {
       p.s0 = nb * 32; p.s1 = nb * 2;
       p.p0 = 0; p.p1 = R * p.s0;
       break;
-    case T_Q4_0: case T_Q4_1:
-      p.s0 = nb * 16; p.s1 = nb * (t == T_Q4_0 ? 2 : 4);
+    case T_IQ4_XS:
+      p.s0 = nsb * 128; p.s1 = nsb * 8;
+      p.p0 = 0; p.p1 = R * p.s0;
+      break;
+    case T_Q4_0: case T_Q4_1: case T_IQ4_NL:
+      p.s0 = nb * 16; p.s1 = nb * (t == T_Q4_1 ? 4 : 2);
       p.p0 = 0; p.p1 = R * p.s0;
       break;
     case T_Q5_0: case T_Q5_1:

@@ -146,6 +146,17 @@ inline int q3k_scale(const uint8_t* q, int s) {
 
 inline float hf(const uint8_t* p) { uint16_t h; std::memcpy(&h, p, 2); return h2f(h); }
 
+// scale of chunk c of a row of IQ4_NL (d) / IQ4_XS (d * (ls - 32)); sp = the row of the scale plane
+inline float iq4_scale(int type, const uint8_t* sp, int c) {
+  if (type == T_IQ4_NL) return hf(sp + 2 * c);
+  const uint8_t* m = sp + 8 * (c >> 3);  // d | scales_h | scales_l[4]
+  const int ib = c & 7;
+  uint16_t sh;
+  std::memcpy(&sh, m + 2, 2);
+  const int ls = ((m[4 + (ib >> 1)] >> (4 * (ib & 1))) & 0xF) | (((sh >> (2 * ib)) & 3) << 4);
+  return hf(m) * (float)(ls - 32);
+}
+
 void decode_chunk(const CpuMat& W, const uint8_t* base, size_t row, int c, Chunk& ch) {
   const Planes& P = W.P;
   const int sb = c >> 3, j = c & 7;
@@ -220,6 +231,21 @@ void decode_chunk(const CpuMat& W, const uint8_t* base, size_t row, int c, Chunk
       ch.s_lo = ch.s_hi = d;
       // sum = s * dot - m * sum(x): the -8 / -16 offset and the block minimum as the m term
       ch.m_lo = ch.m_hi = has_m ? -hf(sp + 4 * c + 2) : (five ? 16.f : 8.f) * d;
+      break;
+    }
+    case T_IQ4_NL:
+    case T_IQ4_XS: {
+      // chunk c = 32 contiguous weights: byte i holds the codebook index of weight i (low nibble)
+      // and of weight 16 + i (high nibble); the codebook is signed, so there is no m term
+      const uint8_t* qs = base + P.p0 + row * P.s0 + 16 * c;
+      for (int i = 0; i < 16; ++i) {
+        ch.w[i] = kIQ4Values[qs[i] & 0xF];
+        ch.w[16 + i] = kIQ4Values[qs[i] >> 4];
+      }
+      ch.s_lo = ch.s_hi = iq4_scale(W.type, base + P.p1 + row * P.s1, c);
+      ch.m_lo = ch.m_hi = 0.f;
+      ch.off_lo = 32 * c;
+      ch.off_hi = 32 * c + 16;
       break;
     }
     case T_Q2_K:
@@ -369,7 +395,19 @@ inline __m256i chunk_w(const CpuMat& W, const uint8_t* base, size_t row, int c, 
     off_hi = 32 * c + 16;
     (void)sb; (void)j;
     return _mm256_set_m128i(hi, lo);
+  } else if constexpr (QT == T_IQ4_NL || QT == T_IQ4_XS) {  // signed codebook values, as Q8_0's bytes
+    const __m128i q = _mm_loadu_si128(reinterpret_cast<const __m128i*>(base + P.p0 + row * P.s0 + 16 * c));
+    const __m128i kv = _mm_loadu_si128(reinterpret_cast<const __m128i*>(kIQ4Values));
+    const __m128i lo = _mm_shuffle_epi8(kv, _mm_and_si128(q, m4));
+    const __m128i hi = _mm_shuffle_epi8(kv, _mm_and_si128(_mm_srli_epi16(q, 4), m4));
+    s_lo = s_hi = iq4_scale(QT, base + P.p1 + row * P.s1, c);
+    m_lo = m_hi = 0.f;
+    off_lo = 32 * c;
+    off_hi = 32 * c + 16;
+    (void)sb; (void)j;
+    return _mm256_set_m128i(hi, lo);
   } else {  // Q8_0 (signed)
+    static_assert(QT == T_Q8_0, "chunk_w: unsupported type");
     const float d = hf(base + P.p1 + row * P.s1 + 2 * c);
     s_lo = s_hi = d;
     m_lo = m_hi = 0.f;
@@ -392,20 +430,21 @@ void gemm_rows_avx2(const CpuMat& W, const uint8_t* base, const Q8& xq, int T, f
       float s_lo, m_lo, s_hi, m_hi;
       int off_lo, off_hi;
       __m256i w = chunk_w<QT>(W, base, (size_t)r, c, s_lo, m_lo, s_hi, m_hi, off_lo, off_hi);
+      constexpr bool signed_w = QT == T_Q8_0 || QT == T_IQ4_NL || QT == T_IQ4_XS;
       __m256i wa = w;
-      if constexpr (QT == T_Q8_0) wa = _mm256_sign_epi8(w, w);  // |w| (unsigned operand of vpmaddubsw)
+      if constexpr (signed_w) wa = _mm256_sign_epi8(w, w);  // |w| (unsigned operand of vpmaddubsw)
       const int blo = off_lo >> 5, bhi = off_hi >> 5;
       for (int t = 0; t < T; ++t) {
         const int8_t* x = xq.q.data() + (size_t)t * K;
         __m256i xv = _mm256_set_m128i(_mm_loadu_si128(reinterpret_cast<const __m128i*>(x + off_hi)),
                                       _mm_loadu_si128(reinterpret_cast<const __m128i*>(x + off_lo)));
-        if constexpr (QT == T_Q8_0) xv = _mm256_sign_epi8(xv, w);
+        if constexpr (signed_w) xv = _mm256_sign_epi8(xv, w);
         const __m256i p = _mm256_madd_epi16(_mm256_maddubs_epi16(wa, xv), ones);
         const float* xd = xq.d.data() + (size_t)t * nb;
         const float xl = xd[blo], xh = xd[bhi];
         const __m256 sv = _mm256_set_m128(_mm_set1_ps(s_hi * xh), _mm_set1_ps(s_lo * xl));
         acc[t] = _mm256_fmadd_ps(_mm256_cvtepi32_ps(p), sv, acc[t]);
-        if constexpr (QT != T_Q8_0) {
+        if constexpr (!signed_w) {
           const int* s16 = xq.s16.data() + (size_t)t * n16;
           mterm[t] += m_lo * xl * (float)s16[off_lo >> 4] + m_hi * xh * (float)s16[off_hi >> 4];
         }
@@ -437,6 +476,8 @@ void gemm_rows(const CpuMat& W, const uint8_t* base, const Q8& xq, int T, float*
     case T_Q5_1: return gemm_rows_avx2<T_Q5_1>(W, base, xq, T, y, ldy, add);
     case T_Q2_K: return gemm_rows_avx2<T_Q2_K>(W, base, xq, T, y, ldy, add);
     case T_Q3_K: return gemm_rows_avx2<T_Q3_K>(W, base, xq, T, y, ldy, add);
+    case T_IQ4_NL: return gemm_rows_avx2<T_IQ4_NL>(W, base, xq, T, y, ldy, add);
+    case T_IQ4_XS: return gemm_rows_avx2<T_IQ4_XS>(W, base, xq, T, y, ldy, add);
     default: return gemm_rows_scalar(W, base, xq, T, y, ldy, add);
   }
 }

@@ -1,6 +1,7 @@
 // Batched decode projection on MFMA (continuous batching, 1-16 activation rows):
 //   out[b][row] += sum_k W[row][k] * x[b][k]
-// W block-quantised (Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / Q8_0, and Q4_0 / Q4_1 / Q5_0 / Q5_1 as Q4_K / Q5_K) read from a tile-ordered copy (tile16, below);
+// W block-quantised (Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / Q8_0 / IQ4_XS, Q4_0 / Q4_1 / Q5_0 / Q5_1 as Q4_K / Q5_K and
+// IQ4_NL as IQ4_XS) read from a tile-ordered copy (tile16, below);
 // x f16 rows in a 4-group swizzled k order, staged per block in LDS - from xh (written by
 // bprep or by the attention kernel) or, for Q|K|V and gate/up, straight from the fp32
 // residual with the RMSNorm folded in.
@@ -99,6 +100,13 @@ struct K23TRaw {
 };
 template <> struct BRaw<T_Q2_K> { using type = K23TRaw; };
 template <> struct BRaw<T_Q3_K> { using type = K23TRaw; };
+// IQ4_XS (and IQ4_NL in the same step format): the chunk's 16 bytes of codebook indices and its
+// scale d * (ls - 32) (IQ4_NL: d) pre-decoded as one f16
+struct IQ4TRaw {
+  int4 q;
+  unsigned s;
+};
+template <> struct BRaw<T_IQ4_XS> { using type = IQ4TRaw; };
 template <int T> using BRawT = typename BRaw<T>::type;
 
 // chunk c of one row (raw loads in WRaw) -> the four A fragments
@@ -201,6 +209,28 @@ __device__ __forceinline__ void dequant_frags(const BRawT<T>& w, int c, HFrag& F
       F.w[4 * i + 3] = deq_pair(bytes13(hi), bias, ahi, mhi);
     }
     (void)j;
+  } else if constexpr (T == T_IQ4_XS) {
+    // the codebook lookup replaces the mask step: the table holds value + 128 as unsigned bytes,
+    // which go under the 1024 exponent as the other types' quants do; the bias removed is then
+    // 1024 + 128 = 1152 (exact in f16: 1024 + byte <= 1279 < 2048) and one multiply by the
+    // chunk's scale follows (the fma with +0 rounds once, as a multiply). VALU per quant dword
+    // (8 weights): lookup 13 (and, shift + and, 4 table perms, 2 x (shift, and-or), 2 merging
+    // perms), 4 magic perms, 4 pk_add, 4 pk_fma = 25, 3.1 per weight against Q4_K's 15 (1.9)
+    const _Float16 sc = __builtin_bit_cast(_Float16, (unsigned short)(w.s & 0xFFFF));
+    const h2_t a = {sc, sc};
+    const h2_t zero = {(_Float16)0.f, (_Float16)0.f};
+    const h2_t bias = {(_Float16)1152.f, (_Float16)1152.f};
+    const unsigned qv[4] = {(unsigned)w.q.x, (unsigned)w.q.y, (unsigned)w.q.z, (unsigned)w.q.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      unsigned lo, hi;
+      iq4_lookup<0x80u>(qv[i], lo, hi);
+      F.w[4 * i + 0] = deq_pair(bytes02(lo), bias, a, zero);
+      F.w[4 * i + 1] = deq_pair(bytes13(lo), bias, a, zero);
+      F.w[4 * i + 2] = deq_pair(bytes02(hi), bias, a, zero);
+      F.w[4 * i + 3] = deq_pair(bytes13(hi), bias, a, zero);
+    }
+    (void)j;
   } else {  // Q8_0: signed bytes, flipped to unsigned for the magic, one scale
     static_assert(T == T_Q8_0, "dequant_frags: unsupported type");
     const float d = h2f(w.d & 0xFFFF);
@@ -258,6 +288,13 @@ __device__ __forceinline__ void chunk_runs(int c, int& off_lo, int& off_hi) {
 //          = third bit of low-run weight 4i + b, bit 4 + i that of the high run's. One 16-byte
 //          load per lane and chunk carries the quants AND their pre-decoded scales: both steps
 //          are 2 x 1 KB, each read by one load instruction.)
+//   IQ4_XS: qs[h][l][16] | sc[r16][8][d*(ls-32) f16]                             2304 B
+//         (chunk j = 4h + kq is sub-block j of the 256-block: 32 contiguous weights, the low
+//          nibbles of its 16 bytes the first 16-run and the high nibbles the second, as Q8_0's x
+//          map. A nibble is a codebook index; the sub-block scale d * (ls - 32) arrives
+//          pre-decoded - the f32 product is exact, rounded once to f16 - so the kernel unpacks
+//          no 6-bit field.)
+//   IQ4_NL: the IQ4_XS step with sc = the eight blocks' d (ls - 32 = 1)
 // Rows past the matrix are zero.
 //
 // The legacy 32-weight blocks have no MFMA decode of their own. Two neighbouring blocks A, B
@@ -268,12 +305,12 @@ __device__ __forceinline__ void chunk_runs(int c, int& off_lo, int& off_hi) {
 // one-rounding q * a + b as the K-quants', so the Q4_K / Q5_K kernels serve these types as they
 // stand; callers keep passing the source type, which is mapped here.
 __host__ __device__ constexpr int t16_kernel_type(int t) {
-  return (t == T_Q4_0 || t == T_Q4_1) ? T_Q4_K : (t == T_Q5_0 || t == T_Q5_1) ? T_Q5_K : t;
+  return (t == T_Q4_0 || t == T_Q4_1) ? T_Q4_K : (t == T_Q5_0 || t == T_Q5_1) ? T_Q5_K : t == T_IQ4_NL ? T_IQ4_XS : t;
 }
 __host__ __device__ constexpr int t16_step_bytes(int t) {
   const int k = t16_kernel_type(t);
   return k == T_Q2_K ? 2048 : k == T_Q3_K ? 2048 : k == T_Q4_K ? 2560 : k == T_Q5_K ? 3072 : k == T_Q6_K ? 3584
-         : k == T_Q8_0 ? 4352 : 0;
+         : k == T_Q8_0 ? 4352 : k == T_IQ4_XS ? 2304 : 0;
 }
 
 int t16_format(int type) { return t16_kernel_type(type); }
@@ -508,6 +545,41 @@ __global__ __launch_bounds__(64) void t16_repack_k23_kernel(QMat w, uint8_t* dst
   }
 }
 
+// IQ4_NL / IQ4_XS -> the IQ4_XS step (see the layout comment above): the quant bytes as they
+// stand, and the eight chunks' scales decoded by lane kq = 0 of each row
+template <int T>
+__global__ __launch_bounds__(64) void t16_repack_iq4_kernel(QMat w, uint8_t* dst, int swiglu) {
+  static_assert(is_iq4_v<T>, "IQ4_NL / IQ4_XS only");
+  const int s = blockIdx.x, t = blockIdx.y, steps = gridDim.x;
+  const int l = threadIdx.x, r16 = l & 15, kq = l >> 4;
+  int row = t * 16 + r16;
+  bool ok = row < w.rows;
+  if (swiglu) {  // as t16_repack_kernel
+    const int f = 8 * t + (r16 & 7);
+    row = 64 * (f >> 5) + (r16 >= 8 ? 32 : 0) + (f & 31);
+    ok = f < w.rows / 2;
+  }
+  const size_t r = ok ? (size_t)row : 0;
+  uint8_t* blk = dst + ((size_t)t * steps + s) * t16_step_bytes(T);
+  const Planes& P = w.P;
+  const uint8_t* p0 = w.base + P.p0 + r * P.s0;
+  const uint8_t* p1 = w.base + P.p1 + r * P.s1;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) copy16(blk + h * 1024 + l * 16, p0 + 16 * (8 * s + 4 * h + kq), ok);
+  if (kq != 0) return;
+  unsigned short sc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    IQ4Raw raw;
+    iq4_load<T, false>(raw, p0, p1, 8 * s + j);
+    // d * (ls - 32): 11 x 6 significant bits, exact in f32; one rounding to f16
+    sc[j] = ok ? __builtin_bit_cast(unsigned short, (_Float16)iq4_scale<T>(raw, 8 * s + j)) : (unsigned short)0;
+  }
+  *reinterpret_cast<uint4*>(blk + 2048 + r16 * 16) =
+      make_uint4(sc[0] | (unsigned)sc[1] << 16, sc[2] | (unsigned)sc[3] << 16, sc[4] | (unsigned)sc[5] << 16,
+                 sc[6] | (unsigned)sc[7] << 16);
+}
+
 void t16_repack(const QMat& w, uint8_t* dst, hipStream_t st, bool swiglu) {
   if (!bmm_supported(w.type, w.K)) throw std::runtime_error("t16_repack: unsupported type / K");
   if (swiglu && w.rows % 64) throw std::runtime_error("t16_repack: SwiGLU copy needs 32-row gate / up groups");
@@ -524,6 +596,8 @@ void t16_repack(const QMat& w, uint8_t* dst, hipStream_t st, bool swiglu) {
     case T_Q5_1: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q5_1>, grid, dim3(64), 0, st, w, dst, sw); break;
     case T_Q2_K: hipLaunchKernelGGL(t16_repack_k23_kernel<T_Q2_K>, grid, dim3(64), 0, st, w, dst, sw); break;
     case T_Q3_K: hipLaunchKernelGGL(t16_repack_k23_kernel<T_Q3_K>, grid, dim3(64), 0, st, w, dst, sw); break;
+    case T_IQ4_NL: hipLaunchKernelGGL(t16_repack_iq4_kernel<T_IQ4_NL>, grid, dim3(64), 0, st, w, dst, sw); break;
+    case T_IQ4_XS: hipLaunchKernelGGL(t16_repack_iq4_kernel<T_IQ4_XS>, grid, dim3(64), 0, st, w, dst, sw); break;
     default: throw std::runtime_error("t16_repack: unsupported type");
   }
 }
@@ -552,6 +626,9 @@ __device__ __forceinline__ void tload(BRawT<T>& w, const uint8_t* blk, int h, in
     w.s = *reinterpret_cast<const unsigned*>(blk + 3072 + r16 * 32 + (4 * h + kq) * 4);
   } else if constexpr (T == T_Q2_K || T == T_Q3_K) {
     w.v = ld_q16<T, NT>(blk + h * 1024 + l * 16);
+  } else if constexpr (T == T_IQ4_XS) {
+    w.q = ld_q16<T, NT>(blk + h * 1024 + l * 16);
+    w.s = *reinterpret_cast<const unsigned short*>(blk + 2048 + r16 * 16 + (4 * h + kq) * 2);
   } else {
     static_assert(T == T_Q8_0, "tload: unsupported type");
     w.a = ld_q16<T, NT>(blk + h * 2048 + l * 16);
@@ -593,6 +670,9 @@ __device__ __forceinline__ void tload_rs(BRawT<T>& w, __amdgpu_buffer_rsrc_t rs,
     w.s = __builtin_amdgcn_raw_buffer_load_b32(rs, r16 * 32 + kq * 4, so + 3072 + 16 * h, 0);
   } else if constexpr (T == T_Q2_K || T == T_Q3_K) {
     w.v = b128(l * 16, h * 1024);
+  } else if constexpr (T == T_IQ4_XS) {
+    w.q = b128(l * 16, h * 1024);
+    w.s = __builtin_amdgcn_raw_buffer_load_b16(rs, r16 * 16 + kq * 2, so + 2048 + 8 * h, 0);
   } else {
     static_assert(T == T_Q8_0, "tload_rs: unsupported type");
     w.a = b128(l * 16, h * 2048);
@@ -603,7 +683,7 @@ __device__ __forceinline__ void tload_rs(BRawT<T>& w, __amdgpu_buffer_rsrc_t rs,
 
 template <int T>
 __device__ __forceinline__ int raw_word(const BRawT<T>& w) {
-  if constexpr (T == T_Q4_K || T == T_Q5_K) return w.q.x;
+  if constexpr (T == T_Q4_K || T == T_Q5_K || T == T_IQ4_XS) return w.q.x;
   else if constexpr (T == T_Q6_K) return w.l.x;
   else if constexpr (T == T_Q2_K || T == T_Q3_K) return w.v.x;
   else return w.a.x;
@@ -1914,7 +1994,7 @@ bool bmm_norm_fits(int K, int B) { return bmm_qkv_fits(K, B) && K == 4096 && B <
 
 bool bmm_supported(int type, int K) {
   const int k = t16_kernel_type(type);  // the legacy 32-block types run as Q4_K / Q5_K
-  if (k != T_Q4_K && k != T_Q5_K && k != T_Q6_K && k != T_Q8_0 && k != T_Q2_K && k != T_Q3_K) return false;
+  if (k != T_Q4_K && k != T_Q5_K && k != T_Q6_K && k != T_Q8_0 && k != T_Q2_K && k != T_Q3_K && k != T_IQ4_XS) return false;
   return K % 256 == 0;  // 256 k per step
 }
 
@@ -2167,6 +2247,7 @@ void bmm(const BmmArgs& a0, hipStream_t s) {
     else if (a.w.type == T_Q8_0) launch_qkv_sk<T_Q8_0, 0>(a, s);
     else if (a.w.type == T_Q2_K) launch_qkv_sk<T_Q2_K, 0>(a, s);
     else if (a.w.type == T_Q3_K) launch_qkv_sk<T_Q3_K, 0>(a, s);
+    else if (a.w.type == T_IQ4_XS) launch_qkv_sk<T_IQ4_XS, 0>(a, s);
     else throw std::runtime_error("bmm: unsupported weight type");
     return;
   }
@@ -2177,6 +2258,7 @@ void bmm(const BmmArgs& a0, hipStream_t s) {
     case T_Q8_0: launch_bmm<T_Q8_0>(a, s); break;
     case T_Q2_K: launch_bmm<T_Q2_K>(a, s); break;
     case T_Q3_K: launch_bmm<T_Q3_K>(a, s); break;
+    case T_IQ4_XS: launch_bmm<T_IQ4_XS>(a, s); break;
     default: throw std::runtime_error("bmm: unsupported weight type");
   }
 }
@@ -2612,6 +2694,7 @@ void gemm_t16(const GemmT16Args& a, int epi, hipStream_t s) {
     case T_Q8_0: gemm_t16_epi<T_Q8_0>(a, epi, s); break;
     case T_Q2_K: gemm_t16_epi<T_Q2_K>(a, epi, s); break;
     case T_Q3_K: gemm_t16_epi<T_Q3_K>(a, epi, s); break;
+    case T_IQ4_XS: gemm_t16_epi<T_IQ4_XS>(a, epi, s); break;
     default: throw std::runtime_error("gemm_t16: unsupported weight type");
   }
 }

@@ -266,6 +266,8 @@ void gemm_dq(const GemmArgs& a, int epi, hipStream_t s) {
     case T_Q5_1: launch_gemm<T_Q5_1>(a, epi, s); break;
     case T_Q2_K: launch_gemm<T_Q2_K>(a, epi, s); break;
     case T_Q3_K: launch_gemm<T_Q3_K>(a, epi, s); break;
+    case T_IQ4_NL: launch_gemm<T_IQ4_NL>(a, epi, s); break;
+    case T_IQ4_XS: launch_gemm<T_IQ4_XS>(a, epi, s); break;
     case T_F16: launch_gemm<T_F16>(a, epi, s); break;
     case T_F32: launch_gemm<T_F32>(a, epi, s); break;
     default: throw std::runtime_error("gemm_dq: unsupported weight type");

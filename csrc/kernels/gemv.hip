@@ -562,7 +562,7 @@ static void launch_gemv_splitk(const GemvArgs& a, hipStream_t s) {
 
 template <int QT, int EPI>
 static void launch_gemv(const GemvArgs& a, hipStream_t s) {
-  if constexpr (EPI == EPI_ADD && (QT == T_Q4_K || QT == T_Q5_K || QT == T_Q6_K || QT == T_Q8_0 || is_legacy_v<QT> || is_k23_v<QT>)) {
+  if constexpr (EPI == EPI_ADD && (QT == T_Q4_K || QT == T_Q5_K || QT == T_Q6_K || QT == T_Q8_0 || is_legacy_v<QT> || is_k23_v<QT> || is_iq4_v<QT>)) {
     // (Q3_K too: its 4-row items spill in the 1024-thread form, yet one row per wave without the
     // K split measured slower - llama3-8b-q2_k 2.09 against 1.90 ms per token)
     if (!a.dbg_clk && a.w.K >= 4096 && !a.debug) return launch_gemv_splitk<QT>(a, s);
@@ -596,6 +596,8 @@ void gemv_legacy(const GemvArgs& a, int epi, hipStream_t s) {
     case T_Q5_1: gemv_t<T_Q5_1>(a, epi, s); break;
     case T_Q2_K: gemv_t<T_Q2_K>(a, epi, s); break;
     case T_Q3_K: gemv_t<T_Q3_K>(a, epi, s); break;
+    case T_IQ4_NL: gemv_t<T_IQ4_NL>(a, epi, s); break;
+    case T_IQ4_XS: gemv_t<T_IQ4_XS>(a, epi, s); break;
     default: throw std::runtime_error("gemv: unsupported weight type");
   }
 }
@@ -611,7 +613,8 @@ void gemv(const GemvArgs& a, int epi, hipStream_t s) {
     case T_Q5_K: gemv_t<T_Q5_K>(a, epi, s); break;
     case T_Q6_K: gemv_t<T_Q6_K>(a, epi, s); break;
     case T_Q8_0: gemv_t<T_Q8_0>(a, epi, s); break;
-    case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: gemv_legacy(a, epi, s); break;
+    case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: case T_IQ4_NL: case T_IQ4_XS:
+      gemv_legacy(a, epi, s); break;
     case T_F16: gemv_t<T_F16>(a, epi, s); break;
     case T_F32: gemv_t<T_F32>(a, epi, s); break;
     default: throw std::runtime_error("gemv: unsupported weight type");
@@ -806,6 +809,8 @@ void gemv_qkv1_legacy(const QkvLaunch& L, int type, int rows, hipStream_t s) {
     case T_Q5_1: launch_qkv1<T_Q5_1>(L, rows, s); break;
     case T_Q2_K: launch_qkv1<T_Q2_K>(L, rows, s); break;
     case T_Q3_K: launch_qkv1<T_Q3_K>(L, rows, s); break;
+    case T_IQ4_NL: launch_qkv1<T_IQ4_NL>(L, rows, s); break;
+    case T_IQ4_XS: launch_qkv1<T_IQ4_XS>(L, rows, s); break;
     default: throw std::runtime_error("gemv_qkv: unsupported type");
   }
 }
@@ -859,7 +864,7 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
       case T_Q5_K: launch_qkv1<T_Q5_K>(L, rows_of(0, 3), s); return;
       case T_Q6_K: launch_qkv1<T_Q6_K>(L, rows_of(0, 3), s); return;
       case T_Q8_0: launch_qkv1<T_Q8_0>(L, rows_of(0, 3), s); return;
-      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K:
+      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: case T_IQ4_NL: case T_IQ4_XS:
         gemv_qkv1_legacy(L, run_type[0], rows_of(0, 3), s); return;
       case T_F16: launch_qkv1<T_F16>(L, rows_of(0, 3), s); return;
       case T_F32: launch_qkv1<T_F32>(L, rows_of(0, 3), s); return;
@@ -886,7 +891,7 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
       case T_Q5_K: launch_qkv1<T_Q5_K>(Li, m[i]->rows, s); break;
       case T_Q6_K: launch_qkv1<T_Q6_K>(Li, m[i]->rows, s); break;
       case T_Q8_0: launch_qkv1<T_Q8_0>(Li, m[i]->rows, s); break;
-      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K:
+      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: case T_IQ4_NL: case T_IQ4_XS:
         gemv_qkv1_legacy(Li, m[i]->type, m[i]->rows, s); break;
       case T_F16: launch_qkv1<T_F16>(Li, m[i]->rows, s); break;
       case T_F32: launch_qkv1<T_F32>(Li, m[i]->rows, s); break;

@@ -254,6 +254,14 @@ __global__ void fix_scales_kernel(uint8_t* base, int type, size_t nblocks, Plane
     } else if (type == T_Q3_K) {
       // sc - 32 uniform in [-32, 31] (mean square 341.5), q - 4 in [-4, 3] (mean square 5.5)
       reinterpret_cast<__half*>(base + P.p3)[b] = __float2half(std / sqrtf(341.5f * 5.5f) * jit);
+    } else if (type == T_IQ4_NL) {
+      // codebook index uniform (mean square 4548); a random sign of d centres the weights (the
+      // codebook's mean is -5.875), as random_blocks
+      const float sgn = (mix64(seed * 17 + b) & 1ull) ? 1.f : -1.f;
+      reinterpret_cast<__half*>(base + P.p1)[b] = __float2half(sgn * std / sqrtf(4548.f) * jit);
+    } else if (type == T_IQ4_XS) {
+      // ls - 32 uniform in [-32, 31] (mean square 341.5); sc record b (8 B): d first
+      reinterpret_cast<__half*>(base + P.p1 + 8 * b)[0] = __float2half(std / sqrtf(341.5f * 4548.f) * jit);
     } else if (type == T_F32) {
       // uniform in [-sqrt(3) std, sqrt(3) std]
       const float u = u01(mix64(seed ^ (b * 0x9E37ull)));
@@ -271,8 +279,9 @@ void fill_random_planar(uint8_t* base, int type, size_t rows, size_t K, float st
   const Planes P = planes_of(type, rows, K);
   hipLaunchKernelGGL(fill_bytes_kernel, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t*>(base), bytes / 4, seed);
   size_t nblocks;
-  if (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q2_K || type == T_Q3_K) nblocks = rows * (K / 256);
-  else if (type == T_Q8_0 || type == T_Q4_0 || type == T_Q4_1 || type == T_Q5_0 || type == T_Q5_1)
+  if (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q2_K || type == T_Q3_K || type == T_IQ4_XS)
+    nblocks = rows * (K / 256);
+  else if (type == T_Q8_0 || type == T_Q4_0 || type == T_Q4_1 || type == T_Q5_0 || type == T_Q5_1 || type == T_IQ4_NL)
     nblocks = rows * (K / 32);
   else if (type == T_F16 || type == T_BF16 || type == T_F32) nblocks = rows * K;
   else throw std::runtime_error("fill_random_planar: unsupported type");

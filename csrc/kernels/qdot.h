@@ -22,6 +22,9 @@
 //               0x03030303 mask per dword. The two lanes' loads fall in one 64-byte line of one
 //               load instruction, so HBM streams every byte once; Q3_K's hmask bytes 16h .. +15
 //               (bit 4n+2(g&1) / +1) are shared by four chunks the same way.
+//   IQ4_NL/IQ4_XS: chunk c = 32 contiguous weights @ 32c like Q8_0 (IQ4_NL: block c; IQ4_XS:
+//               sub-block c & 7 of superblock c >> 3), Q4_0's nibble order; a nibble is an index
+//               into the 16-entry signed codebook (iq4_lookup), so there is no min / offset term
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -353,6 +356,99 @@ __device__ __forceinline__ void k23_dq_decode(const K23Dq& w, int q, float* out)
   }
 }
 
+// ---- non-linear 4-bit (IQ4_NL / IQ4_XS): w = d * kIQ4Values[nibble] (IQ4_XS: d * (ls - 32) with the
+// sub-block's 6-bit ls). The codebook is signed, so the dot is scale * dx * acc with no offset term.
+template <int T> inline constexpr bool is_iq4_v = (T == T_IQ4_NL || T == T_IQ4_XS);
+
+// dword i of the codebook (entries 4i .. 4i + 3, one per byte), every byte xor `flip`: 0 gives the
+// signed bytes v_dot4 takes, 0x80 gives value + 128 as an unsigned byte (bmm.hip's f16 magic)
+constexpr unsigned iq4_table_dword(int i, unsigned flip) {
+  unsigned v = 0;
+  for (int b = 0; b < 4; ++b) v |= ((unsigned)(uint8_t)kIQ4Values[4 * i + b] ^ flip) << (8 * b);
+  return v;
+}
+
+// The codebook bytes of a quant dword's four low nibbles (lo) and four high nibbles (hi).
+// v_perm_b32 picks each result byte from 8 source bytes, the table has 16: one permute looks
+// the index's low three bits up in entries 0..7, one in entries 8..15, and a third takes byte k
+// from the second result where bit 3 of index k is set (selector k + 4) and from the first
+// otherwise (selector k). Per 4 weights: and, 2 perm, shift, and-or, perm (+ a shift for hi);
+// the table's four dwords and the masks are constants the compiler keeps in registers.
+template <unsigned FLIP>
+__device__ __forceinline__ void iq4_lookup(unsigned q, unsigned& lo, unsigned& hi) {
+  constexpr unsigned T0 = iq4_table_dword(0, FLIP), T1 = iq4_table_dword(1, FLIP);
+  constexpr unsigned T2 = iq4_table_dword(2, FLIP), T3 = iq4_table_dword(3, FLIP);
+  const unsigned sl = q & 0x07070707u, sh = (q >> 4) & 0x07070707u;
+  const unsigned pl = ((q >> 1) & 0x04040404u) | 0x03020100u, ph = ((q >> 5) & 0x04040404u) | 0x03020100u;
+  lo = __builtin_amdgcn_perm(__builtin_amdgcn_perm(T3, T2, sl), __builtin_amdgcn_perm(T1, T0, sl), pl);
+  hi = __builtin_amdgcn_perm(__builtin_amdgcn_perm(T3, T2, sh), __builtin_amdgcn_perm(T1, T0, sh), ph);
+}
+
+// one chunk's raw fields: the 16 quant bytes and the scale field(s) -
+// IQ4_NL: s0 = d; IQ4_XS: s0 = d | scales_h << 16, s1 = scales_l[4] (the superblock's 8 bytes)
+struct IQ4Raw {
+  int4 q;
+  unsigned s0, s1;
+};
+
+// chunk c of a row: plane row pointers p0 (qs) and p1 (d / sc)
+template <int T, bool NT>
+__device__ __forceinline__ void iq4_load(IQ4Raw& w, const uint8_t* p0, const uint8_t* p1, int c) {
+  if constexpr (NT) w.q = ld_nt16(p0 + 16 * c);
+  else w.q = *reinterpret_cast<const int4*>(p0 + 16 * c);
+  if constexpr (T == T_IQ4_NL) {
+    w.s0 = *reinterpret_cast<const unsigned short*>(p1 + 2 * c);
+    w.s1 = 0u;
+  } else {
+    const uint2 m = *reinterpret_cast<const uint2*>(p1 + 8 * (c >> 3));
+    w.s0 = m.x;
+    w.s1 = m.y;
+  }
+}
+
+// the chunk's scale: d, or d * (ls - 32) with ls = nibble ib of scales_l | bit pair ib of scales_h << 4
+template <int T>
+__device__ __forceinline__ float iq4_scale(const IQ4Raw& w, int c) {
+  const float d = h2f(w.s0 & 0xFFFF);
+  if constexpr (T == T_IQ4_NL) {
+    return d;
+  } else {
+    const int ib = c & 7;
+    const unsigned ls = ((w.s1 >> (4 * ib)) & 0xFu) | ((((w.s0 >> 16) >> (2 * ib)) & 3u) << 4);
+    return d * (float)((int)ls - 32);
+  }
+}
+
+template <int T>
+__device__ __forceinline__ float iq4_dot(const IQ4Raw& w, const XChunk& X, int c) {
+  const unsigned qv[4] = {(unsigned)w.q.x, (unsigned)w.q.y, (unsigned)w.q.z, (unsigned)w.q.w};
+  int acc = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    unsigned lo, hi;
+    iq4_lookup<0u>(qv[i], lo, hi);
+    acc = dot4((int)lo, X.lo[i], acc);
+    acc = dot4((int)hi, X.hi[i], acc);
+  }
+  return iq4_scale<T>(w, c) * (X.dlo * (float)acc);
+}
+
+template <int T>
+__device__ __forceinline__ void iq4_decode(const IQ4Raw& w, int c, float* out) {
+  const float sc = iq4_scale<T>(w, c);
+  const unsigned qv[4] = {(unsigned)w.q.x, (unsigned)w.q.y, (unsigned)w.q.z, (unsigned)w.q.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    unsigned lo, hi;
+    iq4_lookup<0u>(qv[i], lo, hi);
+#pragma unroll
+    for (int b8 = 0; b8 < 4; ++b8) {
+      out[4 * i + b8] = sc * (float)(signed char)((lo >> (8 * b8)) & 0xFF);
+      out[16 + 4 * i + b8] = sc * (float)(signed char)((hi >> (8 * b8)) & 0xFF);
+    }
+  }
+}
+
 // 6-bit (sc, m) pair for sub-blocks 2g and 2g+1 from the 12 packed scale bytes (ggml get_scale_min_k4).
 __device__ __forceinline__ void scale_min_pair(int g, unsigned y, unsigned z, unsigned w, float& sc_lo, float& m_lo,
                                                float& sc_hi, float& m_hi) {
@@ -453,6 +549,10 @@ __device__ __forceinline__ float chunk_dot(const uint8_t* __restrict__ base, con
     k23_load<T, true>(w, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, base + P.p2 + row * P.s2,
                       base + P.p3 + row * P.s3, c);
     return k23_dot<T>(w, X, c);
+  } else if constexpr (is_iq4_v<T>) {
+    IQ4Raw w;
+    iq4_load<T, true>(w, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, c);
+    return iq4_dot<T>(w, X, c);
   } else {  // F32 / F16 weights: dequantised x
     static_assert(T == T_F32 || T == T_F16, "chunk_dot: unsupported type");
     float s = 0.f;
@@ -495,6 +595,8 @@ template <> struct WRaw<T_Q5_0> : LegacyRaw {};
 template <> struct WRaw<T_Q5_1> : LegacyRaw {};
 template <> struct WRaw<T_Q2_K> : K23Raw {};
 template <> struct WRaw<T_Q3_K> : K23Raw {};
+template <> struct WRaw<T_IQ4_NL> : IQ4Raw {};
+template <> struct WRaw<T_IQ4_XS> : IQ4Raw {};
 template <> struct WRaw<T_F16> { uint4 w[4]; };
 template <> struct WRaw<T_F32> { float4 w[8]; };
 
@@ -541,6 +643,8 @@ __device__ __forceinline__ void wload(WRaw<T>& w, const RowPtr& R, int c) {
     legacy_load<T, true>(w, R.p0, R.p1, R.p2, c);
   } else if constexpr (is_k23_v<T>) {
     k23_load<T, true>(w, R.p0, R.p1, R.p2, R.p3, c);
+  } else if constexpr (is_iq4_v<T>) {
+    iq4_load<T, true>(w, R.p0, R.p1, c);
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) w.w[i] = reinterpret_cast<const uint4*>(R.p0 + 64 * c)[i];
@@ -604,6 +708,8 @@ __device__ __forceinline__ float wdot(const WRaw<T>& w, const XChunk& X, int c) 
     return legacy_dot<T>(w, X);
   } else if constexpr (is_k23_v<T>) {
     return k23_dot<T>(w, X, c);
+  } else if constexpr (is_iq4_v<T>) {
+    return iq4_dot<T>(w, X, c);
   } else {
     static_assert(T == T_F32 || T == T_F16, "wdot: unsupported type");
     const int xv[8] = {X.lo[0], X.lo[1], X.lo[2], X.lo[3], X.hi[0], X.hi[1], X.hi[2], X.hi[3]};
@@ -697,6 +803,10 @@ __device__ __forceinline__ void dequant32(const uint8_t* __restrict__ base, cons
     K23Dq w;
     k23_dq_load<T>(w, base, P, row, q);
     k23_dq_decode<T>(w, q, out);
+  } else if constexpr (is_iq4_v<T>) {
+    IQ4Raw w;
+    iq4_load<T, false>(w, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, q);
+    iq4_decode<T>(w, q, out);
   } else if constexpr (T == T_F32) {
     const float4* wp = reinterpret_cast<const float4*>(base + row * P.s0 + 128 * q);
 #pragma unroll
@@ -730,6 +840,8 @@ template <> struct DqRaw<T_Q5_0> : LegacyRaw {};
 template <> struct DqRaw<T_Q5_1> : LegacyRaw {};
 template <> struct DqRaw<T_Q2_K> : K23Dq {};
 template <> struct DqRaw<T_Q3_K> : K23Dq {};
+template <> struct DqRaw<T_IQ4_NL> : IQ4Raw {};
+template <> struct DqRaw<T_IQ4_XS> : IQ4Raw {};
 template <> struct DqRaw<T_F16> { uint4 w[4]; };
 template <> struct DqRaw<T_F32> { float4 w[8]; };
 
@@ -766,6 +878,8 @@ __device__ __forceinline__ void dq_load(DqRaw<T>& r, const uint8_t* __restrict__
     legacy_load<T, false>(r, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, base + P.p2 + row * P.s2, q);
   } else if constexpr (is_k23_v<T>) {
     k23_dq_load<T>(r, base, P, row, q);
+  } else if constexpr (is_iq4_v<T>) {
+    iq4_load<T, false>(r, base + P.p0 + row * P.s0, base + P.p1 + row * P.s1, q);
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) r.w[i] = reinterpret_cast<const uint4*>(base + row * P.s0 + 64 * q)[i];
@@ -827,6 +941,8 @@ __device__ __forceinline__ void dq_decode(const DqRaw<T>& r, int q, float* out) 
     legacy_decode<T>(r, out);
   } else if constexpr (is_k23_v<T>) {
     k23_dq_decode<T>(r, q, out);
+  } else if constexpr (is_iq4_v<T>) {
+    iq4_decode<T>(r, q, out);
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -849,7 +965,7 @@ __device__ __forceinline__ void dq_decode(const DqRaw<T>& r, int q, float* out) 
 // outside the list runs nothing: host launchers check with dispatchable_type() and throw.
 LFK_HD bool dispatchable_type(int t) {
   return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0 || t == T_Q4_0 || t == T_Q4_1 || t == T_Q5_0 ||
-         t == T_Q5_1 || t == T_Q2_K || t == T_Q3_K || t == T_F16 || t == T_F32;
+         t == T_Q5_1 || t == T_Q2_K || t == T_Q3_K || t == T_IQ4_NL || t == T_IQ4_XS || t == T_F16 || t == T_F32;
 }
 #define LFK_DISPATCH_TYPE(t, ...)                          \
   switch (t) {                                             \
@@ -863,6 +979,8 @@ LFK_HD bool dispatchable_type(int t) {
     case T_Q5_1: { constexpr int QT = T_Q5_1; __VA_ARGS__; } break; \
     case T_Q2_K: { constexpr int QT = T_Q2_K; __VA_ARGS__; } break; \
     case T_Q3_K: { constexpr int QT = T_Q3_K; __VA_ARGS__; } break; \
+    case T_IQ4_NL: { constexpr int QT = T_IQ4_NL; __VA_ARGS__; } break; \
+    case T_IQ4_XS: { constexpr int QT = T_IQ4_XS; __VA_ARGS__; } break; \
     case T_F16: { constexpr int QT = T_F16; __VA_ARGS__; } break;   \
     case T_F32: { constexpr int QT = T_F32; __VA_ARGS__; } break;   \
     default: break;                                                 \

@@ -19,6 +19,7 @@ void repack_planar(int type, const uint8_t* src, size_t K_src, size_t r0, size_t
     case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_Q8_0: case T_F16: case T_BF16: case T_F32: break;
     case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: break;
     case T_Q2_K: case T_Q3_K: break;
+    case T_IQ4_NL: case T_IQ4_XS: break;
     default: throw std::runtime_error("repack: unsupported type");
   }
 #pragma omp parallel for schedule(static)
@@ -75,9 +76,17 @@ void repack_planar(int type, const uint8_t* src, size_t K_src, size_t r0, size_t
           std::memcpy(dst + P.p0 + dr * P.s0 + b * 32, blk + 2, 32);
         }
         break;
+      case T_IQ4_XS:
+        for (size_t b = 0; b < nb; ++b) {
+          const uint8_t* blk = srow + b * 136;
+          std::memcpy(dst + P.p1 + dr * P.s1 + b * 8, blk, 8);  // d | scales_h | scales_l[4]
+          std::memcpy(dst + P.p0 + dr * P.s0 + b * 128, blk + 8, 128);
+        }
+        break;
       case T_Q4_0:
+      case T_IQ4_NL:
       case T_Q4_1: {
-        const size_t sc = type == T_Q4_0 ? 2 : 4;  // d, or d and m
+        const size_t sc = type == T_Q4_1 ? 4 : 2;  // d, or d and m
         for (size_t b = 0; b < nb; ++b) {
           const uint8_t* blk = srow + b * ti.bytes;
           std::memcpy(dst + P.p1 + dr * P.s1 + b * sc, blk, sc);

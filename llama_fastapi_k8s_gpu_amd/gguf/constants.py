@@ -42,6 +42,8 @@ class GGMLType(IntEnum):
     Q5_K = 13
     Q6_K = 14
     Q8_K = 15
+    IQ4_NL = 20
+    IQ4_XS = 23
     BF16 = 30
 
 
@@ -60,6 +62,8 @@ GGML_BLOCK = {
     GGMLType.Q4_K: (256, 144),
     GGMLType.Q5_K: (256, 176),
     GGMLType.Q6_K: (256, 210),
+    GGMLType.IQ4_NL: (32, 18),
+    GGMLType.IQ4_XS: (256, 136),
 }
 
 QK_K = 256
@@ -79,6 +83,8 @@ FTYPE_MOSTLY_Q3_K_L = 13
 FTYPE_MOSTLY_Q4_K_M = 15
 FTYPE_MOSTLY_Q5_K_M = 17
 FTYPE_MOSTLY_Q6_K = 18
+FTYPE_MOSTLY_IQ4_NL = 25
+FTYPE_MOSTLY_IQ4_XS = 30
 
 # llama vocab token types
 TOKEN_TYPE_NORMAL = 1

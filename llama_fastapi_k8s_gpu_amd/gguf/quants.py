@@ -1,6 +1,7 @@
 """NumPy reference implementation of the ggml block formats used by Q4_K_M /
 Q8_0 and the legacy Q4_0 / Q4_1 / Q5_0 / Q5_1 GGUF files: Q4_K, Q5_K, Q6_K, Q8_0,
-Q4_0, Q4_1, Q5_0, Q5_1, and the 2- and 3-bit K-quants Q2_K, Q3_K (+ F16/BF16/F32).
+Q4_0, Q4_1, Q5_0, Q5_1, the 2- and 3-bit K-quants Q2_K, Q3_K, and the non-linear 4-bit pair
+IQ4_NL, IQ4_XS (+ F16/BF16/F32).
 
 This is the *reference* every native path is tested against (T1 in SURVEY
 §4.3): the C++ CPU backend, the GPU repack and the HIP kernels must reproduce
@@ -25,6 +26,11 @@ Block layouts:
                       q = ((qs[32n+l] >> 2j) & 3) + 4*((hmask[l] >> (4n+j)) & 1) - 4
                       sc[s] = 6 bits: low nibble scales[s]&0xF (s<8) / scales[s-8]>>4,
                       top two bits (scales[8+s%4] >> 2*(s//4)) & 3 ; w = d*(sc[s]-32)*q
+  IQ4_NL 18 B / 32 w: d f16 | qs[16]   w[j] = d*KVALUES_IQ4[qs[j]&15], w[j+16] = d*KVALUES_IQ4[qs[j]>>4]
+  IQ4_XS 136 B / 256 w: d f16 | scales_h u16 | scales_l[4] | qs[128]
+                      sub-block ib = 0..7 (weights 32ib..32ib+31, bytes qs[16ib..16ib+15], nibble
+                      order as IQ4_NL): ls = ((scales_l[ib//2] >> 4*(ib%2)) & 15) |
+                      (((scales_h >> 2*ib) & 3) << 4) ; w = d*(ls-32)*KVALUES_IQ4[nibble]
 
 The quantisers are simple (min/max per sub-block, no iterative search) - they
 produce valid blocks with bounded error, which is all the synthetic-model and
@@ -107,6 +113,37 @@ def _legacy_offset(t) -> int:
 
 K23_TYPES = (GGMLType.Q2_K, GGMLType.Q3_K)
 
+IQ4_TYPES = (GGMLType.IQ4_NL, GGMLType.IQ4_XS)
+
+# the 16-entry codebook a nibble of IQ4_NL / IQ4_XS indexes
+KVALUES_IQ4 = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.int8)
+
+
+def _iq4_fields(b: np.ndarray, t):
+    """Blocks uint8 [nb, bytes] of IQ4_NL / IQ4_XS -> (kv int16 [nb, bs] codebook values in weight
+    order, l int16 [nb, bs // 32] sub-block multipliers (ls - 32; 1 for IQ4_NL), d f16 [nb]):
+    w = d * l[i // 32] * kv[i]."""
+    d = b[:, 0:2].copy().view(np.float16)[:, 0]
+    if t == GGMLType.IQ4_NL:
+        qs = b[:, 2:18].reshape(-1, 1, 16)
+        l = np.ones((b.shape[0], 1), np.int16)
+    else:
+        sh = b[:, 2:4].copy().view("<u2")[:, 0].astype(np.uint32)
+        sl = b[:, 4:8]
+        ib = np.arange(8)
+        low = (sl[:, ib // 2] >> (4 * (ib % 2)).astype(np.uint8)) & 15
+        top = (sh[:, None] >> (2 * ib).astype(np.uint32)[None, :]) & 3
+        l = (low.astype(np.int16) | (top.astype(np.int16) << 4)) - 32
+        qs = b[:, 8:136].reshape(-1, 8, 16)
+    idx = np.concatenate([qs & 0xF, qs >> 4], axis=2)  # [nb, sub-blocks, 32]
+    kv = KVALUES_IQ4[idx].astype(np.int16).reshape(b.shape[0], -1)
+    return kv, l, d
+
+
+def _iq4_nearest(r: np.ndarray) -> np.ndarray:
+    """Index of the codebook entry nearest to each element of r."""
+    return np.abs(r[..., None] - KVALUES_IQ4.astype(np.float64)).argmin(axis=-1).astype(np.uint8)
+
 
 def _unpack_q3k_scales(scales: np.ndarray) -> np.ndarray:
     """scales: uint8 [nb, 12] -> the sixteen 6-bit scales, uint8 [nb, 16] (0..63, before the -32)."""
@@ -174,9 +211,12 @@ def dequantize(data, ggml_type, n_elements: int | None = None, arith: str = "f32
     rounded to f16 once, and every weight is ONE f16 rounding of q*scale + offset (a fused
     v_pk_fma_f16). Q2_K: scale f16(d*(scales[s]&0xF)), offset f16(-dmin*(scales[s]>>4)), products
     taken in f32, q in 0..3. Q3_K: scale f16(d*(sc[s]-32)), no offset, q in -4..3 (the -4 is
-    removed exactly before the multiply). Returned as float32 (exact f16 values)."""
+    removed exactly before the multiply). IQ4_NL / IQ4_XS: scale d / f16(d*(ls-32)) (the product is
+    exact in f32), no offset, and every weight is one f16 rounding of codebook value * scale.
+    Returned as float32 (exact f16 values)."""
     t = GGMLType(ggml_type)
-    if arith == "f16" and t in (GGMLType.Q8_0, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K) + LEGACY_TYPES + K23_TYPES:
+    if arith == "f16" and t in (GGMLType.Q8_0, GGMLType.Q4_K, GGMLType.Q5_K, GGMLType.Q6_K) + LEGACY_TYPES + K23_TYPES \
+            + IQ4_TYPES:
         return _dequantize_f16(data, t, n_elements)
     if t == GGMLType.F32:
         return np.frombuffer(bytes(data) if not isinstance(data, np.ndarray) else data.tobytes(),
@@ -205,6 +245,10 @@ def dequantize(data, ggml_type, n_elements: int | None = None, arith: str = "f32
         out = a * q.astype(np.float32)
         if m is not None:
             out -= np.repeat(dmin.astype(np.float32)[:, None] * m.astype(np.float32), 16, axis=1)
+    elif t in IQ4_TYPES:
+        kv, l, d = _iq4_fields(b, t)
+        dl = np.repeat(d.astype(np.float32)[:, None] * l.astype(np.float32), 32, axis=1)
+        out = dl * kv.astype(np.float32)
     elif t in (GGMLType.Q4_K, GGMLType.Q5_K):
         d = b[:, 0:2].copy().view(np.float16).astype(np.float32)
         dmin = b[:, 2:4].copy().view(np.float16).astype(np.float32)
@@ -276,6 +320,11 @@ def _dequantize_f16(data, t, n_elements):
         a = np.repeat(h(f32(d)[:, None] * f32(sc)), 16, axis=1)
         off = 0.0 if m is None else np.repeat(h(-f32(dmin)[:, None] * f32(m)), 16, axis=1)
         out = h(q.astype(np.float64) * a + off)
+    elif t in IQ4_TYPES:
+        # the tile16 copy stores f16(d*(ls-32)) per sub-block (IQ4_NL: d itself)
+        kv, l, d = _iq4_fields(b, t)
+        a = np.repeat(h(np.asarray(d, np.float32)[:, None] * np.asarray(l, np.float32)), 32, axis=1)
+        out = h(kv.astype(np.float64) * a)
     elif t in (GGMLType.Q4_K, GGMLType.Q5_K):
         d = b[:, 0:2].copy().view(np.float16).astype(np.float64)[:, 0]
         dmin = b[:, 2:4].copy().view(np.float16).astype(np.float64)[:, 0]
@@ -441,6 +490,36 @@ def quantize(x: np.ndarray, ggml_type) -> np.ndarray:
                 hmask |= ((q[:, 128 * n + 32 * j:128 * n + 32 * j + 32] >> 2) & 1).astype(np.uint8) << (4 * n + j)
         return np.concatenate([hmask, _pack_2bit(q), _pack_q3k_scales((sc + 32).astype(np.uint8)),
                                d16.reshape(-1, 1).view(np.uint8)], axis=1).reshape(-1)
+    if t == GGMLType.IQ4_NL:
+        # the weight of largest magnitude maps to the codebook's -127 (d takes its sign, flipped)
+        xb = x.reshape(-1, 32).astype(np.float64)
+        vmax = np.take_along_axis(xb, np.argmax(np.abs(xb), axis=1)[:, None], axis=1)[:, 0]
+        d16 = _f16(vmax / -127.0 + 0.0)  # (+ 0.0: an all-zero block gets +0, not -0)
+        df = d16.astype(np.float64)
+        q = np.where(df[:, None] != 0, _iq4_nearest(xb / np.where(df != 0, df, 1)[:, None]), 8).astype(np.uint8)
+        return np.concatenate([d16.reshape(-1, 1).view(np.uint8), q[:, :16] | (q[:, 16:] << 4)], axis=1).reshape(-1)
+    if t == GGMLType.IQ4_XS:
+        # per 32-weight sub-block the IQ4_NL scale; the largest of them is the block's -32 and the
+        # others are truncated towards zero against it (6 bits), so that every sub-block's extreme
+        # weight still lands on the codebook's -127 and a second pass finds the same d, scales
+        # and indices (quantize o dequantize is a fixed point)
+        xb = x.reshape(-1, 8, 32).astype(np.float64)
+        vmax = np.take_along_axis(xb, np.argmax(np.abs(xb), axis=2)[:, :, None], axis=2)[:, :, 0]
+        scale = vmax / -127.0
+        smax = np.take_along_axis(scale, np.argmax(np.abs(scale), axis=1)[:, None], axis=1)[:, 0]
+        d = smax / -32.0 + 0.0
+        d16 = _f16(d)
+        l = np.clip(np.trunc(np.where(d[:, None] != 0, scale / np.where(d != 0, d, 1)[:, None], 0)), -32, 31)
+        eff = d16.astype(np.float64)[:, None] * l
+        q = np.where(eff[:, :, None] != 0, _iq4_nearest(xb / np.where(eff != 0, eff, 1)[:, :, None]), 8).astype(np.uint8)
+        ls = (l + 32).astype(np.uint8)
+        sl = (ls[:, 0::2] & 15) | ((ls[:, 1::2] & 15) << 4)
+        sh = np.zeros(ls.shape[0], np.uint16)
+        for ib in range(8):
+            sh |= (ls[:, ib] >> 4).astype(np.uint16) << (2 * ib)
+        qs = (q[:, :, :16] | (q[:, :, 16:] << 4)).reshape(-1, 128)
+        return np.concatenate([d16.reshape(-1, 1).view(np.uint8), sh.astype("<u2").reshape(-1, 1).view(np.uint8),
+                               sl, qs], axis=1).reshape(-1)
     if t == GGMLType.Q6_K:
         xb = x.reshape(-1, 16, 16)
         amax_idx = np.argmax(np.abs(xb), axis=2)
@@ -520,6 +599,16 @@ def random_blocks(ggml_type, n_elements: int, rng: np.random.Generator, std: flo
         # scales int8 uniform [-128,127] (rms ~73.9); q-32 uniform [-32,31] (rms ~18.5)
         d = np.full(nb, std / (73.9 * 18.5), np.float32) * rng.uniform(0.5, 1.5, nb).astype(np.float32)
         raw[:, 208:210] = _f16(d).reshape(-1, 1).view(np.uint8)
+    elif t == GGMLType.IQ4_NL:
+        # codebook index uniform: mean square 4548; the codebook's mean is -5.875, so d takes a
+        # random sign (a negative d is what the quantiser writes for a positive extreme weight)
+        d = np.full(nb, std / np.sqrt(4548.0), np.float32) * rng.uniform(0.5, 1.5, nb).astype(np.float32)
+        d *= rng.choice(np.array([-1.0, 1.0], np.float32), nb)
+        raw[:, 0:2] = _f16(d).reshape(-1, 1).view(np.uint8)
+    elif t == GGMLType.IQ4_XS:
+        # ls - 32 uniform in [-32,31] (mean square 341.5, mean -0.5: the weights are centred)
+        d = np.full(nb, std / np.sqrt(341.5 * 4548.0), np.float32) * rng.uniform(0.5, 1.5, nb).astype(np.float32)
+        raw[:, 0:2] = _f16(d).reshape(-1, 1).view(np.uint8)
     else:
         raise NotImplementedError(t.name)
     return raw.reshape(-1)

@@ -14,6 +14,9 @@ The legacy file types ("q4_0", "q4_1", "q5_0", "q5_1") are uniform: every 2-D te
 token_embd included, has the file's type and output.weight is Q6_K, as llama.cpp writes them.
 
 The 2- and 3-bit K-quant files ("q2_k", "q3_k_s", "q3_k_m") follow the rule in ``tensor_types``.
+
+The non-linear 4-bit files ("iq4_nl", "iq4_xs") follow a model of the upstream rule, also in
+``tensor_types``. The mix is not load-relevant: any mix of supported types loads.
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .constants import (FTYPE_MOSTLY_Q2_K, FTYPE_MOSTLY_Q3_K_M, FTYPE_MOSTLY_Q3_K_S, FTYPE_MOSTLY_Q4_0,
+from .constants import (FTYPE_MOSTLY_IQ4_NL, FTYPE_MOSTLY_IQ4_XS, FTYPE_MOSTLY_Q2_K, FTYPE_MOSTLY_Q3_K_M, FTYPE_MOSTLY_Q3_K_S, FTYPE_MOSTLY_Q4_0,
                         FTYPE_MOSTLY_Q4_1, FTYPE_MOSTLY_Q4_K_M, FTYPE_MOSTLY_Q5_0, FTYPE_MOSTLY_Q5_1, FTYPE_MOSTLY_Q8_0, GGMLType, GGUFValueType,
                         TOKEN_TYPE_BYTE, TOKEN_TYPE_CONTROL, TOKEN_TYPE_NORMAL)
 from .quants import random_blocks
@@ -74,7 +77,7 @@ class ModelSpec:
     rope_base: float
     tokenizer: str            # "bpe" | "spm"
     quant: str                # "q4_k_m" | "q8_0" | "f32" | "mixed-test" | LEGACY_QUANTS | "legacy-mixed-test"
-    #                           | K23_QUANTS | "kmixed-test"
+    #                           | K23_QUANTS | "kmixed-test" | IQ4_QUANTS | "iq4-mixed-test"
     n_expert: int = 0
     n_expert_used: int = 0
     n_ctx_train: int = 8192
@@ -104,6 +107,12 @@ K23_QUANTS = {
     "q2_k": (GGMLType.Q2_K, FTYPE_MOSTLY_Q2_K),
     "q3_k_s": (GGMLType.Q3_K, FTYPE_MOSTLY_Q3_K_S),
     "q3_k_m": (GGMLType.Q3_K, FTYPE_MOSTLY_Q3_K_M),
+}
+
+# the non-linear 4-bit file types: quant name -> (base tensor type, general.file_type)
+IQ4_QUANTS = {
+    "iq4_nl": (GGMLType.IQ4_NL, FTYPE_MOSTLY_IQ4_NL),
+    "iq4_xs": (GGMLType.IQ4_XS, FTYPE_MOSTLY_IQ4_XS),
 }
 
 SPECS: Dict[str, ModelSpec] = {
@@ -218,6 +227,21 @@ SPECS.update({
 })
 
 
+# the non-linear 4-bit pair (IQ4_NL / IQ4_XS) over existing shapes
+SPECS.update({
+    "tiny-llama3-iq4_xs": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama3-iq4_xs", quant="iq4_xs"),
+    "tiny-llama3-iq4_nl": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama3-iq4_nl", quant="iq4_nl"),
+    # Q|K|V biases and the NeoX row permutation on IQ4_XS attn_q / attn_k; the tied head is an IQ4_XS GEMV
+    "tiny-qwen2-iq4_xs": replace(SPECS["tiny-qwen2-g6-hd64"], name="tiny-qwen2-iq4_xs", quant="iq4_xs"),
+    # IQ4_NL, IQ4_XS, Q4_K and Q6_K in one model, and in one layer
+    "tiny-iq4-mixed": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-iq4-mixed", quant="iq4-mixed-test"),
+    "tiny-iq4-mixed-1l": replace(SPECS["tiny-mixed-1l"], name="tiny-iq4-mixed-1l", quant="iq4-mixed-test"),
+    # n_ff = 576: a multiple of 32 but not of 256 (IQ4_NL's block, not IQ4_XS's; no tile16 copy of down)
+    "tiny-iq4_nl-oddff": replace(SPECS["tiny-q8-oddff"], name="tiny-iq4_nl-oddff", quant="iq4_nl"),
+    "llama3-8b-iq4_xs": replace(SPECS["llama3-8b-q4_k_m"], name="Llama-3-8B-IQ4_XS", quant="iq4_xs"),
+})
+
+
 def use_more_bits(i: int, n: int) -> bool:
     return i < n // 8 or i >= 7 * n // 8 or (i - n // 8) % 3 == 2
 
@@ -233,8 +257,29 @@ def tensor_types(spec: ModelSpec, layer: int) -> Dict[str, GGMLType]:
               ffn_down Q5_K in the first n_layer/16 layers, Q4_K after.
       q2_k:   base Q2_K; attn_v Q4_K when the GQA group is >= 4, else Q3_K; attn_output Q3_K;
               ffn_down Q3_K.
-    8-expert models keep attn_k / attn_v at Q8_0 as in the Q4_K_M rule."""
+    8-expert models keep attn_k / attn_v at Q8_0 as in the Q4_K_M rule.
+
+    The non-linear 4-bit files model the upstream rule for dense models (written from memory, with
+    no copy to check against; the mix is not load-relevant - any mix of supported types loads):
+
+      iq4_nl / iq4_xs: the base type everywhere; attn_v Q5_K when the GQA group is >= 4; ffn_down
+                       Q5_K in the first n_layer/8 layers; token_embd the base type; output.weight
+                       Q6_K."""
     q = spec.quant
+    if q in IQ4_QUANTS:
+        base = IQ4_QUANTS[q][0]
+        out = {k: base for k in ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")}
+        if spec.n_head // spec.n_head_kv >= 4:
+            out["attn_v"] = GGMLType.Q5_K
+        if layer < spec.n_layer // 8:
+            out["ffn_down"] = GGMLType.Q5_K
+        return out
+    if q == "iq4-mixed-test":  # IQ4_NL and IQ4_XS beside Q4_K and Q6_K in one model
+        cyc = [GGMLType.IQ4_NL, GGMLType.IQ4_XS, GGMLType.Q4_K, GGMLType.Q6_K]
+        names = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_down")
+        out = {k: cyc[(layer + j) % 4] for j, k in enumerate(names)}
+        out["ffn_up"] = out["ffn_gate"]
+        return out
     if q in K23_QUANTS:
         base = K23_QUANTS[q][0]
         out = {k: base for k in ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")}
@@ -367,6 +412,10 @@ def tensor_plan(spec: ModelSpec, n_vocab: int) -> List[Tuple[str, GGMLType, Tupl
         emb_t, out_t = K23_QUANTS[spec.quant][0], GGMLType.Q6_K
     elif spec.quant == "kmixed-test":
         emb_t, out_t = GGMLType.Q2_K, GGMLType.Q6_K
+    elif spec.quant in IQ4_QUANTS:
+        emb_t, out_t = IQ4_QUANTS[spec.quant][0], GGMLType.Q6_K
+    elif spec.quant == "iq4-mixed-test":
+        emb_t, out_t = GGMLType.IQ4_XS, GGMLType.Q6_K
     else:
         emb_t, out_t = GGMLType.Q4_K, GGMLType.Q6_K
     plan = [("token_embd.weight", emb_t, (d, n_vocab))]
@@ -404,6 +453,8 @@ def hparams_metadata(spec: ModelSpec, n_vocab: int) -> Dict:
         ftype = LEGACY_QUANTS[spec.quant][1]
     elif spec.quant in K23_QUANTS:
         ftype = K23_QUANTS[spec.quant][1]
+    elif spec.quant in IQ4_QUANTS:
+        ftype = IQ4_QUANTS[spec.quant][1]
     else:
         ftype = FTYPE_MOSTLY_Q8_0 if spec.quant == "q8_0" else FTYPE_MOSTLY_Q4_K_M
     md = {"general.architecture": a, "general.name": spec.name + " (synthetic random-init)",
