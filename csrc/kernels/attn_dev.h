@@ -89,7 +89,12 @@ __device__ __forceinline__ float rows_sum(float v) {
 //      (sc1 loads; no cache-maintenance fences).
 // BIAS: the split-K raw sums carry Q|K|V biases (AttnDecodeArgs::qkv_bias, qwen2) - a kernel of its
 // own, so that the code of the unbiased models is exactly what it was without them.
-template <int HD, int G, bool TL, bool BIAS = false>
+// LIVE (AttnDecodeArgs::live 1 / 2): the position is read at the top (batched: beside the slot, under
+// the wait that read needs anyway), so that a block past the row's length exits before it has issued
+// any load and the lanes past it fetch nothing (buffer loads, the offset out of range: 0 comes back
+// with no memory request). live 2 also spreads the keys evenly over the launched splits. A kernel
+// of its own, like BIAS: without it the K / V rows go out before the position is known.
+template <int HD, int G, bool TL, bool BIAS = false, bool LIVE = false>
 __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
   constexpr int DPL = HD / 4;   // dims per lane in QK
   constexpr int NLD = DPL / 8;  // 16-B loads per lane per K (or V) row
@@ -109,7 +114,7 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
                "s"(a.part), "s"(a.counters), "s"(a.out), "s"(a.debug_stop), "s"(a.batch), "s"(a.slots),
                "s"(a.slot_stride), "s"(a.q_stride), "s"(a.out_stride), "s"(a.part_stride), "s"(a.out_h),
                "s"(a.out_h_stride), "s"(a.done), "s"(a.qkv_raw), "s"(a.qkv_ld), "s"(a.k_off), "s"(a.v_off), "s"(a.ss),
-               "s"(a.inv_k), "s"(a.eps), "s"(a.rope_freq), "s"(a.qkv_bias));
+               "s"(a.inv_k), "s"(a.eps), "s"(a.rope_freq), "s"(a.qkv_bias), "s"(a.live));
   if ((int)blockIdx.z == (a.batch > 0 ? a.batch : 1)) {  // weight-touch plane (see AttnDecodeArgs::pf)
     const int nb = gridDim.x * gridDim.y, b = blockIdx.y * gridDim.x + blockIdx.x;
     uint32_t acc = 0;
@@ -128,6 +133,8 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
     if (acc == 0x9E3779B9u) *a.pf_sink = (int)acc;
     return;
   }
+  int posv = 0;  // LIVE: the row's position, one batch of loads with its slot
+  if constexpr (LIVE) posv = a.pos[a.batch > 0 ? (int)blockIdx.z : 0];
   if (a.batch > 0) {  // batched decode: this row's query, KV slot, position, workspaces and output
     const int b = blockIdx.z;
     const size_t so = (size_t)a.slots[b] * a.slot_stride;
@@ -147,8 +154,25 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
   const int kvh = blockIdx.x, split = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int kw = lane >> 2, sub = lane & 3;
-  const int start = split * CH;
-  const int key = start + wave * KPW + kw;
+  // LIVE: the length is known here. live 2: kb keys per block, the row's keys spread evenly over
+  // the first 16 launched splits (16 <= kb <= 64; past 1024 keys the 64-key splits again) and a
+  // block's keys over its 4 waves, kpw each (the lanes kw >= kpw idle)
+  int Lq = 0, kb = CH, kpw = KPW;
+  if constexpr (LIVE) {
+    posv = __builtin_amdgcn_readfirstlane(posv);
+    Lq = min(posv + 1, a.n_ctx);
+    if (a.live == 2) {
+      const int sp = min((a.n_ctx + CH - 1) / CH, 16);  // (= gridDim.y, without its kernarg read)
+      kb = min(max((Lq + sp - 1) / sp, 16), CH);
+      kpw = (kb + 3) >> 2;
+    }
+  }
+  const int start = split * kb;
+  const int key = start + wave * kpw + kw;
+  if constexpr (LIVE) {  // a dead block: no load has gone out
+    LFK_STAMP(0);
+    if (start >= Lq || a.debug_stop == 1) return;
+  }
 
   __shared__ __attribute__((aligned(16))) h2v qs[G][HD / 2];   // q * scale in f16 pairs
   __shared__ __attribute__((aligned(16))) __half vs[4][KPW][HD + 8];
@@ -194,14 +218,30 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
   for (int j = 0; j < QPT; ++j) fq[j] = (drope ? a.rope_freq : a.q)[drope ? min(tid + 256 * j, G * HD / 2 - 1) % (HD / 2) : 0];
   const size_t row = ((size_t)kvh * a.n_ctx + min(key, a.n_ctx - 1)) * HD + sub * DPL;
   uint4 kr[NLD], vr[NLD];
+  // LIVE: this kv head's cache planes as buffers; a lane without a key takes an offset past them
+  const bool inr = LIVE && kw < kpw && key < min(Lq, start + kb);
+  const int voff = inr ? (int)((key * HD + sub * DPL) * sizeof(__half)) : (int)0x80000000;
+  if constexpr (LIVE) {
+    const size_t plane = (size_t)kvh * a.n_ctx * HD;
+    const int pbytes = a.n_ctx * HD * (int)sizeof(__half);
+    const auto rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(a.k_cache + plane), 0, pbytes, 0x00020000);
+    const auto rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(a.v_cache + plane), 0, pbytes, 0x00020000);
 #pragma unroll
-  for (int i = 0; i < NLD; ++i) kr[i] = *reinterpret_cast<const uint4*>(a.k_cache + row + 8 * i);
+    for (int i = 0; i < NLD; ++i)
+      kr[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rk, voff + 16 * i, 0, 0));
 #pragma unroll
-  for (int i = 0; i < NLD; ++i) vr[i] = *reinterpret_cast<const uint4*>(a.v_cache + row + 8 * i);
+    for (int i = 0; i < NLD; ++i)
+      vr[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rv, voff + 16 * i, 0, 0));
+  } else {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) kr[i] = *reinterpret_cast<const uint4*>(a.k_cache + row + 8 * i);
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) vr[i] = *reinterpret_cast<const uint4*>(a.v_cache + row + 8 * i);
+  }
   const float rs = raw ? rsqrtf(ssv * a.inv_k + a.eps) : 1.f;
   const float qscale = a.scale * rs;
   // deferred RoPE (adjacent pairs): angle = pos * freq in fp32, as llama.cpp computes it
-  const float pf = (float)min(max(*a.pos, 0), a.n_ctx - 1);
+  const float pf = (float)min(max(LIVE ? posv : *a.pos, 0), a.n_ctx - 1);
   auto rot = [&](float2 v, float f) {
     if (!drope) return v;
     float sn, cs;
@@ -235,20 +275,22 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
       kvn[tid / (HD / 2)][tid % (HD / 2)] = h2v{(_Float16)(n2.x * rs), (_Float16)(n2.y * rs)};
     }
   }
-  const int L = min(*a.pos + 1, a.n_ctx);
-  LFK_STAMP(0);
-  if (start >= L || a.debug_stop == 1) return;
+  const int L = LIVE ? Lq : min(*a.pos + 1, a.n_ctx);
+  if constexpr (!LIVE) {
+    LFK_STAMP(0);
+    if (start >= L || a.debug_stop == 1) return;
+  }
 
-  const int ns = (L + CH - 1) / CH;
+  const int ns = (L + kb - 1) / kb;
   __syncthreads();  // qs, kvn
   LFK_STAMP(1);
   // the new position (split-K Q|K|V): its cache rows are written here from the LDS copy (this
   // launch's only reader of them is this lane; write-through stores), and its key / value slices
   // replace the speculatively loaded stale rows where they are used - not by writing into the K / V
   // load registers (a conditional overwrite of those made the wave wait for every load first)
-  const bool newkey = a.qkv_raw && key == L - 1;
-  // block-uniform: only the block whose 64 keys hold the new position reads the LDS copies
-  const bool newblk = a.qkv_raw && start <= L - 1 && L - 1 < start + CH;
+  const bool newkey = a.qkv_raw && key == L - 1 && (!LIVE || inr);
+  // block-uniform: only the block whose keys hold the new position reads the LDS copies
+  const bool newblk = a.qkv_raw && start <= L - 1 && L - 1 < start + kb;
   const uint4* kn = reinterpret_cast<const uint4*>(&kvn[0][sub * (DPL / 2)]);
   const uint4* vn = reinterpret_cast<const uint4*>(&kvn[1][sub * (DPL / 2)]);
   if (newkey) {
@@ -256,6 +298,7 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
     const auto rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(a.v_cache), 0, 0x7FFFFFFF, 0x00020000);
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
+      // (LIVE: key = L - 1 < n_ctx here, so `row` is this lane's own row as without it)
       const int off = (int)((row + 8 * i) * sizeof(__half));
       const uint4 kk = kn[i], vv = vn[i];
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, kk), rk, off, 0, 16);  // aux 16: sc1
@@ -268,7 +311,7 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
   }
 
   // ---- 2a. scores
-  const bool valid = key < L;
+  const bool valid = LIVE ? inr : key < L;
   // K row slice as f16 pairs, dotted with f16 q on v_dot2_f32_f16 (f32 accumulate)
   h2v kh[DPL / 2];
 #pragma unroll
@@ -311,7 +354,10 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
   // this wave's V rows (the wave's own keys: a wave barrier, no block barrier)
 #pragma unroll
   for (int i = 0; i < NLD; ++i) {  // (the new position: its value in place of the stale cache row)
-    *reinterpret_cast<uint4*>(&vs[wave][kw][sub * DPL + 8 * i]) = newblk ? sel4(newkey, vn[i], vr[i]) : vr[i];
+    const uint4 v4 = newblk ? sel4(newkey, vn[i], vr[i]) : vr[i];
+    // a lane past the length loaded a row that is not the request's (LIVE: zeros): its weight is 0,
+    // and 0 times a stale row's NaN / Inf must not reach the sum
+    *reinterpret_cast<uint4*>(&vs[wave][kw][sub * DPL + 8 * i]) = LIVE ? v4 : sel4(valid, v4, make_uint4(0, 0, 0, 0));
   }
   LFK_STAMP(2);
   // ---- 2c. P.V over this wave's keys (LDS written by this wave only)

@@ -395,6 +395,13 @@ struct AttnDecodeArgs {
   // (q at 0, k at k_off, v at v_off). Needs rope_freq (the deferred RoPE): the kernel computes
   // rot(q rs + bq) scale, rot(k rs + bk) and v rs + bv. Null: none
   const float* qkv_bias = nullptr;
+  // which keys a block loads (attn_dev.h LIVE). 0: every launched block issues its 64 K / V rows
+  // before the position is known (rows clamped to the cache) and the blocks past the length exit
+  // with them in flight. 1: the position is read first - blocks past the length exit before any
+  // load, lanes past it fetch nothing; same key grouping, bit-identical outputs. 2: as 1, and the
+  // live keys are spread evenly over the launched splits (up to 16 of them, 16 to 64 keys each):
+  // another f32 summation grouping
+  int live = 0;
   static constexpr int kTouchRanges = 6;
   const uint8_t* pf[kTouchRanges] = {};
   size_t pf_bytes[kTouchRanges] = {};

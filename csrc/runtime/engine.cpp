@@ -453,6 +453,7 @@ void Engine::setup_batch_mfma() {
   moe_b_ = att && moe;
   const char* sk = std::getenv("LFK_QKV_SK");
   qkv_sk_ = !(sk && sk[0] == '0');
+  if (const char* e = std::getenv("LFK_ATTN_LIVE")) attn_live_ = std::max(0, std::min(2, std::atoi(e)));  // A/B
   if (const char* sc = std::getenv("LFK_STEP_CLK")) {
     step_clk_layer_ = std::atoi(sc);
     step_clk_ = (long long*)dalloc(sizeof(long long) * 5 * kStepClkBlocks * 16);
@@ -1326,6 +1327,7 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     aa.qkv_bias = L.bqkv;
   }
   aa.dbg_clk = clk_of(l, 1);
+  aa.live = attn_live_;
   // (the batched Wo stays its own launch: in one launch with the attention - Wo planes streaming
   // their weights meanwhile and starting on done counters - the B = 6 step measured 2.42 vs 2.34
   // ms, r4: the in-launch hand-off costs what the boundary did and the weight stream slowed the

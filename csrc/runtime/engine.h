@@ -405,6 +405,11 @@ class Engine : public SlotBackend {
   // attention normalises them and appends the new K / V, the Wo launch re-zeroes both
   // (LFK_QKV_SK=0: the one-part Q|K|V with the RoPE / KV-append epilogue, A/B)
   bool qkv_sk_ = true;
+  // the batched decode attention's key loads (AttnDecodeArgs::live): 0 every launched block loads
+  // its 64 rows before the position is known, 1 only the keys below each row's length are loaded,
+  // 2 those spread evenly over the launched splits (LFK_ATTN_LIVE, A/B: 1 measured 1.926 vs 1.982 ms
+  // per B = 6 step against 0, and 2 1.950 ms, round 9)
+  int attn_live_ = 1;
   bool tp_on_ = false;        // the tensor-parallel code paths (tp_size > 1, or comm=rccl at one rank)
   int layer_end_ = 0;         // layers [opt_.layer_begin, layer_end_) live here
   long long* step_clk_ = nullptr;

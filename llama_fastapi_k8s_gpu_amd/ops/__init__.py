@@ -151,8 +151,11 @@ def embed(W: QuantMatrix, tokens):
     return out
 
 
-def attention_decode(q, k_cache, v_cache, pos: int, scale: Optional[float] = None):
-    """One query token per head against keys [0, pos] of an f16 cache [n_kv, n_ctx, hd]."""
+def attention_decode(q, k_cache, v_cache, pos: int, scale: Optional[float] = None, live: int = 0):
+    """One query token per head against keys [0, pos] of an f16 cache [n_kv, n_ctx, hd].
+
+    live: which keys a block loads (AttnDecodeArgs::live) - 0 all 64 of every launched split, 1 only
+    those below the length, 2 those spread evenly over the launched splits."""
     import torch
     n_kv, n_ctx, hd = map(int, k_cache.shape)
     n_head = int(q.numel()) // hd
@@ -167,7 +170,7 @@ def attention_decode(q, k_cache, v_cache, pos: int, scale: Optional[float] = Non
     p = torch.tensor([pos], device=q.device, dtype=torch.int32)
     out = torch.empty(n_head * hd, device=q.device, dtype=torch.float32)
     hip.attn_decode(qp, kp, vp, p.data_ptr(), n_ctx, n_head, n_kv, hd, scale or hd ** -0.5, part.data_ptr(),
-                    out.data_ptr(), _stream(), cnt.data_ptr())
+                    out.data_ptr(), _stream(), cnt.data_ptr(), live=live)
     return out
 
 

@@ -2,7 +2,12 @@
 // L = 700 keys, head_dim 128, f16 K and V): how fast does the chip pull one layer's 17 MB of
 // K/V when
 //   split : every (row, kv head) is cut into 64-key chunks, one 256-thread block per chunk
-//           (the production attn_decode grid: 528 blocks, 32 KB each), vs
+//           (the live blocks of the attn_decode grid: 528 blocks, 32 KB each), vs
+//   split+dead: the whole grid that production launches, ceil(n_ctx / 64) chunks per (row, kv
+//           head) = 768 blocks - AttnDecodeArgs::live 0, where the 240 blocks past L pull 64 real
+//           cache rows each (clamped to the cache, not to L) and exit with the loads in flight, vs
+//   split+gate: the same 768 blocks, those past L exiting before any load and the lanes past L
+//           fetching nothing (live 1), vs
 //   whole : ONE block per (row, kv head) reads all of its L keys (48 blocks of 1024 threads,
 //           358 KB each; no cross-block merge would be needed), its waves issuing every load
 //           up front, vs
@@ -38,6 +43,29 @@ __global__ __launch_bounds__(256) void split_kernel(const unsigned char* base, u
   for (int i = 0; i < 4; ++i) r[i] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(k) + i);
 #pragma unroll
   for (int i = 0; i < 4; ++i) r[4 + i] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(v) + i);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc ^= r[i];
+  if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x9e3779b9u) out[tid] = acc.x;
+}
+
+// the production grid: ceil(kCtx / 64) chunks. GATE false: every block loads its 64 rows, clamped to
+// the cache; true: the blocks past kL exit first and the lanes past kL fetch nothing
+template <bool GATE>
+__global__ __launch_bounds__(256) void grid_kernel(const unsigned char* base, unsigned* out) {
+  const int kvh = blockIdx.x, chunk = blockIdx.y, b = blockIdx.z;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (GATE && chunk * 64 >= kL) return;
+  const int key0 = chunk * 64 + wave * 16 + (lane >> 2), key = min(key0, kCtx - 1);
+  const unsigned char* k = base + (size_t)b * kSlotBytes + ((size_t)kvh * kCtx + key) * kRowBytes + (lane & 3) * 64;
+  const unsigned char* v = k + (size_t)kB * kSlotBytes;
+  u4 acc = {0, 0, 0, 0};
+  u4 r[8] = {};
+  if (!GATE || key0 < kL) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(k) + i);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[4 + i] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(v) + i);
+  }
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc ^= r[i];
   if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x9e3779b9u) out[tid] = acc.x;
@@ -101,6 +129,14 @@ int main() {
       hipLaunchKernelGGL(split_kernel, dim3(kKV, (kL + 63) / 64, kB), dim3(256), 0, 0, buf + (size_t)i * kLayerBytes, out);
     }, nreg, 64);
     printf("split  (528 blocks x 32 KB)        %7.2f us  %5.2f TB/s\n", t0, mb / t0);
+    const double t0d = timeit([&](int i) {
+      hipLaunchKernelGGL(grid_kernel<false>, dim3(kKV, kCtx / 64, kB), dim3(256), 0, 0, buf + (size_t)i * kLayerBytes, out);
+    }, nreg, 64);
+    printf("split+dead (768 blocks x 32 KB)    %7.2f us  %5.2f TB/s of useful bytes\n", t0d, mb / t0d);
+    const double t0g = timeit([&](int i) {
+      hipLaunchKernelGGL(grid_kernel<true>, dim3(kKV, kCtx / 64, kB), dim3(256), 0, 0, buf + (size_t)i * kLayerBytes, out);
+    }, nreg, 64);
+    printf("split+gate (768 blocks, 528 load)  %7.2f us  %5.2f TB/s\n", t0g, mb / t0g);
     const double t1 = timeit([&](int i) {
       hipLaunchKernelGGL((whole_kernel<1, 3>), dim3(kKV, 1, kB), dim3(1024), 0, 0, buf + (size_t)i * kLayerBytes, out);
     }, nreg, 64);
