@@ -465,21 +465,8 @@ void gemm_rows_scalar(const CpuMat& W, const uint8_t* base, const Q8& xq, int T,
 // y[t][r] (+)= W[r] . x_t for rows r of a (possibly expert-offset) matrix
 void gemm_rows(const CpuMat& W, const uint8_t* base, const Q8& xq, int T, float* y, int ldy, bool add) {
   if (T > 128) throw std::runtime_error("cpu gemm: at most 128 tokens per call");
-  switch (W.type) {
-    case T_Q4_K: return gemm_rows_avx2<T_Q4_K>(W, base, xq, T, y, ldy, add);
-    case T_Q5_K: return gemm_rows_avx2<T_Q5_K>(W, base, xq, T, y, ldy, add);
-    case T_Q6_K: return gemm_rows_avx2<T_Q6_K>(W, base, xq, T, y, ldy, add);
-    case T_Q8_0: return gemm_rows_avx2<T_Q8_0>(W, base, xq, T, y, ldy, add);
-    case T_Q4_0: return gemm_rows_avx2<T_Q4_0>(W, base, xq, T, y, ldy, add);
-    case T_Q4_1: return gemm_rows_avx2<T_Q4_1>(W, base, xq, T, y, ldy, add);
-    case T_Q5_0: return gemm_rows_avx2<T_Q5_0>(W, base, xq, T, y, ldy, add);
-    case T_Q5_1: return gemm_rows_avx2<T_Q5_1>(W, base, xq, T, y, ldy, add);
-    case T_Q2_K: return gemm_rows_avx2<T_Q2_K>(W, base, xq, T, y, ldy, add);
-    case T_Q3_K: return gemm_rows_avx2<T_Q3_K>(W, base, xq, T, y, ldy, add);
-    case T_IQ4_NL: return gemm_rows_avx2<T_IQ4_NL>(W, base, xq, T, y, ldy, add);
-    case T_IQ4_XS: return gemm_rows_avx2<T_IQ4_XS>(W, base, xq, T, y, ldy, add);
-    default: return gemm_rows_scalar(W, base, xq, T, y, ldy, add);
-  }
+  LFK_DISPATCH(LFK_TYPES_QUANT, W.type, gemm_rows_scalar(W, base, xq, T, y, ldy, add),
+               gemm_rows_avx2<QT>(W, base, xq, T, y, ldy, add));
 }
 
 // portable path (F16/F32 and the numerics reference of the AVX2 path)

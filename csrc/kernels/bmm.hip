@@ -580,26 +580,22 @@ __global__ __launch_bounds__(64) void t16_repack_iq4_kernel(QMat w, uint8_t* dst
                  sc[6] | (unsigned)sc[7] << 16);
 }
 
+// the repack kernel of a source type, by family (a template: only the taken branch is instantiated)
+template <int T>
+static auto t16_repack_kernel_of() {
+  if constexpr (is_legacy_v<T>) return t16_repack_legacy_kernel<T>;
+  else if constexpr (is_k23_v<T>) return t16_repack_k23_kernel<T>;
+  else if constexpr (is_iq4_v<T>) return t16_repack_iq4_kernel<T>;
+  else return t16_repack_kernel<T>;
+}
+
 void t16_repack(const QMat& w, uint8_t* dst, hipStream_t st, bool swiglu) {
   if (!bmm_supported(w.type, w.K)) throw std::runtime_error("t16_repack: unsupported type / K");
   if (swiglu && w.rows % 64) throw std::runtime_error("t16_repack: SwiGLU copy needs 32-row gate / up groups");
   const dim3 grid(w.K / 256, (w.rows + 15) / 16);
   const int sw = swiglu ? 1 : 0;
-  switch (w.type) {
-    case T_Q4_K: hipLaunchKernelGGL(t16_repack_kernel<T_Q4_K>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_Q5_K: hipLaunchKernelGGL(t16_repack_kernel<T_Q5_K>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_Q6_K: hipLaunchKernelGGL(t16_repack_kernel<T_Q6_K>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_Q8_0: hipLaunchKernelGGL(t16_repack_kernel<T_Q8_0>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_Q4_0: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q4_0>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_Q4_1: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q4_1>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_Q5_0: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q5_0>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_Q5_1: hipLaunchKernelGGL(t16_repack_legacy_kernel<T_Q5_1>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_Q2_K: hipLaunchKernelGGL(t16_repack_k23_kernel<T_Q2_K>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_Q3_K: hipLaunchKernelGGL(t16_repack_k23_kernel<T_Q3_K>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_IQ4_NL: hipLaunchKernelGGL(t16_repack_iq4_kernel<T_IQ4_NL>, grid, dim3(64), 0, st, w, dst, sw); break;
-    case T_IQ4_XS: hipLaunchKernelGGL(t16_repack_iq4_kernel<T_IQ4_XS>, grid, dim3(64), 0, st, w, dst, sw); break;
-    default: throw std::runtime_error("t16_repack: unsupported type");
-  }
+  LFK_DISPATCH(LFK_TYPES_QUANT, w.type, throw std::runtime_error("t16_repack: unsupported type"),
+               auto k = t16_repack_kernel_of<QT>(); hipLaunchKernelGGL(k, grid, dim3(64), 0, st, w, dst, sw));
 }
 
 // raw loads of lane l's chunk h (8s + 4h + kq) from a tile16 step block (NT: the quant
@@ -1994,7 +1990,7 @@ bool bmm_norm_fits(int K, int B) { return bmm_qkv_fits(K, B) && K == 4096 && B <
 
 bool bmm_supported(int type, int K) {
   const int k = t16_kernel_type(type);  // the legacy 32-block types run as Q4_K / Q5_K
-  if (k != T_Q4_K && k != T_Q5_K && k != T_Q6_K && k != T_Q8_0 && k != T_Q2_K && k != T_Q3_K && k != T_IQ4_XS) return false;
+  if (!LFK_TYPE_IN(LFK_TYPES_T16, k)) return false;
   return K % 256 == 0;  // 256 k per step
 }
 
@@ -2241,26 +2237,13 @@ void bmm(const BmmArgs& a0, hipStream_t s) {
     else if (a.w.type == T_Q4_K && t2 == T_Q5_K) launch_qkv_sk<T_Q4_K, T_Q5_K>(a, s);
     else if (a.w.type == T_Q4_K && t2 == T_Q8_0) launch_qkv_sk<T_Q4_K, T_Q8_0>(a, s);
     else if (t2 != 0) throw std::runtime_error("bmm: split-K Q|K|V type pair");
-    else if (a.w.type == T_Q4_K) launch_qkv_sk<T_Q4_K, 0>(a, s);
-    else if (a.w.type == T_Q5_K) launch_qkv_sk<T_Q5_K, 0>(a, s);
-    else if (a.w.type == T_Q6_K) launch_qkv_sk<T_Q6_K, 0>(a, s);
-    else if (a.w.type == T_Q8_0) launch_qkv_sk<T_Q8_0, 0>(a, s);
-    else if (a.w.type == T_Q2_K) launch_qkv_sk<T_Q2_K, 0>(a, s);
-    else if (a.w.type == T_Q3_K) launch_qkv_sk<T_Q3_K, 0>(a, s);
-    else if (a.w.type == T_IQ4_XS) launch_qkv_sk<T_IQ4_XS, 0>(a, s);
-    else throw std::runtime_error("bmm: unsupported weight type");
+    else {
+      LFK_DISPATCH(LFK_TYPES_T16, a.w.type, throw std::runtime_error("bmm: unsupported weight type"),
+                   launch_qkv_sk<QT, 0>(a, s));
+    }
     return;
   }
-  switch (a.w.type) {
-    case T_Q4_K: launch_bmm<T_Q4_K>(a, s); break;
-    case T_Q5_K: launch_bmm<T_Q5_K>(a, s); break;
-    case T_Q6_K: launch_bmm<T_Q6_K>(a, s); break;
-    case T_Q8_0: launch_bmm<T_Q8_0>(a, s); break;
-    case T_Q2_K: launch_bmm<T_Q2_K>(a, s); break;
-    case T_Q3_K: launch_bmm<T_Q3_K>(a, s); break;
-    case T_IQ4_XS: launch_bmm<T_IQ4_XS>(a, s); break;
-    default: throw std::runtime_error("bmm: unsupported weight type");
-  }
+  LFK_DISPATCH(LFK_TYPES_T16, a.w.type, throw std::runtime_error("bmm: unsupported weight type"), launch_bmm<QT>(a, s));
 }
 
 bool bmm_ffn_chain_supported(const BmmArgs& gu, const BmmArgs& dn) {
@@ -2687,16 +2670,8 @@ void gemm_t16(const GemmT16Args& a, int epi, hipStream_t s) {
     throw std::runtime_error("gemm_t16: output");
   }
   if (reinterpret_cast<uintptr_t>(a.x) % 16) throw std::runtime_error("gemm_t16: X must be 16-byte aligned");
-  switch (t16_kernel_type(a.w.type)) {
-    case T_Q4_K: gemm_t16_epi<T_Q4_K>(a, epi, s); break;
-    case T_Q5_K: gemm_t16_epi<T_Q5_K>(a, epi, s); break;
-    case T_Q6_K: gemm_t16_epi<T_Q6_K>(a, epi, s); break;
-    case T_Q8_0: gemm_t16_epi<T_Q8_0>(a, epi, s); break;
-    case T_Q2_K: gemm_t16_epi<T_Q2_K>(a, epi, s); break;
-    case T_Q3_K: gemm_t16_epi<T_Q3_K>(a, epi, s); break;
-    case T_IQ4_XS: gemm_t16_epi<T_IQ4_XS>(a, epi, s); break;
-    default: throw std::runtime_error("gemm_t16: unsupported weight type");
-  }
+  LFK_DISPATCH(LFK_TYPES_T16, t16_kernel_type(a.w.type), throw std::runtime_error("gemm_t16: unsupported weight type"),
+               gemm_t16_epi<QT>(a, epi, s));
 }
 
 }  // namespace lfk

@@ -255,23 +255,8 @@ void gemm_dq(const GemmArgs& a, int epi, hipStream_t s) {
   if (a.T <= 0) return;
   if (a.w.K % BK) throw std::runtime_error("gemm_dq: K must be a multiple of 64");
   if (epi == GEMM_SWIGLU && (a.w.rows % 64)) throw std::runtime_error("gemm_dq: swiglu needs 64-row groups");
-  switch (a.w.type) {
-    case T_Q4_K: launch_gemm<T_Q4_K>(a, epi, s); break;
-    case T_Q5_K: launch_gemm<T_Q5_K>(a, epi, s); break;
-    case T_Q6_K: launch_gemm<T_Q6_K>(a, epi, s); break;
-    case T_Q8_0: launch_gemm<T_Q8_0>(a, epi, s); break;
-    case T_Q4_0: launch_gemm<T_Q4_0>(a, epi, s); break;
-    case T_Q4_1: launch_gemm<T_Q4_1>(a, epi, s); break;
-    case T_Q5_0: launch_gemm<T_Q5_0>(a, epi, s); break;
-    case T_Q5_1: launch_gemm<T_Q5_1>(a, epi, s); break;
-    case T_Q2_K: launch_gemm<T_Q2_K>(a, epi, s); break;
-    case T_Q3_K: launch_gemm<T_Q3_K>(a, epi, s); break;
-    case T_IQ4_NL: launch_gemm<T_IQ4_NL>(a, epi, s); break;
-    case T_IQ4_XS: launch_gemm<T_IQ4_XS>(a, epi, s); break;
-    case T_F16: launch_gemm<T_F16>(a, epi, s); break;
-    case T_F32: launch_gemm<T_F32>(a, epi, s); break;
-    default: throw std::runtime_error("gemm_dq: unsupported weight type");
-  }
+  LFK_DISPATCH(LFK_TYPES_KERNEL, a.w.type, throw std::runtime_error("gemm_dq: unsupported weight type"),
+               launch_gemm<QT>(a, epi, s));
 }
 
 }  // namespace lfk

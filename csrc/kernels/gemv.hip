@@ -562,7 +562,7 @@ static void launch_gemv_splitk(const GemvArgs& a, hipStream_t s) {
 
 template <int QT, int EPI>
 static void launch_gemv(const GemvArgs& a, hipStream_t s) {
-  if constexpr (EPI == EPI_ADD && (QT == T_Q4_K || QT == T_Q5_K || QT == T_Q6_K || QT == T_Q8_0 || is_legacy_v<QT> || is_k23_v<QT> || is_iq4_v<QT>)) {
+  if constexpr (EPI == EPI_ADD && LFK_TYPE_IN(LFK_TYPES_QUANT, QT)) {
     // (Q3_K too: its 4-row items spill in the 1024-thread form, yet one row per wave without the
     // K split measured slower - llama3-8b-q2_k 2.09 against 1.90 ms per token)
     if (!a.dbg_clk && a.w.K >= 4096 && !a.debug) return launch_gemv_splitk<QT>(a, s);
@@ -589,17 +589,8 @@ static void gemv_t(const GemvArgs& a, int epi, hipStream_t s) {
 #ifdef LFK_GEMV_LEGACY_TU
 // gemv_legacy.hip: the legacy 32-block types' instantiations, compiled beside the rest
 void gemv_legacy(const GemvArgs& a, int epi, hipStream_t s) {
-  switch (a.w.type) {
-    case T_Q4_0: gemv_t<T_Q4_0>(a, epi, s); break;
-    case T_Q4_1: gemv_t<T_Q4_1>(a, epi, s); break;
-    case T_Q5_0: gemv_t<T_Q5_0>(a, epi, s); break;
-    case T_Q5_1: gemv_t<T_Q5_1>(a, epi, s); break;
-    case T_Q2_K: gemv_t<T_Q2_K>(a, epi, s); break;
-    case T_Q3_K: gemv_t<T_Q3_K>(a, epi, s); break;
-    case T_IQ4_NL: gemv_t<T_IQ4_NL>(a, epi, s); break;
-    case T_IQ4_XS: gemv_t<T_IQ4_XS>(a, epi, s); break;
-    default: throw std::runtime_error("gemv: unsupported weight type");
-  }
+  LFK_DISPATCH(LFK_TYPES_GEMV_LEGACY, a.w.type, throw std::runtime_error("gemv: unsupported weight type"),
+               gemv_t<QT>(a, epi, s));
 }
 #else
 void gemv_legacy(const GemvArgs& a, int epi, hipStream_t s);
@@ -608,17 +599,8 @@ void gemv(const GemvArgs& a, int epi, hipStream_t s) {
   if (epi == EPI_SWIGLU && (a.n_out % 32)) throw std::runtime_error("gemv: swiglu features must be a multiple of 32");
   if (a.w.K % 32) throw std::runtime_error("gemv: K must be a multiple of 32");
   if (a.n_out <= 0) return;
-  switch (a.w.type) {
-    case T_Q4_K: gemv_t<T_Q4_K>(a, epi, s); break;
-    case T_Q5_K: gemv_t<T_Q5_K>(a, epi, s); break;
-    case T_Q6_K: gemv_t<T_Q6_K>(a, epi, s); break;
-    case T_Q8_0: gemv_t<T_Q8_0>(a, epi, s); break;
-    case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: case T_IQ4_NL: case T_IQ4_XS:
-      gemv_legacy(a, epi, s); break;
-    case T_F16: gemv_t<T_F16>(a, epi, s); break;
-    case T_F32: gemv_t<T_F32>(a, epi, s); break;
-    default: throw std::runtime_error("gemv: unsupported weight type");
-  }
+  // a type that is not compiled here goes to gemv_legacy.hip, which refuses what it does not have either
+  LFK_DISPATCH(LFK_TYPES_GEMV_MAIN, a.w.type, gemv_legacy(a, epi, s), gemv_t<QT>(a, epi, s));
 }
 #endif  // LFK_GEMV_LEGACY_TU
 
@@ -802,20 +784,16 @@ static void launch_qkv1(QkvLaunch L, int rows, hipStream_t s) {
 
 #ifdef LFK_GEMV_LEGACY_TU
 void gemv_qkv1_legacy(const QkvLaunch& L, int type, int rows, hipStream_t s) {
-  switch (type) {
-    case T_Q4_0: launch_qkv1<T_Q4_0>(L, rows, s); break;
-    case T_Q4_1: launch_qkv1<T_Q4_1>(L, rows, s); break;
-    case T_Q5_0: launch_qkv1<T_Q5_0>(L, rows, s); break;
-    case T_Q5_1: launch_qkv1<T_Q5_1>(L, rows, s); break;
-    case T_Q2_K: launch_qkv1<T_Q2_K>(L, rows, s); break;
-    case T_Q3_K: launch_qkv1<T_Q3_K>(L, rows, s); break;
-    case T_IQ4_NL: launch_qkv1<T_IQ4_NL>(L, rows, s); break;
-    case T_IQ4_XS: launch_qkv1<T_IQ4_XS>(L, rows, s); break;
-    default: throw std::runtime_error("gemv_qkv: unsupported type");
-  }
+  LFK_DISPATCH(LFK_TYPES_GEMV_LEGACY, type, throw std::runtime_error("gemv_qkv: unsupported type"),
+               launch_qkv1<QT>(L, rows, s));
 }
 #else
 void gemv_qkv1_legacy(const QkvLaunch& L, int type, int rows, hipStream_t s);
+
+// one type in the launch (as gemv: what is not compiled here is gemv_legacy.hip's to serve or refuse)
+static void launch_qkv1_any(const QkvLaunch& L, int type, int rows, hipStream_t s) {
+  LFK_DISPATCH(LFK_TYPES_GEMV_MAIN, type, gemv_qkv1_legacy(L, type, rows, s), launch_qkv1<QT>(L, rows, s));
+}
 
 // two type runs in one launch: (2 rows, 2 passes) items for the first run and
 // (2 rows, 1 pass) for the second (keeps the combined kernel near 128 VGPRs)
@@ -858,19 +836,7 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
   for (int i = 0; i < 3; ++i) L.seg[i] = QkvSeg{m[i]->base, m[i]->P, m[i]->rows, i, bias[i]};
   L.nseg = 3;
   auto rows_of = [&](int lo, int hi) { int r = 0; for (int i = lo; i < hi; ++i) r += m[i]->rows; return r; };
-  if (nrun == 1) {
-    switch (run_type[0]) {
-      case T_Q4_K: launch_qkv1<T_Q4_K>(L, rows_of(0, 3), s); return;
-      case T_Q5_K: launch_qkv1<T_Q5_K>(L, rows_of(0, 3), s); return;
-      case T_Q6_K: launch_qkv1<T_Q6_K>(L, rows_of(0, 3), s); return;
-      case T_Q8_0: launch_qkv1<T_Q8_0>(L, rows_of(0, 3), s); return;
-      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: case T_IQ4_NL: case T_IQ4_XS:
-        gemv_qkv1_legacy(L, run_type[0], rows_of(0, 3), s); return;
-      case T_F16: launch_qkv1<T_F16>(L, rows_of(0, 3), s); return;
-      case T_F32: launch_qkv1<T_F32>(L, rows_of(0, 3), s); return;
-      default: throw std::runtime_error("gemv_qkv: unsupported type");
-    }
-  }
+  if (nrun == 1) return launch_qkv1_any(L, run_type[0], rows_of(0, 3), s);
   if (nrun == 2) {
     L.g1 = run_start[1];
     const int r0 = rows_of(0, L.g1), r1 = rows_of(L.g1, 3);
@@ -886,17 +852,7 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
     QkvLaunch Li = L;
     Li.seg[0] = L.seg[i];
     Li.nseg = 1;
-    switch (m[i]->type) {
-      case T_Q4_K: launch_qkv1<T_Q4_K>(Li, m[i]->rows, s); break;
-      case T_Q5_K: launch_qkv1<T_Q5_K>(Li, m[i]->rows, s); break;
-      case T_Q6_K: launch_qkv1<T_Q6_K>(Li, m[i]->rows, s); break;
-      case T_Q8_0: launch_qkv1<T_Q8_0>(Li, m[i]->rows, s); break;
-      case T_Q4_0: case T_Q4_1: case T_Q5_0: case T_Q5_1: case T_Q2_K: case T_Q3_K: case T_IQ4_NL: case T_IQ4_XS:
-        gemv_qkv1_legacy(Li, m[i]->type, m[i]->rows, s); break;
-      case T_F16: launch_qkv1<T_F16>(Li, m[i]->rows, s); break;
-      case T_F32: launch_qkv1<T_F32>(Li, m[i]->rows, s); break;
-      default: throw std::runtime_error("gemv_qkv: unsupported type");
-    }
+    launch_qkv1_any(Li, m[i]->type, m[i]->rows, s);
   }
 }
 
@@ -944,15 +900,8 @@ void gemv_moe_down(const MoeDownArgs& a, hipStream_t s) {
   const int K = a.w.K;
   const size_t lds = (size_t)a.n_slots * (K + (K / 32) * 4) + 64;
   dim3 grid(grid_for((a.w.rows + 1) / 2)), block(256);
-  switch (a.w.type) {
-    case T_Q4_K: hipLaunchKernelGGL(gemv_moe_down_kernel<T_Q4_K>, grid, block, lds, s, a); break;
-    case T_Q5_K: hipLaunchKernelGGL(gemv_moe_down_kernel<T_Q5_K>, grid, block, lds, s, a); break;
-    case T_Q6_K: hipLaunchKernelGGL(gemv_moe_down_kernel<T_Q6_K>, grid, block, lds, s, a); break;
-    case T_Q8_0: hipLaunchKernelGGL(gemv_moe_down_kernel<T_Q8_0>, grid, block, lds, s, a); break;
-    case T_F16: hipLaunchKernelGGL(gemv_moe_down_kernel<T_F16>, grid, block, lds, s, a); break;
-    case T_F32: hipLaunchKernelGGL(gemv_moe_down_kernel<T_F32>, grid, block, lds, s, a); break;
-    default: throw std::runtime_error("moe_down: unsupported type");
-  }
+  LFK_DISPATCH(LFK_TYPES_MOE, a.w.type, throw std::runtime_error("moe_down: unsupported type"),
+               hipLaunchKernelGGL(gemv_moe_down_kernel<QT>, grid, block, lds, s, a));
 }
 
 // ------------------------------------------------------------------ MoE router (one wave)

@@ -32,7 +32,8 @@ __device__ void embed_body(const QMat& e, const int* tokens, int T, float* x) {
 // side job: zero [zero, zero + zero_n) ints (the decode step's done counters, attn_wo1)
 __global__ __launch_bounds__(128) void embed_kernel(QMat e, const int* tokens, int T, float* x, int* zero, int zero_n) {
   for (int i = blockIdx.x * 128 + threadIdx.x; i < zero_n; i += gridDim.x * 128) zero[i] = 0;
-  LFK_DISPATCH_TYPE(e.type, embed_body<QT>(e, tokens, T, x));
+  // wave-uniform; a type outside the list runs nothing here: embed_rows checks it and throws
+  LFK_DISPATCH(LFK_TYPES_KERNEL, e.type, , embed_body<QT>(e, tokens, T, x));
 }
 
 void embed_rows(const QMat& emb, const int* tokens, int T, float* x, hipStream_t s, int* zero, int zero_n) {
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(128) void batch_embed_kernel(QMat e, const int* slo
     tok[b] = token;
     pos[b] = st[S_POS];
   }
-  LFK_DISPATCH_TYPE(e.type, embed_row<QT>(e, token, b, x));
+  LFK_DISPATCH(LFK_TYPES_KERNEL, e.type, , embed_row<QT>(e, token, b, x));  // as embed_kernel
 }
 void batch_gather_embed(const int* slots, int B, const int* state, int* tok, int* pos, const QMat& emb, float* x,
                         hipStream_t s, int* zero, int zero_n, int zero_stride) {
@@ -278,13 +279,7 @@ void fill_random_planar(uint8_t* base, int type, size_t rows, size_t K, float st
   const size_t bytes = qbytes(type, rows, K);
   const Planes P = planes_of(type, rows, K);
   hipLaunchKernelGGL(fill_bytes_kernel, dim3(2048), dim3(256), 0, s, reinterpret_cast<uint32_t*>(base), bytes / 4, seed);
-  size_t nblocks;
-  if (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q2_K || type == T_Q3_K || type == T_IQ4_XS)
-    nblocks = rows * (K / 256);
-  else if (type == T_Q8_0 || type == T_Q4_0 || type == T_Q4_1 || type == T_Q5_0 || type == T_Q5_1 || type == T_IQ4_NL)
-    nblocks = rows * (K / 32);
-  else if (type == T_F16 || type == T_BF16 || type == T_F32) nblocks = rows * K;
-  else throw std::runtime_error("fill_random_planar: unsupported type");
+  const size_t nblocks = rows * (K / type_info(type).block);  // qbytes above has refused an unknown type
   hipLaunchKernelGGL(fix_scales_kernel, dim3(2048), dim3(256), 0, s, base, type, nblocks, P, std, seed + 1);
 }
 

@@ -961,29 +961,4 @@ __device__ __forceinline__ void dq_decode(const DqRaw<T>& r, int q, float* out) 
   }
 }
 
-// Dispatch helper: call F.template operator()<T>() for the runtime type (wave-uniform). A type
-// outside the list runs nothing: host launchers check with dispatchable_type() and throw.
-LFK_HD bool dispatchable_type(int t) {
-  return t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_Q8_0 || t == T_Q4_0 || t == T_Q4_1 || t == T_Q5_0 ||
-         t == T_Q5_1 || t == T_Q2_K || t == T_Q3_K || t == T_IQ4_NL || t == T_IQ4_XS || t == T_F16 || t == T_F32;
-}
-#define LFK_DISPATCH_TYPE(t, ...)                          \
-  switch (t) {                                             \
-    case T_Q4_K: { constexpr int QT = T_Q4_K; __VA_ARGS__; } break; \
-    case T_Q5_K: { constexpr int QT = T_Q5_K; __VA_ARGS__; } break; \
-    case T_Q6_K: { constexpr int QT = T_Q6_K; __VA_ARGS__; } break; \
-    case T_Q8_0: { constexpr int QT = T_Q8_0; __VA_ARGS__; } break; \
-    case T_Q4_0: { constexpr int QT = T_Q4_0; __VA_ARGS__; } break; \
-    case T_Q4_1: { constexpr int QT = T_Q4_1; __VA_ARGS__; } break; \
-    case T_Q5_0: { constexpr int QT = T_Q5_0; __VA_ARGS__; } break; \
-    case T_Q5_1: { constexpr int QT = T_Q5_1; __VA_ARGS__; } break; \
-    case T_Q2_K: { constexpr int QT = T_Q2_K; __VA_ARGS__; } break; \
-    case T_Q3_K: { constexpr int QT = T_Q3_K; __VA_ARGS__; } break; \
-    case T_IQ4_NL: { constexpr int QT = T_IQ4_NL; __VA_ARGS__; } break; \
-    case T_IQ4_XS: { constexpr int QT = T_IQ4_XS; __VA_ARGS__; } break; \
-    case T_F16: { constexpr int QT = T_F16; __VA_ARGS__; } break;   \
-    case T_F32: { constexpr int QT = T_F32; __VA_ARGS__; } break;   \
-    default: break;                                                 \
-  }
-
 }  // namespace lfk

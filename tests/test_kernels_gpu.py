@@ -82,10 +82,13 @@ def test_gemv_swiglu_interleaved(torch, F, K):
     assert rel_err(out.cpu().numpy(), ref) < 1e-3
 
 
-def test_gemv_moe_slots_and_down(torch):
+# The down projection with F % 256 == 0 and a K-quant or Q8_0 runs split-K (moe.hip); F16 / F32 experts,
+# and Q8_0 experts whose F is no multiple of 256, run the per-slot kernel of gemv.hip. (Its Q4_K /
+# Q5_K / Q6_K instantiations take over only past n_slots * F = 65536, which no model here has.)
+@pytest.mark.parametrize("t,F", [(GGMLType.Q4_K, 256), (GGMLType.Q8_0, 288), (GGMLType.F16, 256), (GGMLType.F32, 256)])
+def test_gemv_moe_slots_and_down(torch, t, F):
     rng = np.random.default_rng(9)
-    E, F, K, d = 4, 256, 256, 128
-    t = GGMLType.Q4_K
+    E, K, d = 4, 256, 128
     mats = [(make_matrix(t, F, K, rng), make_matrix(t, F, K, rng)) for _ in range(E)]
     planar = []
     for (rg, Wg), (ru, Wu) in mats:
@@ -160,7 +163,11 @@ def test_moe_router_rows_vs_fp64(torch, E, k, d, B):
 @pytest.mark.parametrize("tq,tk,tv", [(GGMLType.Q4_K, GGMLType.Q4_K, GGMLType.Q6_K),   # two runs, one launch
                                       (GGMLType.Q4_K, GGMLType.Q8_0, GGMLType.Q8_0),
                                       (GGMLType.Q4_K, GGMLType.Q4_K, GGMLType.Q4_K),   # one run
-                                      (GGMLType.Q6_K, GGMLType.Q4_K, GGMLType.Q6_K)])  # three runs: per-segment
+                                      (GGMLType.Q6_K, GGMLType.Q4_K, GGMLType.Q6_K),   # three runs: per-segment
+                                      # one run of each remaining type that has no case in a per-family file
+                                      (GGMLType.Q8_0,) * 3, (GGMLType.F16,) * 3, (GGMLType.F32,) * 3,
+                                      (GGMLType.Q4_0,) * 3, (GGMLType.Q4_1,) * 3, (GGMLType.Q5_0,) * 3,
+                                      (GGMLType.Q5_1,) * 3])
 @pytest.mark.parametrize("K", [512, 8192])   # 8192: the one-CU launch path (K > 4096, 70B)
 def test_gemv_qkv_rope_kvstore(torch, tq, tk, tv, K):
     rng = np.random.default_rng(10)
@@ -907,7 +914,10 @@ def _rope_pairs(y, pos, tab):
 
 
 @pytest.mark.parametrize("types", [(GGMLType.Q4_K,) * 3, (GGMLType.Q4_K, GGMLType.Q4_K, GGMLType.Q6_K),
-                                   (GGMLType.Q4_K, GGMLType.Q8_0, GGMLType.Q8_0)])
+                                   (GGMLType.Q4_K, GGMLType.Q8_0, GGMLType.Q8_0),
+                                   # one run of every other tile16 format
+                                   (GGMLType.Q5_K,) * 3, (GGMLType.Q6_K,) * 3, (GGMLType.Q8_0,) * 3,
+                                   (GGMLType.Q2_K,) * 3, (GGMLType.Q3_K,) * 3, (GGMLType.IQ4_XS,) * 3])
 @pytest.mark.parametrize("B", [1, 6, 8])
 @pytest.mark.parametrize("hd,H,Hkv,K", [(128, 32, 8, 4096), (64, 32, 4, 2048)])
 def test_bmm_qkv_splitk_then_attention(torch, types, B, hd, H, Hkv, K):
