@@ -420,6 +420,92 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("wo"), py::arg("to"), py::arg("Kwo"), py::arg("xa"), py::arg("wg"), py::arg("tg"), py::arg("F"),
      py::arg("K"), py::arg("norm"), py::arg("eps"), py::arg("wd"), py::arg("td"), py::arg("xh"), py::arg("hout"),
      py::arg("resid"), py::arg("B"), py::arg("cnt"), py::arg("stream"), py::arg("tr") = -1);
+  // Q|K|V of a batched decode step as Engine::enqueue_batch_layer launches it when the split-K form
+  // is off (tests/test_qkv_paths_gpu.py): up to three tile16 matrices (base, type, rows) over xh
+  // [B][ldh], or over xf / norm / eps (the folded norm), split into runs of equal tile16 format.
+  // fused: the one-part epilogue (RoPE, q_out, K / V into the slot caches; bias = one f32 vector
+  // laid out as a Q|K|V row, or 0); else the runs accumulate into out [B][ldo] (Q at 0, K at nq,
+  // V at nq + nkv). two_launch: two runs go through bmm_qkv2 if it takes them. Returns whether one
+  // launch served both runs.
+  m.def("bmm_qkv", [](const std::vector<std::tuple<uintptr_t, int, int>>& mats, int K, int B, uintptr_t stream,
+                      uintptr_t xh, int ldh, uintptr_t xf, int ldxf, uintptr_t norm, float eps, bool fused,
+                      uintptr_t out, int ldo, uintptr_t q_out, int q_ld, uintptr_t k_cache, uintptr_t v_cache,
+                      size_t slot_stride, int n_ctx, int head_dim, uintptr_t pos, uintptr_t slots, uintptr_t rope,
+                      uintptr_t bias, bool two_launch) {
+    const int n = (int)mats.size();
+    if (n < 1 || n > 3) throw std::runtime_error("bmm_qkv: 1 to 3 matrices");
+    QMat mt[3];
+    int off[3] = {0, 0, 0};  // first column of each matrix's rows in an out / bias row
+    for (int i = 0; i < n; ++i) {
+      mt[i] = make_qmat(P<void>(std::get<0>(mats[i])), std::get<1>(mats[i]), std::get<2>(mats[i]), K);
+      if (i + 1 < n) off[i + 1] = off[i] + mt[i].rows;
+    }
+    std::vector<BmmArgs> rl;
+    for (int i = 0; i < n;) {
+      int j = i + 1;
+      while (j < n && t16_format(mt[j].type) == t16_format(mt[i].type)) ++j;
+      BmmArgs a;
+      a.w = mt[i]; a.xh = P<__half>(xh); a.ldh = ldh;
+      a.out = P<float>(out) + off[i]; a.ldo = ldo; a.n_out = mt[i].rows; a.B = B;
+      a.nseg = j - i;
+      for (int k = 1; k < a.nseg; ++k) {
+        a.seg_base[k] = mt[i + k].base; a.seg_rows[k] = mt[i + k].rows; a.seg_out[k] = P<float>(out) + off[i + k];
+      }
+      if (xf) {
+        a.xf = P<float>(xf); a.ldxf = ldxf; a.norm_w = P<float>(norm); a.eps = eps;
+      }
+      if (fused) {
+        a.qkv_epi = true;
+        for (int k = 0; k < a.nseg; ++k) a.qkv.kind[k] = i + k;
+        a.qkv.q_out = P<float>(q_out); a.qkv.q_ld = q_ld;
+        a.qkv.k_cache = P<__half>(k_cache); a.qkv.v_cache = P<__half>(v_cache); a.qkv.slot_stride = slot_stride;
+        a.qkv.n_ctx = n_ctx; a.qkv.head_dim = head_dim;
+        a.qkv.pos = P<int>(pos); a.qkv.slots = P<int>(slots); a.qkv.rope = P<float2>(rope);
+        if (bias)
+          for (int k = 0; k < a.nseg; ++k) a.qkv.bias[k] = P<float>(bias) + off[i + k];
+      }
+      rl.push_back(a);
+      i = j;
+    }
+    const bool one = two_launch && rl.size() == 2 && bmm_qkv2(rl[0], rl[1], S(stream));
+    if (!one)
+      for (const BmmArgs& a : rl) bmm(a, S(stream));
+    hip_ok("bmm_qkv");
+    return one;
+  }, py::arg("mats"), py::arg("K"), py::arg("B"), py::arg("stream"), py::arg("xh") = 0, py::arg("ldh") = 0,
+     py::arg("xf") = 0, py::arg("ldxf") = 0, py::arg("norm") = 0, py::arg("eps") = 1e-5f, py::arg("fused") = false,
+     py::arg("out") = 0, py::arg("ldo") = 0, py::arg("q_out") = 0, py::arg("q_ld") = 0, py::arg("k_cache") = 0,
+     py::arg("v_cache") = 0, py::arg("slot_stride") = 0, py::arg("n_ctx") = 0, py::arg("head_dim") = 0,
+     py::arg("pos") = 0, py::arg("slots") = 0, py::arg("rope") = 0, py::arg("bias") = 0,
+     py::arg("two_launch") = true);
+  m.def("bmm_qkv_fits", &bmm_qkv_fits);
+  m.def("rope_kv_prefill", [](uintptr_t qkv, int T, int pos0, int n_q, int n_kv, int head_dim, int n_ctx,
+                              uintptr_t rope, uintptr_t q_out, uintptr_t k_cache, uintptr_t v_cache, uintptr_t stream,
+                              uintptr_t pos_arr, uintptr_t slot_arr, size_t slot_stride, uintptr_t bias) {
+    rope_kv_prefill(P<float>(qkv), T, pos0, n_q, n_kv, head_dim, n_ctx, P<float2>(rope), P<float>(q_out),
+                    P<__half>(k_cache), P<__half>(v_cache), S(stream), P<int>(pos_arr), P<int>(slot_arr), slot_stride,
+                    P<float>(bias));
+    hip_ok("rope_kv_prefill");
+  }, py::arg("qkv"), py::arg("T"), py::arg("pos0"), py::arg("n_q"), py::arg("n_kv"), py::arg("head_dim"),
+     py::arg("n_ctx"), py::arg("rope"), py::arg("q_out"), py::arg("k_cache"), py::arg("v_cache"), py::arg("stream"),
+     py::arg("pos_arr") = 0, py::arg("slot_arr") = 0, py::arg("slot_stride") = 0, py::arg("bias") = 0);
+  m.def("state_layout", []() { return std::make_tuple((int)S_NSTATE, (int)S_TOKEN, (int)S_POS); });
+  m.def("batch_gather", [](uintptr_t slots, int B, uintptr_t state, uintptr_t tok, uintptr_t pos, uintptr_t stream,
+                           uintptr_t zero, int zero_n, int zero_stride) {
+    batch_gather(P<int>(slots), B, P<int>(state), P<int>(tok), P<int>(pos), S(stream), P<int>(zero), zero_n,
+                 zero_stride);
+    hip_ok("batch_gather");
+  }, py::arg("slots"), py::arg("B"), py::arg("state"), py::arg("tok"), py::arg("pos"), py::arg("stream"),
+     py::arg("zero") = 0, py::arg("zero_n") = 0, py::arg("zero_stride") = 1);
+  m.def("batch_gather_embed", [](uintptr_t slots, int B, uintptr_t state, uintptr_t tok, uintptr_t pos, uintptr_t w,
+                                 int type, int V, int d, uintptr_t x, uintptr_t stream, uintptr_t zero, int zero_n,
+                                 int zero_stride) {
+    batch_gather_embed(P<int>(slots), B, P<int>(state), P<int>(tok), P<int>(pos), make_qmat(P<void>(w), type, V, d),
+                       P<float>(x), S(stream), P<int>(zero), zero_n, zero_stride);
+    hip_ok("batch_gather_embed");
+  }, py::arg("slots"), py::arg("B"), py::arg("state"), py::arg("tok"), py::arg("pos"), py::arg("w"), py::arg("type"),
+     py::arg("V"), py::arg("d"), py::arg("x"), py::arg("stream"), py::arg("zero") = 0, py::arg("zero_n") = 0,
+     py::arg("zero_stride") = 1);
   m.def("bmm_norm_fits", &bmm_norm_fits);
   m.def("bmm_supported", &bmm_supported);
   m.def("t16_bytes", &t16_bytes);

@@ -5,6 +5,7 @@ import pytest
 
 from llama_fastapi_k8s_gpu_amd.gguf.constants import GGMLType
 from gpu_helpers import dev_bytes, hip, make_matrix, q8_emulate, rel_err, rmsnorm, stream, to_planar
+from qkv_ref import _rope_pairs, _rope_table
 
 pytestmark = pytest.mark.gpu
 
@@ -897,20 +898,6 @@ def test_rmsnorm_f16_swizzled(torch):
     xf = x.cpu().double()
     ref = (xf / torch.sqrt((xf * xf).mean(1, keepdim=True) + 1e-5) * w.cpu().double()).numpy()
     assert rel_err(_swizzle4(y.float().cpu().numpy()), ref) < 1e-3
-
-
-def _rope_table(n_ctx, hd, theta=5e5):
-    inv = theta ** (-np.arange(0, hd, 2, dtype=np.float64) / hd)
-    ang = np.arange(n_ctx, dtype=np.float64)[:, None] * inv[None, :]
-    return np.stack([np.cos(ang), np.sin(ang)], -1).astype(np.float32)   # [n_ctx][hd/2][2]
-
-
-def _rope_pairs(y, pos, tab):
-    """RoPE on adjacent pairs (GGUF normal mode) of y [rows] at position pos, rows % hd per head."""
-    hd2 = tab.shape[1]
-    z = y.reshape(-1, hd2, 2).astype(np.float64)
-    c, s = tab[pos, :, 0].astype(np.float64), tab[pos, :, 1].astype(np.float64)
-    return np.stack([z[..., 0] * c - z[..., 1] * s, z[..., 0] * s + z[..., 1] * c], -1).reshape(y.shape)
 
 
 @pytest.mark.parametrize("types", [(GGMLType.Q4_K,) * 3, (GGMLType.Q4_K, GGMLType.Q4_K, GGMLType.Q6_K),
