@@ -356,12 +356,17 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("swiglu_group") = 32);
   m.def("bmm", [](uintptr_t w, int type, int rows, int K, uintptr_t xh, int ldh, uintptr_t out, int ldo, int B,
                   uintptr_t stream, int debug, uintptr_t h_out, int ldh_out, uintptr_t xf, int ldxf,
-                  uintptr_t norm, float eps, bool store_out, uintptr_t dbg_clk, int tr) {
+                  uintptr_t norm, float eps, bool store_out, uintptr_t dbg_clk, int tr, uintptr_t ew, int ew_ld,
+                  int tiles_per_expert, int steps_per_expert, uintptr_t zero, int zero_n) {
     BmmArgs a;
     a.debug = debug;
     a.tr = tr;
     a.dbg_clk = P<long long>(dbg_clk);
     a.w = make_qmat(P<void>(w), type, rows, K);
+    // MoE experts as one matrix (tests/test_moe_paths_gpu.py): routing weights ew [B][ew_ld], the
+    // stacked gate/up's tiles per expert or the K-concatenated down's steps per expert
+    a.ew = P<float>(ew); a.ew_ld = ew_ld; a.tiles_per_expert = tiles_per_expert; a.steps_per_expert = steps_per_expert;
+    a.zero = P<float>(zero); a.zero_n = zero_n;
     a.xh = P<__half>(xh); a.ldh = ldh; a.out = P<float>(out); a.ldo = ldo; a.n_out = rows; a.B = B;
     if (h_out) {  // SwiGLU epilogue (gate/up rows in 32-row groups)
       a.swiglu_epi = true; a.h_out = P<__half>(h_out); a.ldh_out = ldh_out;
@@ -375,7 +380,9 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("w"), py::arg("type"), py::arg("rows"), py::arg("K"), py::arg("xh"), py::arg("ldh"), py::arg("out"),
      py::arg("ldo"), py::arg("B"), py::arg("stream"), py::arg("debug") = 0, py::arg("h_out") = 0,
      py::arg("ldh_out") = 0, py::arg("xf") = 0, py::arg("ldxf") = 0, py::arg("norm") = 0, py::arg("eps") = 1e-5f,
-     py::arg("store_out") = false, py::arg("dbg_clk") = 0, py::arg("tr") = -1);
+     py::arg("store_out") = false, py::arg("dbg_clk") = 0, py::arg("tr") = -1, py::arg("ew") = 0,
+     py::arg("ew_ld") = 0, py::arg("tiles_per_expert") = 0, py::arg("steps_per_expert") = 0, py::arg("zero") = 0,
+     py::arg("zero_n") = 0);
   // the gate/up + down chain in one launch (tests/test_kernels_gpu.py::test_bmm_ffn_chain_*): gate/up
   // rows in the SwiGLU tile16 copy (wg, 2F x K), down (wd, K x F) over the f16 SwiGLU output hout
   // [B][F]; out [B][K] accumulates; cnt >= 64 ints, zeroed by the caller
@@ -575,15 +582,35 @@ PYBIND11_MODULE(_hip, m) {
   });
 
   m.def("gemm", [](uintptr_t w, int type, int rows, int K, uintptr_t x, int T, uintptr_t out, uintptr_t out_bf16,
-                   int ldo, int epi, uintptr_t stream, uintptr_t resid) {
+                   int ldo, int epi, uintptr_t stream, uintptr_t resid, uintptr_t seg_dev, int rows_hint,
+                   bool out_zeroed) {
     GemmArgs a;
+    a.seg_dev = P<int>(seg_dev); a.rows_hint = rows_hint; a.out_zeroed = out_zeroed;  // grouped (MoE) form
     a.w = make_qmat(P<void>(w), type, rows, K);
     a.x = P<__hip_bfloat16>(x); a.T = T; a.out = P<float>(out); a.out_bf16 = P<__hip_bfloat16>(out_bf16);
     a.ldo = ldo; a.resid = P<float>(resid);
     gemm_dq(a, epi, S(stream));
     hip_ok("gemm");
   }, py::arg("w"), py::arg("type"), py::arg("rows"), py::arg("K"), py::arg("x"), py::arg("T"), py::arg("out"),
-     py::arg("out_bf16"), py::arg("ldo"), py::arg("epi"), py::arg("stream"), py::arg("resid") = 0);
+     py::arg("out_bf16"), py::arg("ldo"), py::arg("epi"), py::arg("stream"), py::arg("resid") = 0,
+     py::arg("seg_dev") = 0, py::arg("rows_hint") = 0, py::arg("out_zeroed") = false);
+
+  // MoE prefill routing and data movement (tests/test_moe_paths_gpu.py)
+  m.def("moe_route_group", [](uintptr_t logits, int T, int E, int k, uintptr_t sel, uintptr_t selw, uintptr_t cnt_off,
+                              uintptr_t tok, uintptr_t gw, uintptr_t pos, uintptr_t stream) {
+    moe_route_group(P<float>(logits), T, E, k, P<int>(sel), P<float>(selw), P<int>(cnt_off), P<int>(tok), P<float>(gw),
+                    P<int>(pos), S(stream));
+    hip_ok("moe_route_group");
+  });
+  m.def("gather_rows", [](uintptr_t src, uintptr_t tok, int n_rows, int d, uintptr_t dst, uintptr_t stream) {
+    gather_rows_bf16(P<__hip_bfloat16>(src), P<int>(tok), n_rows, d, P<__hip_bfloat16>(dst), S(stream));
+    hip_ok("gather_rows");
+  });
+  m.def("moe_scatter_add", [](uintptr_t acc, uintptr_t y, uintptr_t pos, uintptr_t gw, int T, int k, int d,
+                              uintptr_t stream) {
+    moe_scatter_add(P<float>(acc), P<float>(y), P<int>(pos), P<float>(gw), T, k, d, S(stream));
+    hip_ok("moe_scatter_add");
+  });
 
   m.def("moe_router_rows", [](uintptr_t x, int ldx, int B, uintptr_t nw, float eps, uintptr_t W, int d, int E, int k,
                               uintptr_t wd, int ld, uintptr_t stream) {
@@ -620,8 +647,12 @@ PYBIND11_MODULE(_hip, m) {
 
   m.def("gemm_t16", [](uintptr_t w, int type, int rows, int K, uintptr_t x, int T, uintptr_t out, int ldo,
                        uintptr_t out_h, int ldh, int epi, uintptr_t stream, uintptr_t resid, int cfg,
-                       std::vector<std::pair<uintptr_t, int>> wseg) {
+                       std::vector<std::pair<uintptr_t, int>> wseg, uintptr_t seg_dev, int rows_hint, bool out_zeroed,
+                       size_t tile_stride, int step0) {
     GemmT16Args a;
+    // grouped (MoE) form, and a matrix inside a wider tile16 copy (the K-concatenated down)
+    a.seg_dev = P<int>(seg_dev); a.rows_hint = rows_hint; a.out_zeroed = out_zeroed;
+    a.tile_stride = tile_stride; a.step0 = step0;
     a.w = make_qmat(P<void>(w), type, rows, K);
     a.x = P<__half>(x); a.T = T; a.out = P<float>(out); a.ldo = ldo; a.resid = P<float>(resid);
     a.out_h = P<__half>(out_h); a.ldh = ldh; a.cfg = cfg;
@@ -637,7 +668,8 @@ PYBIND11_MODULE(_hip, m) {
     hip_ok("gemm_t16");
   }, py::arg("w"), py::arg("type"), py::arg("rows"), py::arg("K"), py::arg("x"), py::arg("T"), py::arg("out"),
      py::arg("ldo"), py::arg("out_h"), py::arg("ldh"), py::arg("epi"), py::arg("stream"), py::arg("resid") = 0,
-     py::arg("cfg") = 0, py::arg("wseg") = std::vector<std::pair<uintptr_t, int>>{});
+     py::arg("cfg") = 0, py::arg("wseg") = std::vector<std::pair<uintptr_t, int>>{}, py::arg("seg_dev") = 0,
+     py::arg("rows_hint") = 0, py::arg("out_zeroed") = false, py::arg("tile_stride") = 0, py::arg("step0") = 0);
 
   m.def("attn_decode", [](uintptr_t q, uintptr_t kc, uintptr_t vc, uintptr_t pos, int n_ctx, int n_head, int n_kv,
                           int hd, float scale, uintptr_t part, uintptr_t out, uintptr_t stream, uintptr_t counters,

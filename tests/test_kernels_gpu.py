@@ -85,7 +85,9 @@ def test_gemv_swiglu_interleaved(torch, F, K):
 
 # The down projection with F % 256 == 0 and a K-quant or Q8_0 runs split-K (moe.hip); F16 / F32 experts,
 # and Q8_0 experts whose F is no multiple of 256, run the per-slot kernel of gemv.hip. (Its Q4_K /
-# Q5_K / Q6_K instantiations take over only past n_slots * F = 65536, which no model here has.)
+# Q5_K / Q6_K instantiations take over only past n_slots * F = 65536, which no model here has:
+# test_moe_paths_gpu.py::test_moe_down_per_slot_kquants runs them, and test_moe_down_splitk_parts the
+# split-K form with more than one K part, F > 2048.)
 @pytest.mark.parametrize("t,F", [(GGMLType.Q4_K, 256), (GGMLType.Q8_0, 288), (GGMLType.F16, 256), (GGMLType.F32, 256)])
 def test_gemv_moe_slots_and_down(torch, t, F):
     rng = np.random.default_rng(9)
