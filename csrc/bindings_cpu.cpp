@@ -242,6 +242,7 @@ PYBIND11_MODULE(_cpu, m) {
         d["n_expert"] = h.n_expert; d["n_expert_used"] = h.n_expert_used;
         d["rope_base"] = h.rope_base; d["rms_eps"] = h.rms_eps;
         d["arch"] = h.arch; d["rope_neox"] = h.rope_neox; d["qkv_bias"] = h.qkv_bias;
+        d["qk_norm"] = h.qk_norm;
         return d;
       })
       .def_property_readonly("n_vocab", &CpuEngine::n_vocab)

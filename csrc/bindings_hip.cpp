@@ -279,6 +279,7 @@ PYBIND11_MODULE(_hip, m) {
         d["n_expert"] = h.n_expert; d["n_expert_used"] = h.n_expert_used;
         d["rope_base"] = h.rope_base; d["rms_eps"] = h.rms_eps;
         d["arch"] = h.arch; d["rope_neox"] = h.rope_neox; d["qkv_bias"] = h.qkv_bias;
+        d["qk_norm"] = h.qk_norm;
         return d;
       });
 
@@ -496,6 +497,20 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("qkv"), py::arg("T"), py::arg("pos0"), py::arg("n_q"), py::arg("n_kv"), py::arg("head_dim"),
      py::arg("n_ctx"), py::arg("rope"), py::arg("q_out"), py::arg("k_cache"), py::arg("v_cache"), py::arg("stream"),
      py::arg("pos_arr") = 0, py::arg("slot_arr") = 0, py::arg("slot_stride") = 0, py::arg("bias") = 0);
+  // QK-norm models (qwen3): head norm + RoPE + KV append of projection rows [T][n_q + 2 n_kv];
+  // qk_norm = [q_norm | k_norm] (2 head_dim floats). pos_dev: T = 1 at the position read from the device
+  m.def("qk_norm_rope_kv", [](uintptr_t qkv, int T, int pos0, int n_q, int n_kv, int head_dim, int n_ctx,
+                              uintptr_t rope, uintptr_t qk_norm, float eps, uintptr_t q_out, uintptr_t k_cache,
+                              uintptr_t v_cache, uintptr_t stream, uintptr_t pos_arr, uintptr_t slot_arr,
+                              size_t slot_stride, uintptr_t pos_dev) {
+    qk_norm_rope_kv(P<float>(qkv), T, pos0, n_q, n_kv, head_dim, n_ctx, P<float2>(rope), P<float>(qk_norm), eps,
+                    P<float>(q_out), P<__half>(k_cache), P<__half>(v_cache), S(stream), P<int>(pos_arr),
+                    P<int>(slot_arr), slot_stride, P<int>(pos_dev));
+    hip_ok("qk_norm_rope_kv");
+  }, py::arg("qkv"), py::arg("T"), py::arg("pos0"), py::arg("n_q"), py::arg("n_kv"), py::arg("head_dim"),
+     py::arg("n_ctx"), py::arg("rope"), py::arg("qk_norm"), py::arg("eps"), py::arg("q_out"), py::arg("k_cache"),
+     py::arg("v_cache"), py::arg("stream"), py::arg("pos_arr") = 0, py::arg("slot_arr") = 0,
+     py::arg("slot_stride") = 0, py::arg("pos_dev") = 0);
   m.def("state_layout", []() { return std::make_tuple((int)S_NSTATE, (int)S_TOKEN, (int)S_POS); });
   m.def("batch_gather", [](uintptr_t slots, int B, uintptr_t state, uintptr_t tok, uintptr_t pos, uintptr_t stream,
                            uintptr_t zero, int zero_n, int zero_stride) {
@@ -551,8 +566,9 @@ PYBIND11_MODULE(_hip, m) {
   m.def("gemv_qkv", [](uintptr_t wq, int tq, uintptr_t wk, int tk, uintptr_t wv, int tv, int nq, int nkv, int K,
                        uintptr_t x, uintptr_t norm, float eps, uintptr_t q_out, uintptr_t kc, uintptr_t vc, int n_ctx,
                        int hd, uintptr_t pos, uintptr_t rope, uintptr_t stream, uintptr_t bq, uintptr_t bk,
-                       uintptr_t bv) {
+                       uintptr_t bv, uintptr_t raw_out) {
     QkvArgs a;
+    a.raw_out = P<float>(raw_out);  // the raw-sum form of the QK-norm models: [nq | nkv | nkv] f32, nothing else written
     a.bq = P<float>(bq); a.bk = P<float>(bk); a.bv = P<float>(bv);
     a.wq = make_qmat(P<void>(wq), tq, nq, K);
     a.wk = make_qmat(P<void>(wk), tk, nkv, K);
@@ -565,7 +581,7 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("wq"), py::arg("tq"), py::arg("wk"), py::arg("tk"), py::arg("wv"), py::arg("tv"), py::arg("nq"),
      py::arg("nkv"), py::arg("K"), py::arg("x"), py::arg("norm"), py::arg("eps"), py::arg("q_out"), py::arg("kc"),
      py::arg("vc"), py::arg("n_ctx"), py::arg("hd"), py::arg("pos"), py::arg("rope"), py::arg("stream"),
-     py::arg("bq") = 0, py::arg("bk") = 0, py::arg("bv") = 0);
+     py::arg("bq") = 0, py::arg("bk") = 0, py::arg("bv") = 0, py::arg("raw_out") = 0);
 
   m.def("moe_down", [](uintptr_t w, int type, int rows, int K, size_t expert_stride, uintptr_t h, uintptr_t ids,
                        uintptr_t ew, int n_slots, uintptr_t out, uintptr_t stream) {
@@ -675,8 +691,10 @@ PYBIND11_MODULE(_hip, m) {
                           int hd, float scale, uintptr_t part, uintptr_t out, uintptr_t stream, uintptr_t counters,
                           int debug_stop, uintptr_t dbg_clk, int batch, uintptr_t slots, size_t slot_stride,
                           uintptr_t out_h, uintptr_t qkv_raw, size_t qkv_ld, size_t k_off, size_t v_off, uintptr_t ss,
-                          float inv_k, float eps, uintptr_t rope_freq, uintptr_t qkv_bias, int live) {
+                          float inv_k, float eps, uintptr_t rope_freq, uintptr_t qkv_bias, int live, uintptr_t qk_norm,
+                          float qkn_eps) {
     AttnDecodeArgs a;
+    a.qk_norm = P<float>(qk_norm); a.qkn_eps = qkn_eps;
     a.live = live;
     a.qkv_bias = P<float>(qkv_bias);
     a.rope_freq = P<float>(rope_freq);
@@ -701,7 +719,8 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("debug_stop") = 0, py::arg("dbg_clk") = 0, py::arg("batch") = 0, py::arg("slots") = 0,
      py::arg("slot_stride") = 0, py::arg("out_h") = 0, py::arg("qkv_raw") = 0, py::arg("qkv_ld") = 0,
      py::arg("k_off") = 0, py::arg("v_off") = 0, py::arg("ss") = 0, py::arg("inv_k") = 0.f, py::arg("eps") = 1e-5f,
-     py::arg("rope_freq") = 0, py::arg("qkv_bias") = 0, py::arg("live") = 0);
+     py::arg("rope_freq") = 0, py::arg("qkv_bias") = 0, py::arg("live") = 0, py::arg("qk_norm") = 0,
+     py::arg("qkn_eps") = 1e-6f);
   // split-K Q|K|V (BmmArgs::qkv_sk) over tile16 copies: RoPE'd partial sums added into out [B][ldo]
   // (Q at 0, K at nq, V at nq + nkv), the rows' sums of squares into ss_out [B]
   m.def("bmm_qkv_sk", [](uintptr_t wq, int tq, int nq, uintptr_t wk, int tk, uintptr_t wv, int tv, int nkv, int K,

@@ -626,6 +626,17 @@ CpuEngine::CpuEngine(const std::string& path, const CpuOptions& o)
       L.bk = slice("attn_k.bias", sp_.kv_row0(), sp_.nkvd, true);
       L.bv = slice("attn_v.bias", sp_.kv_row0(), sp_.nkvd, false);
     }
+    if (hp_.qk_norm) {  // [head_dim] each, permuted with the map of the q / k rows (as on the GPU)
+      auto head_w = [&](const char* nm) {
+        const std::vector<float> all = load_f32(f, p + nm);
+        if ((int)all.size() != head_dim_) throw std::runtime_error(p + nm + ": expected [head_dim]");
+        std::vector<float> o(all.size());
+        for (size_t r = 0; r < o.size(); ++r) o[r] = all[neox ? neox_src_row(r, neox) : r];
+        return o;
+      };
+      L.q_norm = head_w("attn_q_norm.weight");
+      L.k_norm = head_w("attn_k_norm.weight");
+    }
     L.wv = load_mat(f, p + "attn_v.weight", 0, sp_.kv_row0(), sp_.nkvd);
     L.wo = load_mat(f, p + "attn_output.weight", 0, 0, -1, sp_.q_row0(), sp_.nq);
     if (n_expert_ > 0) {
@@ -806,6 +817,20 @@ void CpuEngine::run_layers(float* x, int T, int pos0, int l0, int l1) {
           k[(size_t)t * nkv + i] += L.bk[i];
           v[(size_t)t * nkv + i] += L.bv[i];
         }
+      }
+    }
+    if (!L.q_norm.empty()) {  // QK-norm (qwen3): RMSNorm over each q and k head, before the rotation
+      auto headnorm = [&](float* r, int n, const std::vector<float>& w) {
+        for (int h0 = 0; h0 < n; h0 += hd) {
+          float ss = 0.f;
+          for (int i = 0; i < hd; ++i) ss += r[h0 + i] * r[h0 + i];
+          const float sc = 1.f / std::sqrt(ss / (float)hd + eps_);
+          for (int i = 0; i < hd; ++i) r[h0 + i] *= sc * w[i];
+        }
+      };
+      for (int t = 0; t < T; ++t) {
+        headnorm(q.data() + (size_t)t * nq, nq, L.q_norm);
+        headnorm(k.data() + (size_t)t * nkv, nkv, L.k_norm);
       }
     }
     for (int t = 0; t < T; ++t) {

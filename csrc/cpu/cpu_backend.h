@@ -30,6 +30,7 @@ struct CpuMat {
 struct CpuLayer {
   std::vector<float> attn_norm, ffn_norm;
   std::vector<float> bq, bk, bv;  // Q|K|V biases of this rank's rows (qwen2; empty: none)
+  std::vector<float> q_norm, k_norm;  // QK-norm weights [head_dim], pair-permuted (qwen3; empty: none)
   CpuMat wq, wk, wv, wo, w_gu, w_down, router, gu_exps, down_exps;
 };
 

@@ -19,31 +19,38 @@
 
 namespace lfk {
 
-template <int HD, int G, bool TL, bool BIAS = false, bool LIVE = false>
+template <int HD, int G, bool TL, bool BIAS = false, bool LIVE = false, bool QKNORM = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(AttnDecodeArgs a) {
-  attn_decode_body<HD, G, TL, BIAS, LIVE>(a);
+  attn_decode_body<HD, G, TL, BIAS, LIVE, QKNORM>(a);
 }
 
 size_t attn_decode_workspace_floats(int n_ctx, int n_head, int head_dim) {
   return (size_t)((n_ctx + CH - 1) / CH) * n_head * (head_dim + 2);
 }
 
-template <int HD, bool TL, bool BIAS = false, bool LIVE = false>
+template <int HD, bool TL, bool BIAS = false, bool LIVE = false, bool QKNORM = false>
 static void launch_attn_decode_tl(const AttnDecodeArgs& a, int G, dim3 grid, hipStream_t s) {
   switch (G) {
-    case 1: hipLaunchKernelGGL((attn_decode_kernel<HD, 1, TL, BIAS, LIVE>), grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((attn_decode_kernel<HD, 2, TL, BIAS, LIVE>), grid, dim3(256), 0, s, a); break;
-    case 3: hipLaunchKernelGGL((attn_decode_kernel<HD, 3, TL, BIAS, LIVE>), grid, dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((attn_decode_kernel<HD, 4, TL, BIAS, LIVE>), grid, dim3(256), 0, s, a); break;
-    case 5: hipLaunchKernelGGL((attn_decode_kernel<HD, 5, TL, BIAS, LIVE>), grid, dim3(256), 0, s, a); break;
-    case 6: hipLaunchKernelGGL((attn_decode_kernel<HD, 6, TL, BIAS, LIVE>), grid, dim3(256), 0, s, a); break;
-    case 7: hipLaunchKernelGGL((attn_decode_kernel<HD, 7, TL, BIAS, LIVE>), grid, dim3(256), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((attn_decode_kernel<HD, 8, TL, BIAS, LIVE>), grid, dim3(256), 0, s, a); break;
+    case 1: hipLaunchKernelGGL((attn_decode_kernel<HD, 1, TL, BIAS, LIVE, QKNORM>), grid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((attn_decode_kernel<HD, 2, TL, BIAS, LIVE, QKNORM>), grid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL((attn_decode_kernel<HD, 3, TL, BIAS, LIVE, QKNORM>), grid, dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((attn_decode_kernel<HD, 4, TL, BIAS, LIVE, QKNORM>), grid, dim3(256), 0, s, a); break;
+    case 5: hipLaunchKernelGGL((attn_decode_kernel<HD, 5, TL, BIAS, LIVE, QKNORM>), grid, dim3(256), 0, s, a); break;
+    case 6: hipLaunchKernelGGL((attn_decode_kernel<HD, 6, TL, BIAS, LIVE, QKNORM>), grid, dim3(256), 0, s, a); break;
+    case 7: hipLaunchKernelGGL((attn_decode_kernel<HD, 7, TL, BIAS, LIVE, QKNORM>), grid, dim3(256), 0, s, a); break;
+    case 8: hipLaunchKernelGGL((attn_decode_kernel<HD, 8, TL, BIAS, LIVE, QKNORM>), grid, dim3(256), 0, s, a); break;
     default: throw std::runtime_error("attn_decode: gqa group must be 1 to 8");
   }
 }
 template <int HD>
 static void launch_attn_decode(const AttnDecodeArgs& a, int G, dim3 grid, hipStream_t s) {
+  if (a.qk_norm) {  // QK-norm (qwen3): its own kernels, every LIVE mode, with and without the timeline
+    if (a.live && a.dbg_clk) launch_attn_decode_tl<HD, true, false, true, true>(a, G, grid, s);
+    else if (a.live) launch_attn_decode_tl<HD, false, false, true, true>(a, G, grid, s);
+    else if (a.dbg_clk) launch_attn_decode_tl<HD, true, false, false, true>(a, G, grid, s);
+    else launch_attn_decode_tl<HD, false, false, false, true>(a, G, grid, s);
+    return;
+  }
   if (a.live) {  // (AttnDecodeArgs::live 1 and 2 share a kernel: the key spread is launch-uniform)
     if (a.qkv_bias && a.dbg_clk) launch_attn_decode_tl<HD, true, true, true>(a, G, grid, s);
     else if (a.qkv_bias) launch_attn_decode_tl<HD, false, true, true>(a, G, grid, s);
@@ -75,6 +82,8 @@ void attn_decode(const AttnDecodeArgs& a, hipStream_t s) {
     throw std::runtime_error("attn_decode: split-K Q|K|V arguments");
   if (a.qkv_bias && (!a.qkv_raw || !a.rope_freq))
     throw std::runtime_error("attn_decode: Q|K|V biases need the raw sums with the RoPE deferred");
+  if (a.qk_norm && (!a.qkv_raw || !a.rope_freq || a.qkv_bias))
+    throw std::runtime_error("attn_decode: QK-norm needs the raw sums with the RoPE deferred, and no biases");
   if (a.done) throw std::runtime_error("attn_decode: done counters are attn_wo1's (gemv.hip)");
   if (a.live < 0 || a.live > 2) throw std::runtime_error("attn_decode: live must be 0, 1 or 2");
   // z: the rows (batched) or one; the weight-touch plane, if any, is the next z index

@@ -94,8 +94,13 @@ __device__ __forceinline__ float rows_sum(float v) {
 // any load and the lanes past it fetch nothing (buffer loads, the offset out of range: 0 comes back
 // with no memory request). live 2 also spreads the keys evenly over the launched splits. A kernel
 // of its own, like BIAS: without it the K / V rows go out before the position is known.
-template <int HD, int G, bool TL, bool BIAS = false, bool LIVE = false>
+// QKNORM (AttnDecodeArgs::qk_norm, qwen3): q and the new key get an RMSNorm over their head between
+// the row scale and the rotation. A q head is the pairs of one wave (HD 128) or half a wave (HD 64),
+// the new key the pairs of threads 0 .. HD/2 - 1, so the head's sum of squares is a shuffle
+// reduction. A kernel of its own, like BIAS.
+template <int HD, int G, bool TL, bool BIAS = false, bool LIVE = false, bool QKNORM = false>
 __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
+  static_assert(!(BIAS && QKNORM), "no model has both");
   constexpr int DPL = HD / 4;   // dims per lane in QK
   constexpr int NLD = DPL / 8;  // 16-B loads per lane per K (or V) row
   constexpr int KPW = 16;       // keys per wave
@@ -115,6 +120,7 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
                "s"(a.slot_stride), "s"(a.q_stride), "s"(a.out_stride), "s"(a.part_stride), "s"(a.out_h),
                "s"(a.out_h_stride), "s"(a.done), "s"(a.qkv_raw), "s"(a.qkv_ld), "s"(a.k_off), "s"(a.v_off), "s"(a.ss),
                "s"(a.inv_k), "s"(a.eps), "s"(a.rope_freq), "s"(a.qkv_bias), "s"(a.live));
+  if constexpr (QKNORM) asm volatile("" ::"s"(a.qk_norm), "s"(a.qkn_eps));
   if ((int)blockIdx.z == (a.batch > 0 ? a.batch : 1)) {  // weight-touch plane (see AttnDecodeArgs::pf)
     const int nb = gridDim.x * gridDim.y, b = blockIdx.y * gridDim.x + blockIdx.x;
     uint32_t acc = 0;
@@ -210,6 +216,15 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
   const int kvsel = tid / (HD / 2), pr = tid % (HD / 2);
   const float2 nv = reinterpret_cast<const float2*>(
       raw && tid < HD ? a.qkv_raw + (kvsel ? a.v_off : a.k_off) + (size_t)kvh * HD : a.q)[raw && tid < HD ? pr : 0];
+  // QK-norm weights (the launcher guarantees raw sums and the deferred RoPE): in the bias loads' place
+  float2 wq[QKNORM ? QPT : 1];
+  float2 wn = make_float2(1.f, 1.f);
+  if constexpr (QKNORM) {
+#pragma unroll
+    for (int j = 0; j < QPT; ++j)
+      wq[j] = reinterpret_cast<const float2*>(a.qk_norm)[min(tid + 256 * j, G * HD / 2 - 1) % (HD / 2)];
+    wn = reinterpret_cast<const float2*>(a.qk_norm + HD)[pr];
+  }
   float2 bn = make_float2(0.f, 0.f);
   if constexpr (BIAS)
     bn = reinterpret_cast<const float2*>(a.qkv_bias + (tid < HD && kvsel ? a.v_off : a.k_off) + (size_t)kvh * HD)[tid < HD ? pr : 0];
@@ -248,7 +263,33 @@ __device__ __forceinline__ void attn_decode_body(AttnDecodeArgs a) {
     sincosf(pf * f, &sn, &cs);
     return make_float2(v.x * cs - v.y * sn, v.x * sn + v.y * cs);
   };
-  if constexpr (BIAS) {
+  if constexpr (QKNORM) {
+    // rot(headnorm(q rs, q_norm)) scale, rot(headnorm(k rs, k_norm)), v rs: the row scale goes on
+    // before the head norm (its eps does not commute with it). A head's HD / 2 pairs sit on HD / 2
+    // consecutive lanes starting at a multiple of HD / 2: a whole wave (HD 128) or half of one.
+    // Every lane takes part in the shuffles; the clamped pairs past G HD / 2 fill whole groups.
+    auto head_ss = [](float v) {
+#pragma unroll
+      for (int o = HD / 4; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      return v;
+    };
+#pragma unroll
+    for (int j = 0; j < QPT; ++j) {
+      const int i = tid + 256 * j;
+      const float y0 = qv[j].x * rs, y1 = qv[j].y * rs;
+      const float hs = rsqrtf(head_ss(y0 * y0 + y1 * y1) * (1.f / HD) + a.qkn_eps);
+      const float2 q2 = rot(make_float2(y0 * hs * wq[j].x, y1 * hs * wq[j].y), fq[j]);
+      if (i < G * HD / 2) qs[i / (HD / 2)][i % (HD / 2)] = h2v{(_Float16)(q2.x * a.scale), (_Float16)(q2.y * a.scale)};
+    }
+    {  // threads 0 .. HD/2 - 1: the new key's pairs (one reduction group); HD/2 .. HD - 1: the value's
+      const float y0 = nv.x * rs, y1 = nv.y * rs;
+      const float hs = rsqrtf(head_ss(y0 * y0 + y1 * y1) * (1.f / HD) + a.qkn_eps);
+      if (tid < HD) {
+        const float2 n2 = tid < HD / 2 ? rot(make_float2(y0 * hs * wn.x, y1 * hs * wn.y), fq[0]) : make_float2(y0, y1);
+        kvn[tid / (HD / 2)][tid % (HD / 2)] = h2v{(_Float16)n2.x, (_Float16)n2.y};
+      }
+    }
+  } else if constexpr (BIAS) {
     // with biases the row scale applies to the sum BEFORE the bias and the rotation,
     // so it cannot be folded into the softmax scale as below: rot(q rs + bq) scale, rot(k rs + bk),
     // v rs + bv

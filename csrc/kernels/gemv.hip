@@ -618,6 +618,7 @@ struct QkvSeg {
   int rows;
   int kind;  // 0 = Q, 1 = K, 2 = V
   const float* bias;  // optional f32 bias of the segment's rows (null: none)
+  int off;            // raw form (QkvLaunch::raw_out): where the segment's rows start in the output row
 };
 struct QkvLaunch {
   QkvSeg seg[3];
@@ -634,6 +635,7 @@ struct QkvLaunch {
   int n_ctx, head_dim;
   const int* pos;
   const float2* rope;
+  float* raw_out;  // QK-norm models: the normalised sums [Q | K | V] go here, unrotated, nothing appended
 };
 
 template <int QT, int NR>
@@ -651,7 +653,10 @@ __device__ __forceinline__ void qkv_item(const QkvLaunch& a, int s_lo, int s_hi,
 // BIAS: the segments carry Q|K|V biases (qwen2). A separate instantiation, chosen once per block
 // (inlined into the same kernel), so that the arithmetic of the unbiased models is compiled from
 // the source it was compiled from without them.
-template <int QT, int NR, int U, int BLOCK, bool BIAS>
+// RAW: the raw-sum form of a QK-norm model (qwen3; QkvLaunch::raw_out) - no (cos, sin) load, no
+// rotation, no cache append: row r of segment si is stored as f32 at raw_out[seg.off + r]. Its own
+// instantiation in the same way.
+template <int QT, int NR, int U, int BLOCK, bool BIAS, bool RAW = false>
 __device__ __forceinline__ void qkv_run(const QkvLaunch& a, int s_lo, int s_hi, int blk, int nblk, int pos,
                                         XPrologue<true, BLOCK>& xp, int8_t* xq, float* xd, float* red) {
   const int wave = wave_id(), lane = threadIdx.x & 63;
@@ -682,7 +687,9 @@ __device__ __forceinline__ void qkv_run(const QkvLaunch& a, int s_lo, int s_hi, 
   {  // unconditional (clamped item): no control-flow join between these loads and finish()'s x wait
     qkv_item<QT, NR>(a, s_lo, s_hi, min(item, total - 1), R, si, r0);
     ws.load(R, 0, nchunks, lane);
-    if (lane < NR && a.seg[si].kind < 2) cs = rope_of(r0 + lane);
+    if constexpr (!RAW) {
+      if (lane < NR && a.seg[si].kind < 2) cs = rope_of(r0 + lane);
+    }
     if constexpr (BIAS) {
       if (lane < NR) bs = a.seg[si].bias[r0 + lane];
     }
@@ -700,7 +707,9 @@ __device__ __forceinline__ void qkv_run(const QkvLaunch& a, int s_lo, int s_hi, 
     if (next < item_end) {
       qkv_item<QT, NR>(a, s_lo, s_hi, next, R, si, r0);
       ws.load(R, 0, nchunks, lane);
-      if (lane < NR && a.seg[si].kind < 2) cs = rope_of(r0 + lane);
+      if constexpr (!RAW) {
+        if (lane < NR && a.seg[si].kind < 2) cs = rope_of(r0 + lane);
+      }
       if constexpr (BIAS) {
         if (lane < NR) bs = a.seg[si].bias[r0 + lane];
       }
@@ -709,6 +718,11 @@ __device__ __forceinline__ void qkv_run(const QkvLaunch& a, int s_lo, int s_hi, 
     for (int r = 0; r < NR; ++r) acc[r] *= xs;
     float v = reduce_rows<NR>(acc, lane);
     if constexpr (BIAS) v += cbs;  // the row's bias, before the rotation
+    if constexpr (RAW) {
+      if (lane < NR) a.raw_out[a.seg[csi].off + cr0 + lane] = v;
+      item = next;
+      continue;
+    }
     const float partner = __shfl_xor(v, 1);
     const int kind = a.seg[csi].kind;
     if (lane < NR) {
@@ -739,6 +753,15 @@ __global__ __launch_bounds__(BLOCK) void gemv_qkv_kernel(QkvLaunch a) {
   const int pos = *a.pos;
   XPrologue<true, BLOCK> xp;   // QKV always follows the attention RMSNorm
   xp.load(a.x, a.norm_w, a.K);
+  if (a.raw_out) {  // (launch-uniform: the raw-sum form of a QK-norm model; gemv_qkv refuses biases with it)
+    if (!TWO || (int)blockIdx.x < a.blocks0) {
+      qkv_run<QT0, NR0, U0, BLOCK, false, true>(a, 0, a.g1, blockIdx.x, TWO ? a.blocks0 : gridDim.x, 0, xp, xq, xd, red);
+    } else if constexpr (TWO) {
+      qkv_run<QT1, NR1, U1, BLOCK, false, true>(a, a.g1, a.nseg, blockIdx.x - a.blocks0, gridDim.x - a.blocks0, 0, xp,
+                                                xq, xd, red);
+    }
+    return;
+  }
   if (a.seg[0].bias) {  // (launch-uniform: every segment has a bias or none does, gemv_qkv checks)
     if (!TWO || (int)blockIdx.x < a.blocks0) {
       qkv_run<QT0, NR0, U0, BLOCK, true>(a, 0, a.g1, blockIdx.x, TWO ? a.blocks0 : gridDim.x, pos, xp, xq, xd, red);
@@ -822,18 +845,22 @@ void gemv_qkv(const QkvArgs& a, hipStream_t s) {
   if (!a.norm_w) throw std::runtime_error("gemv_qkv: the attention RMSNorm weight is required");
   if ((a.bq != nullptr) != (a.bk != nullptr) || (a.bq != nullptr) != (a.bv != nullptr))
     throw std::runtime_error("gemv_qkv: biases on all of Q, K and V, or on none");
+  if (a.raw_out && !a.pos) throw std::runtime_error("gemv_qkv: pos must be readable (the shared prologue loads it)");
+  if (a.raw_out && a.bq) throw std::runtime_error("gemv_qkv: the raw-sum form takes no biases");
   if (a.wq.rows % 4 || a.wk.rows % 4 || a.wv.rows % 4) throw std::runtime_error("gemv_qkv: rows must be multiples of 4");
   const QMat* m[3] = {&a.wq, &a.wk, &a.wv};
   QkvLaunch L{};
   L.K = K; L.x = a.x; L.norm_w = a.norm_w; L.eps = a.eps; L.q_out = a.q_out; L.k_cache = a.k_cache;
   L.v_cache = a.v_cache; L.n_ctx = a.n_ctx; L.head_dim = a.head_dim; L.pos = a.pos; L.rope = a.rope;
+  L.raw_out = a.raw_out;
   // runs of equal type
   int run_start[3], run_type[3], nrun = 0;
   for (int i = 0; i < 3; ++i) {
     if (i == 0 || m[i]->type != m[i - 1]->type) { run_start[nrun] = i; run_type[nrun] = m[i]->type; ++nrun; }
   }
   const float* bias[3] = {a.bq, a.bk, a.bv};
-  for (int i = 0; i < 3; ++i) L.seg[i] = QkvSeg{m[i]->base, m[i]->P, m[i]->rows, i, bias[i]};
+  const int off[3] = {0, a.wq.rows, a.wq.rows + a.wk.rows};
+  for (int i = 0; i < 3; ++i) L.seg[i] = QkvSeg{m[i]->base, m[i]->P, m[i]->rows, i, bias[i], off[i]};
   L.nseg = 3;
   auto rows_of = [&](int lo, int hi) { int r = 0; for (int i = lo; i < hi; ++i) r += m[i]->rows; return r; };
   if (nrun == 1) return launch_qkv1_any(L, run_type[0], rows_of(0, 3), s);

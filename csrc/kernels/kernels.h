@@ -293,6 +293,10 @@ struct QkvArgs {
   const float* bq = nullptr;
   const float* bk = nullptr;
   const float* bv = nullptr;
+  // QK-norm models (qwen3): the launch stores the normalised projection sums [nq | nkv | nkv] as f32
+  // here, with no rotation and no cache append (q_out, the caches, pos and rope are unused, biases
+  // refused); qk_norm_rope_kv finishes them. Null: the rotating / appending form
+  float* raw_out = nullptr;
 };
 void gemv_qkv(const QkvArgs& a, hipStream_t s);
 
@@ -395,6 +399,11 @@ struct AttnDecodeArgs {
   // (q at 0, k at k_off, v at v_off). Needs rope_freq (the deferred RoPE): the kernel computes
   // rot(q rs + bq) scale, rot(k rs + bk) and v rs + bv. Null: none
   const float* qkv_bias = nullptr;
+  // split-K Q|K|V of a QK-norm model (qwen3): [q_norm | k_norm], 2 head_dim floats in the projections'
+  // (pair-permuted) row order. Needs rope_freq, excludes qkv_bias: the kernel computes
+  // rot(headnorm(q rs, q_norm)) scale, rot(headnorm(k rs, k_norm)) and v rs, headnorm with qkn_eps
+  const float* qk_norm = nullptr;
+  float qkn_eps = 1e-6f;
   // which keys a block loads (attn_dev.h LIVE). 0: every launched block issues its 64 K / V rows
   // before the position is known (rows clamped to the cache) and the blocks past the length exit
   // with them in flight. 1: the position is read first - blocks past the length exit before any
@@ -517,6 +526,14 @@ void rope_kv_prefill(const float* qkv, int T, int pos0, int n_q, int n_kv, int h
                      const float2* rope, float* q_out, __half* k_cache, __half* v_cache, hipStream_t s,
                      const int* pos_arr = nullptr, const int* slot_arr = nullptr, size_t slot_stride = 0,
                      const float* bias = nullptr);  // bias: optional [n_q + 2 n_kv] f32 added before the RoPE
+// The same for a QK-norm model (qwen3): every q and k head of qkv [T][n_q + 2 n_kv] is RMS-normalised
+// over its head_dim values (eps inside the root) and multiplied by qk_norm ([q_norm | k_norm],
+// 2 head_dim floats in the rows' order) before the rotation; v is appended as it is. One wave per
+// head of one token; head_dim 64 or 128. pos_dev (without pos_arr): T = 1 at the position *pos_dev.
+void qk_norm_rope_kv(const float* qkv, int T, int pos0, int n_q, int n_kv, int head_dim, int n_ctx,
+                     const float2* rope, const float* qk_norm, float eps, float* q_out, __half* k_cache,
+                     __half* v_cache, hipStream_t s, const int* pos_arr = nullptr, const int* slot_arr = nullptr,
+                     size_t slot_stride = 0, const int* pos_dev = nullptr);
 // batched decode: tok[b] / pos[b] = the current token / position of KV slot slots[b]
 // (+ zero zero[i * zero_stride], i < zero_n: the step's in-launch chain counters)
 void batch_gather(const int* slots, int B, const int* state, int* tok, int* pos, hipStream_t s, int* zero = nullptr,

@@ -151,6 +151,69 @@ void rope_kv_prefill(const float* qkv, int T, int pos0, int n_q, int n_kv, int h
                        rope, q_out, k_cache, v_cache, pos_arr, slot_arr, slot_stride, bias);
 }
 
+// QK-norm models (qwen3): rope_kv_prefill with an RMSNorm over each q and k head in front of the
+// rotation. One wave owns one head of one token (q heads, then k, then v): lane p holds the adjacent
+// pair p of the head (HD 64: the lanes 32 .. 63 hold nothing), the head's sum of squares is a wave
+// reduction. A kernel of its own beside rope_kv_prefill_kernel, which other models keep.
+template <int HD>
+__global__ __launch_bounds__(256) void qk_norm_rope_kv_kernel(const float* qkv, int pos0, int n_q, int n_kv, int n_ctx,
+                                                              const float2* rope, const float* qk_norm, float eps,
+                                                              float* q_out, __half* kc, __half* vc,
+                                                              const int* pos_arr, const int* slot_arr,
+                                                              size_t slot_stride, const int* pos_dev) {
+  const int t = blockIdx.x, lane = threadIdx.x & 63;
+  const int nhq = n_q / HD, nhk = n_kv / HD;
+  const int h = blockIdx.y * 4 + (threadIdx.x >> 6);  // wave-uniform
+  if (h >= nhq + 2 * nhk) return;
+  const int pos = pos_arr ? min(max(pos_arr[t], 0), n_ctx - 1)
+                          : pos_dev ? min(max(*pos_dev, 0), n_ctx - 1) : pos0 + t;
+  if (slot_arr) {
+    kc += (size_t)slot_arr[t] * slot_stride;
+    vc += (size_t)slot_arr[t] * slot_stride;
+  }
+  const bool on = lane < HD / 2;
+  const int p = on ? lane : 0;
+  const float2 a = reinterpret_cast<const float2*>(qkv + (size_t)t * (n_q + 2 * n_kv) + (size_t)h * HD)[p];
+  float y0 = a.x, y1 = a.y;
+  if (h < nhq + nhk) {  // q or k: head norm, then the rotation
+    const float2 w = reinterpret_cast<const float2*>(qk_norm + (h < nhq ? 0 : HD))[p];
+    const float2 cs = rope[(size_t)pos * (HD / 2) + p];
+    const float ss = wave_sum(on ? a.x * a.x + a.y * a.y : 0.f);
+    const float sc = rsqrtf(ss * (1.f / HD) + eps);
+    const float n0 = a.x * sc * w.x, n1 = a.y * sc * w.y;
+    y0 = n0 * cs.x - n1 * cs.y;
+    y1 = n0 * cs.y + n1 * cs.x;
+  }
+  if (!on) return;
+  if (h < nhq) {
+    reinterpret_cast<float2*>(q_out + (size_t)t * n_q + (size_t)h * HD)[p] = make_float2(y0, y1);
+  } else {
+    const bool isk = h < nhq + nhk;
+    const int kvh = isk ? h - nhq : h - nhq - nhk;
+    __half* dst = (isk ? kc : vc) + ((size_t)kvh * n_ctx + pos) * HD;
+    reinterpret_cast<__half2*>(dst)[p] = __floats2half2_rn(y0, y1);
+  }
+}
+
+void qk_norm_rope_kv(const float* qkv, int T, int pos0, int n_q, int n_kv, int head_dim, int n_ctx, const float2* rope,
+                     const float* qk_norm, float eps, float* q_out, __half* k_cache, __half* v_cache, hipStream_t s,
+                     const int* pos_arr, const int* slot_arr, size_t slot_stride, const int* pos_dev) {
+  if (T <= 0) return;
+  if ((pos_arr == nullptr) != (slot_arr == nullptr)) throw std::runtime_error("qk_norm_rope_kv: pos/slot arrays");
+  if (!qk_norm) throw std::runtime_error("qk_norm_rope_kv: the norm weights are required");
+  if (head_dim != 64 && head_dim != 128) throw std::runtime_error("qk_norm_rope_kv: head_dim must be 64 or 128");
+  if (n_q % head_dim || n_kv % head_dim) throw std::runtime_error("qk_norm_rope_kv: whole heads");
+  if (pos_dev && (pos_arr || T != 1)) throw std::runtime_error("qk_norm_rope_kv: a device position serves one row");
+  if (!pos_arr && !pos_dev && (pos0 < 0 || pos0 + T > n_ctx)) throw std::runtime_error("qk_norm_rope_kv: pos0 + T > n_ctx");
+  const dim3 grid(T, ((n_q + 2 * n_kv) / head_dim + 3) / 4);
+  if (head_dim == 128)
+    hipLaunchKernelGGL(qk_norm_rope_kv_kernel<128>, grid, dim3(256), 0, s, qkv, pos0, n_q, n_kv, n_ctx, rope, qk_norm,
+                       eps, q_out, k_cache, v_cache, pos_arr, slot_arr, slot_stride, pos_dev);
+  else
+    hipLaunchKernelGGL(qk_norm_rope_kv_kernel<64>, grid, dim3(256), 0, s, qkv, pos0, n_q, n_kv, n_ctx, rope, qk_norm,
+                       eps, q_out, k_cache, v_cache, pos_arr, slot_arr, slot_stride, pos_dev);
+}
+
 __global__ void batch_gather_kernel(const int* slots, int B, const int* state, int* tok, int* pos, int* zero,
                                     int zero_n, int zero_stride) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;

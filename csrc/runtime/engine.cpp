@@ -271,6 +271,24 @@ float* Engine::upload_qkv_bias(const GGUFFile& f, const std::string& p) {
   return d;
 }
 
+// the layer's QK-norm weights as one vector [q_norm | k_norm] of 2 head_dim floats, permuted with the
+// map of the q / k rows (NeoX -> adjacent pair); the same on every rank (heads never straddle ranks)
+float* Engine::upload_qk_norm(const GGUFFile& f, const std::string& p) {
+  const size_t hd = (size_t)hp_.head_dim;
+  float* d = static_cast<float*>(dalloc(2 * hd * sizeof(float)));
+  float* h = reinterpret_cast<float*>(stage_acquire(2 * hd * sizeof(float)));
+  const char* names[2] = {"attn_q_norm.weight", "attn_k_norm.weight"};
+  for (int i = 0; i < 2; ++i) {
+    const GGUFTensor* t = f.find(p + names[i]);
+    if (!t) throw std::runtime_error("missing tensor " + p + names[i]);
+    if (t->type != T_F32 || (size_t)t->n_elements() != hd) throw std::runtime_error(p + names[i] + ": expected F32 [head_dim]");
+    const float* src = reinterpret_cast<const float*>(f.data(*t));
+    for (size_t r = 0; r < hd; ++r) h[i * hd + r] = src[hp_.rope_neox ? neox_src_row(r, hd) : r];
+  }
+  stage_commit(d, 2 * hd * sizeof(float));
+  return d;
+}
+
 void Engine::load(const GGUFFile& f) {
   const int r = opt_.tp_rank;
   const int d = hp_.n_embd, hd = hp_.head_dim;
@@ -294,6 +312,7 @@ void Engine::load(const GGUFFile& f) {
     L.wq = upload_matrix(f, p + "attn_q.weight", q0_, nq_, 0, d, 0, neox);
     L.wk = upload_matrix(f, p + "attn_k.weight", kv0_, nkvd_, 0, d, 0, neox);
     if (hp_.qkv_bias) L.bqkv = upload_qkv_bias(f, p);
+    if (hp_.qk_norm) L.qkn = upload_qk_norm(f, p);
     L.wv = upload_matrix(f, p + "attn_v.weight", kv0_, nkvd_, 0, d);
     L.wo = upload_matrix(f, p + "attn_output.weight", 0, d, q0_, nq_);
     if (hp_.n_expert > 0) {
@@ -740,7 +759,13 @@ void Engine::enqueue_layer_decode(int l, hipStream_t s) {
   qa.pos = st + S_POS;
   qa.rope = rope_;
   if (L.bqkv) { qa.bq = L.bqkv; qa.bk = L.bqkv + nq_; qa.bv = L.bqkv + nq_ + nkvd_; }
+  // QK-norm (qwen3): the GEMV rotates two rows at a time and never sees a head - it stores the
+  // normalised sums, and the head norm + RoPE + append kernel finishes them at the device's position
+  if (L.qkn) qa.raw_out = qkv_;
   gemv_qkv(qa, s);
+  if (L.qkn)
+    qk_norm_rope_kv(qkv_, 1, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, qa.k_cache, qa.v_cache, s,
+                    nullptr, nullptr, 0, st + S_POS);
 
   AttnDecodeArgs aa;
   aa.q = q_; aa.k_cache = qa.k_cache; aa.v_cache = qa.v_cache; aa.pos = st + S_POS;
@@ -752,7 +777,7 @@ void Engine::enqueue_layer_decode(int l, hipStream_t s) {
   const bool tpe = tp && tp_epilogue(o);  // the all-reduce in the GEMV epilogue (no collective launch)
   // attention + Wo in one launch: Wo's weights stream while the attention runs
   bool fused = false;
-  if (!tp && wo_fuse_) {
+  if (!tp && wo_fuse_ && !L.qkn) {  // (QK-norm layers: the plain attention after the norm kernel)
     aa.done = dec_done_ + 64 * l;
     o.out = x_;
     o.wait = aa.done; o.wait_cnt = nkv_l_; o.wait_n = 1; o.wait_err = wo_err_;
@@ -917,7 +942,11 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
     if (!batched && segs_) {  // packed prompts: per-row slot / position, attention per piece
       __half* kcl = kc_ + kv_layer * (l - opt_.layer_begin);  // slot 0's layer l; + slot * slot_stride_
       __half* vcl = vc_ + kv_layer * (l - opt_.layer_begin);
-      rope_kv_prefill(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, rpos_, rslots_, slot_stride_, L.bqkv);
+      if (L.qkn)
+        qk_norm_rope_kv(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, kcl, vcl, s, rpos_, rslots_,
+                        slot_stride_);
+      else
+        rope_kv_prefill(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, rpos_, rslots_, slot_stride_, L.bqkv);
       // every piece in one launch (up to 16 per launch; grid z = pieces): the pieces of a joint
       // admission ran one launch each, ~100 blocks apiece on a 256-CU chip
       const std::vector<PrefillSeg>& sg = *segs_;
@@ -953,7 +982,10 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
     } else if (!batched) {
       __half* kcl = kc_ + slot_stride_ * kv_slot_ + kv_layer * (l - opt_.layer_begin);
       __half* vcl = vc_ + slot_stride_ * kv_slot_ + kv_layer * (l - opt_.layer_begin);
-      rope_kv_prefill(qkv_, T, pos0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, nullptr, nullptr, 0, L.bqkv);
+      if (L.qkn)
+        qk_norm_rope_kv(qkv_, T, pos0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, kcl, vcl, s);
+      else
+        rope_kv_prefill(qkv_, T, pos0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, nullptr, nullptr, 0, L.bqkv);
       AttnPrefillArgs pa;
       pa.q = q_; pa.k_cache = kcl; pa.v_cache = vcl; pa.T = T; pa.pos0 = pos0; pa.n_ctx = opt_.n_ctx;
       pa.n_head = nh_l_; pa.n_kv_head = nkv_l_; pa.head_dim = hd; pa.scale = 1.f / std::sqrt((float)hd);
@@ -964,8 +996,12 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
     } else {  // T decode rows, each of its own KV slot and position
       __half* kcl = kc_ + kv_layer * (l - opt_.layer_begin);  // slot 0's layer l; the kernels add slot * slot_stride_
       __half* vcl = vc_ + kv_layer * (l - opt_.layer_begin);
-      rope_kv_prefill(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, bpos_, bslots_, slot_stride_,
-                      L.bqkv);
+      if (L.qkn)
+        qk_norm_rope_kv(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, kcl, vcl, s, bpos_, bslots_,
+                        slot_stride_);
+      else
+        rope_kv_prefill(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, bpos_, bslots_, slot_stride_,
+                        L.bqkv);
       AttnDecodeArgs aa;
       aa.q = q_; aa.k_cache = kcl; aa.v_cache = vcl; aa.pos = bpos_;
       aa.n_ctx = opt_.n_ctx; aa.n_head = nh_l_; aa.n_kv_head = nkv_l_; aa.head_dim = hd;
@@ -1239,12 +1275,16 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
   const bool fused = B <= kBmmMaxRows && bmm_qkv_fits(d, B);
   // attention / FFN RMSNorm folded into the one-part projections' x staging (no prep launch)
   const bool fnorm = fused && bmm_norm_fits(d, B);
+  // the Q|K|V side of both, which a QK-norm layer (qwen3) declines: the epilogue's tile holds 16 rows
+  // of a head, never the head - such a layer takes bprep + bmm + the head-norm kernel as a model
+  // too wide for one part does (its FFN keeps `fused` / `fnorm`)
+  const bool qepi = fused && !L.qkn, qfnorm = fnorm && !L.qkn;
   // Q|K|V split over K (the default at B <= 8): RoPE'd partial sums into qkv_b_, normalised and
   // appended to the caches by the attention
   // (Q|K|V biases: only with the RoPE deferred to the attention, which adds them to the normalised
   // sums before rotating; the form with rotated partials takes the one-part / unfused path)
   const bool sk = qkv_sk_ && bmm_qkv_sk_supported(L.t_wq.type, L.t_wk.type, L.t_wv.type, d, B) &&
-                  (!L.bqkv || bmm_qkv_sk_defers_rope());
+                  (!(L.bqkv || L.qkn) || bmm_qkv_sk_defers_rope());
   // FFN paths without the down projection's zero side job: a memset node re-zeroes qkv_b_ / ss_b_
   auto zero_qkv = [&]() {
     if (sk) HIPCHK(hipMemsetAsync(qkv_b_, 0, sizeof(float) * qkv_b_zero_n(), s));
@@ -1265,7 +1305,7 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     a.dbg_clk = clk_of(l, 0);
     bmm(a, s);
   } else {
-    if (!fnorm) bprep_rows(x_, d, false, L.attn_norm, d, B, fused ? nullptr : qkv_, fused ? 0 : B * ncol, s);
+    if (!qfnorm) bprep_rows(x_, d, false, L.attn_norm, d, B, qepi ? nullptr : qkv_, qepi ? 0 : B * ncol, s);
     // Q|K|V: one launch per run of equal weight type (Q4_K_M: one, or Q|K + V on bumped layers;
     // a side-stream graph branch for the V run measured no gain)
     const QMat* m[3] = {&L.t_wq, &L.t_wk, &L.t_wv};
@@ -1283,11 +1323,11 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
         for (int k = 1; k < a.nseg; ++k) {
           a.seg_base[k] = m[i + k]->base; a.seg_rows[k] = m[i + k]->rows; a.seg_out[k] = o[i + k] + (size_t)b0 * ncol;
         }
-        if (fnorm) {
+        if (qfnorm) {
           a.xf = x_ + (size_t)b0 * d; a.ldxf = d; a.norm_w = L.attn_norm; a.eps = hp_.rms_eps;
         }
         if (rl.empty() && b0 == 0) a.dbg_clk = clk_of(l, 0);
-        if (fused) {
+        if (qepi) {
           a.qkv_epi = true;
           for (int k = 0; k < a.nseg; ++k) a.qkv.kind[k] = i + k;
           a.qkv.q_out = q_ + (size_t)b0 * nq_; a.qkv.q_ld = nq_;
@@ -1306,7 +1346,10 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     // bumped layers (Q|K Q4_K + V Q6_K): both runs in one launch
     if (!(rl.size() == 2 && B <= kBmmMaxRows && bmm_qkv2(rl[0], rl[1], s)))
       for (const BmmArgs& a : rl) bmm(a, s);
-    if (!fused)
+    if (L.qkn)
+      qk_norm_rope_kv(qkv_, B, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, kcl, vcl, s, bpos_, bslots_,
+                      slot_stride_);
+    else if (!fused)
       rope_kv_prefill(qkv_, B, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, bpos_, bslots_, slot_stride_,
                       L.bqkv);
   }
@@ -1325,6 +1368,7 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     aa.ss = ss_b_; aa.inv_k = 1.f / (float)d; aa.eps = hp_.rms_eps;
     if (bmm_qkv_sk_defers_rope()) aa.rope_freq = rope_freq_;
     aa.qkv_bias = L.bqkv;
+    aa.qk_norm = L.qkn; aa.qkn_eps = hp_.rms_eps;
   }
   aa.dbg_clk = clk_of(l, 1);
   aa.live = attn_live_;

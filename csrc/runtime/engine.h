@@ -69,6 +69,7 @@ struct Layer {
   float* ffn_norm = nullptr;
   QMat wq, wk, wv, wo;
   float* bqkv = nullptr;             // Q|K|V biases [nq | nkvd | nkvd] (qwen2; null: none)
+  float* qkn = nullptr;              // QK-norm weights [q_norm | k_norm], 2 head_dim (qwen3; null: none)
   QMat w_gu, w_down;                 // dense FFN (gate/up interleaved in 32-row groups)
   QMat router, gu_exps, down_exps;   // MoE
   // batched decode (bmm.hip): tile16 copies of the projections (base = the copy)
@@ -215,6 +216,7 @@ class Engine : public SlotBackend {
   QMat upload_matrix(const GGUFFile& f, const std::string& name, size_t r0, size_t R, size_t c0, size_t K,
                      int n_expert = 0, size_t neox_hd = 0);
   float* upload_qkv_bias(const GGUFFile& f, const std::string& layer_prefix);
+  float* upload_qk_norm(const GGUFFile& f, const std::string& layer_prefix);
   QMat upload_gate_up(const GGUFFile& f, const std::string& gate, const std::string& up, size_t f0, size_t F,
                       int n_expert = 0);
   float* upload_f32(const GGUFFile& f, const std::string& name);

@@ -216,7 +216,9 @@ void GGUFFile::prefetch(const GGUFTensor& t) const {
 HParams read_hparams(const GGUFFile& f) {
   HParams h;
   const std::string arch = f.get_str("general.architecture", "llama");
-  if (arch != "llama" && arch != "mistral" && arch != "mixtral" && arch != "qwen2")
+  if (arch == "qwen3moe")
+    throw std::runtime_error("unsupported architecture qwen3moe (general.architecture): the Qwen3 MoE models are not served");
+  if (arch != "llama" && arch != "mistral" && arch != "mixtral" && arch != "qwen2" && arch != "qwen3")
     throw std::runtime_error("unsupported architecture " + arch);
   h.arch = arch;
   auto gi = [&](const char* k, int64_t d) { return (int)f.get_int(arch + "." + k, d); };
@@ -225,6 +227,15 @@ HParams read_hparams(const GGUFFile& f) {
   h.n_head = gi("attention.head_count", 0);
   h.n_head_kv = gi("attention.head_count_kv", h.n_head);
   h.head_dim = gi("rope.dimension_count", h.n_head ? h.n_embd / h.n_head : 0);
+  if (arch == "qwen3") {  // the head width is a key of its own (Qwen3-0.6B: 16 heads of 128 at n_embd 1024)
+    const std::string kl = arch + ".attention.key_length", vl = arch + ".attention.value_length";
+    if (f.has(kl)) h.head_dim = (int)f.get_int(kl, 0);
+    if (f.has(vl) && (int)f.get_int(vl, 0) != h.head_dim)
+      throw std::runtime_error(vl + " = " + std::to_string(f.get_int(vl, 0)) + " differs from " + kl + " = " +
+                               std::to_string(h.head_dim) + ": not supported");
+    if (h.head_dim != 64 && h.head_dim != 128)
+      throw std::runtime_error(kl + " (head_dim) = " + std::to_string(h.head_dim) + ": the attention kernels serve 64 and 128");
+  }
   h.n_ff = gi("feed_forward_length", 0);
   h.n_expert = gi("expert_count", 0);
   h.n_expert_used = gi("expert_used_count", 0);
@@ -234,12 +245,12 @@ HParams read_hparams(const GGUFFile& f) {
   const GGUFTensor* emb = f.find("token_embd.weight");
   if (!emb) throw std::runtime_error("missing token_embd.weight");
   h.n_vocab = (int)emb->ne[1];
-  if (arch == "qwen2") {
+  if (arch == "qwen2" || arch == "qwen3") {
     h.rope_neox = true;
     const std::string key = arch + ".rope.scaling.type";
     if (f.has(key) && f.get_str(key, "") != "none")
       throw std::runtime_error(key + " = " + f.get_str(key, "?") + ": RoPE scaling is not supported");
-    if (h.head_dim % 2) throw std::runtime_error("qwen2: head_dim must be even");
+    if (h.head_dim % 2) throw std::runtime_error(arch + ": head_dim must be even");
     // the Q|K|V biases: all three of every layer, or none anywhere
     int with = 0;
     for (int l = 0; l < h.n_layer; ++l) {
@@ -258,6 +269,30 @@ HParams read_hparams(const GGUFFile& f) {
       throw std::runtime_error("blk.N.attn_q.bias: present in " + std::to_string(with) + " of " +
                                std::to_string(h.n_layer) + " layers");
     h.qkv_bias = with > 0;
+  }
+  if (arch == "qwen3") {
+    // QK-norm weights: both of every layer, F32 [head_dim], or none anywhere
+    int with = 0;
+    for (int l = 0; l < h.n_layer; ++l) {
+      const std::string p = "blk." + std::to_string(l) + ".";
+      const char* names[2] = {"attn_q_norm.weight", "attn_k_norm.weight"};
+      int n = 0;
+      for (const char* nm : names) n += f.find(p + nm) != nullptr;
+      for (const char* nm : names) {
+        const GGUFTensor* t = f.find(p + nm);
+        if (n > 0 && !t) throw std::runtime_error("missing tensor " + p + nm + " (the layer has the other QK-norm weight)");
+        if (t && t->type != T_F32) throw std::runtime_error(p + nm + ": expected F32");
+        if (t && (t->ne.empty() || t->ne[0] != h.head_dim || (int)t->n_elements() != h.head_dim))
+          throw std::runtime_error(p + nm + ": expected [head_dim] = [" + std::to_string(h.head_dim) + "]");
+      }
+      if (n == 2) ++with;
+      else if (with > 0) throw std::runtime_error("missing tensor " + p + names[0] + " (other layers have QK-norm weights)");
+    }
+    if (with != 0 && with != h.n_layer)
+      throw std::runtime_error("blk.N.attn_q_norm.weight: present in " + std::to_string(with) + " of " +
+                               std::to_string(h.n_layer) + " layers");
+    if (h.qkv_bias && with > 0) throw std::runtime_error("blk.0.attn_q.bias: Q|K|V biases together with QK-norm are not supported");
+    h.qk_norm = with > 0;
   }
   return h;
 }

@@ -68,7 +68,8 @@ class GGUFFile {
 };
 
 // Model hyper-parameters as the GPU engine and the CPU backend read them from the metadata
-// (general.architecture llama / mistral / mixtral / qwen2; anything else is refused).
+// (general.architecture llama / mistral / mixtral / qwen2 / qwen3; anything else is refused). qwen3:
+// head_dim is qwen3.attention.key_length where present (it need not be n_embd / n_head), 64 or 128.
 struct HParams {
   int n_vocab = 0, n_embd = 0, n_layer = 0, n_head = 0, n_head_kv = 0, head_dim = 0, n_ff = 0;
   int n_expert = 0, n_expert_used = 0, n_ctx_train = 0;
@@ -79,6 +80,10 @@ struct HParams {
   bool rope_neox = false;
   // blk.N.attn_{q,k,v}.bias (F32) are present: added to the projections before RoPE
   bool qkv_bias = false;
+  // blk.N.attn_{q,k}_norm.weight (F32 [head_dim]) are present (qwen3): an RMSNorm over each q and k
+  // head after the projection and before RoPE. The loaders permute these weights with the map of
+  // the q / k rows (neox_src_row), which leaves a head's mean square as it was
+  bool qk_norm = false;
 };
 HParams read_hparams(const GGUFFile& f);
 

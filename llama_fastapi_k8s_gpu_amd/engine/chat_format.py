@@ -122,8 +122,8 @@ def guess_chat_format(metadata: dict) -> Optional[str]:
     if tmpl is None:
         return None
     known = KNOWN_TEMPLATES.get(tmpl)
-    # a Qwen2 / Qwen2.5 template (ChatML behind a long tool-calling preamble) matches none exactly
-    if known is None and metadata.get("general.architecture") == "qwen2":
+    # a Qwen2 / Qwen2.5 / Qwen3 template (ChatML behind a long tool-calling preamble) matches none exactly
+    if known is None and metadata.get("general.architecture") in ("qwen2", "qwen3"):
         return "chatml"
     return known
 

@@ -86,6 +86,20 @@ FTYPE_MOSTLY_Q6_K = 18
 FTYPE_MOSTLY_IQ4_NL = 25
 FTYPE_MOSTLY_IQ4_XS = 30
 
+# general.architecture values the engines serve, and the ones refused by name
+ARCHITECTURES = ("llama", "mistral", "mixtral", "qwen2", "qwen3")
+ARCH_QWEN3 = "qwen3"
+ARCH_QWEN3MOE = "qwen3moe"   # refused: 128 experts, a different router
+
+# qwen3 metadata keys ("{arch}." in front)
+KEY_ATTN_KEY_LENGTH = "attention.key_length"      # head_dim (need not be n_embd / n_head)
+KEY_ATTN_VALUE_LENGTH = "attention.value_length"  # must equal key_length
+KEY_ROPE_SCALING_TYPE = "rope.scaling.type"       # absent or "none"
+
+# per-layer QK-norm weights (qwen3): F32 [head_dim], "blk.N." in front
+TENSOR_ATTN_Q_NORM = "attn_q_norm.weight"
+TENSOR_ATTN_K_NORM = "attn_k_norm.weight"
+
 # llama vocab token types
 TOKEN_TYPE_NORMAL = 1
 TOKEN_TYPE_UNKNOWN = 2

@@ -30,6 +30,7 @@ import numpy as np
 from .constants import (FTYPE_MOSTLY_IQ4_NL, FTYPE_MOSTLY_IQ4_XS, FTYPE_MOSTLY_Q2_K, FTYPE_MOSTLY_Q3_K_M, FTYPE_MOSTLY_Q3_K_S, FTYPE_MOSTLY_Q4_0,
                         FTYPE_MOSTLY_Q4_1, FTYPE_MOSTLY_Q4_K_M, FTYPE_MOSTLY_Q5_0, FTYPE_MOSTLY_Q5_1, FTYPE_MOSTLY_Q8_0, GGMLType, GGUFValueType,
                         TOKEN_TYPE_BYTE, TOKEN_TYPE_CONTROL, TOKEN_TYPE_NORMAL)
+from .constants import ARCH_QWEN3, KEY_ATTN_KEY_LENGTH, KEY_ATTN_VALUE_LENGTH, TENSOR_ATTN_K_NORM, TENSOR_ATTN_Q_NORM
 from .quants import random_blocks
 from .writer import GGUFWriter
 
@@ -85,13 +86,19 @@ class ModelSpec:
     size_class: str = "8B"    # "8B" | "70B" (affects the Q4_K_M attn_v rule)
     weight_std: float = 0.02
     chat_template: Optional[str] = None
-    arch: str = "llama"       # general.architecture: "llama" | "qwen2" (keys under it; NeoX RoPE, no BOS)
+    arch: str = "llama"       # general.architecture: "llama" | "qwen2" | "qwen3" (keys under it; NeoX RoPE, no BOS)
     qkv_bias: bool = False    # F32 blk.N.attn_{q,k,v}.bias (Qwen2)
     tied_output: bool = False  # no output.weight: the head is token_embd.weight
+    qk_norm: bool = False     # F32 blk.N.attn_{q,k}_norm.weight [head_dim] (Qwen3)
+    hd: int = 0               # head width where it is not n_embd / n_head (Qwen3: attention.key_length)
 
     @property
     def head_dim(self) -> int:
-        return self.n_embd // self.n_head
+        return self.hd or self.n_embd // self.n_head
+
+    @property
+    def n_q(self) -> int:     # rows of attn_q / columns of attn_output
+        return self.head_dim * self.n_head
 
 
 # uniform legacy (32-weight block) file types: quant name -> (tensor type, general.file_type)
@@ -197,6 +204,25 @@ SPECS.update({
     # Qwen2.5-7B-Instruct's shape (for measuring, not for tests)
     "qwen2.5-7b-q4_k_m": replace(_qwen2("Qwen2.5-7B", 3584, 28, 28, 4, 18944, "q4_k_m", n_vocab=152064),
                                  n_ctx_train=32768),
+})
+
+# Qwen3 (dense): no biases, QK-norm, a head width of its own (key_length), NeoX RoPE, the qwen2 tokenizer
+def _qwen3(name, d, n_layer, n_head, n_kv, hd, n_ff, quant, n_vocab=0, **kw):
+    return ModelSpec(name, d, n_layer, n_head, n_kv, n_ff, n_vocab, 1e6, "bpe", quant, n_ctx_train=1024,
+                     rms_eps=1e-6, arch="qwen3", qk_norm=True, hd=hd, **kw)
+
+
+SPECS.update({
+    # n_q = 1024 != d = 768 (the 0.6B's kind of geometry), tied output
+    "tiny-qwen3-g2-hd128": _qwen3("tiny-qwen3-g2-hd128", 768, 2, 8, 4, 128, 512, "q4_k_m", tied_output=True),
+    "tiny-qwen3-g4-hd64": _qwen3("tiny-qwen3-g4-hd64", 512, 2, 8, 2, 64, 512, "q8_0"),
+    # mixed types: the batched step takes the unfused path (bprep + bmm + head-norm kernel)
+    "tiny-qwen3-g5": _qwen3("tiny-qwen3-g5", 1280, 2, 10, 2, 128, 512, "mixed-test"),
+    "tiny-qwen3-g8": _qwen3("tiny-qwen3-g8", 2048, 2, 16, 2, 128, 512, "q4_k_m"),
+    "tiny-qwen3-tp": _qwen3("tiny-qwen3-tp", 1536, 2, 16, 4, 128, 512, "q4_k_m"),
+    # Qwen3-8B's shape (for measuring, not for tests)
+    "qwen3-8b-q4_k_m": replace(_qwen3("Qwen3-8B", 4096, 36, 32, 8, 128, 12288, "q4_k_m", n_vocab=151936),
+                               n_ctx_train=40960),
 })
 
 # the legacy 32-weight block formats (Q4_0 / Q4_1 / Q5_0 / Q5_1) over existing shapes
@@ -357,7 +383,7 @@ def build_vocab(spec: ModelSpec) -> Tuple[Dict, int]:
                 tokens.append(cand)
         base = len(tokens)
         types = [TOKEN_TYPE_NORMAL] * base
-        qwen2 = spec.arch == "qwen2"
+        qwen2 = spec.arch in ("qwen2", "qwen3")
         for k in range(256):
             name = (QWEN2_SPECIALS if qwen2 else LLAMA3_SPECIALS).get(k, f"<|reserved_special_token_{k}|>")
             tokens.append(name)
@@ -399,7 +425,7 @@ def build_vocab(spec: ModelSpec) -> Tuple[Dict, int]:
 
 def tensor_plan(spec: ModelSpec, n_vocab: int) -> List[Tuple[str, GGMLType, Tuple[int, ...]]]:
     d, f, L = spec.n_embd, spec.n_ff, spec.n_layer
-    dkv = spec.head_dim * spec.n_head_kv
+    dkv, nq = spec.head_dim * spec.n_head_kv, spec.n_q
     if spec.quant == "q8_0":
         emb_t, out_t = GGMLType.Q8_0, GGMLType.Q8_0
     elif spec.quant == "f32":
@@ -423,14 +449,17 @@ def tensor_plan(spec: ModelSpec, n_vocab: int) -> List[Tuple[str, GGMLType, Tupl
         tt = tensor_types(spec, i)
         p = f"blk.{i}."
         plan += [(p + "attn_norm.weight", GGMLType.F32, (d,)),
-                 (p + "attn_q.weight", tt["attn_q"], (d, d)),
+                 (p + "attn_q.weight", tt["attn_q"], (d, nq)),
                  (p + "attn_k.weight", tt["attn_k"], (d, dkv)),
                  (p + "attn_v.weight", tt["attn_v"], (d, dkv)),
-                 (p + "attn_output.weight", tt["attn_output"], (d, d)),
+                 (p + "attn_output.weight", tt["attn_output"], (nq, d)),
                  (p + "ffn_norm.weight", GGMLType.F32, (d,))]
         if spec.qkv_bias:
-            plan += [(p + "attn_q.bias", GGMLType.F32, (d,)), (p + "attn_k.bias", GGMLType.F32, (dkv,)),
+            plan += [(p + "attn_q.bias", GGMLType.F32, (nq,)), (p + "attn_k.bias", GGMLType.F32, (dkv,)),
                      (p + "attn_v.bias", GGMLType.F32, (dkv,))]
+        if spec.qk_norm:
+            plan += [(p + TENSOR_ATTN_Q_NORM, GGMLType.F32, (spec.head_dim,)),
+                     (p + TENSOR_ATTN_K_NORM, GGMLType.F32, (spec.head_dim,))]
         if spec.n_expert:
             E = spec.n_expert
             plan += [(p + "ffn_gate_inp.weight", GGMLType.F32, (d, E)),
@@ -470,6 +499,10 @@ def hparams_metadata(spec: ModelSpec, n_vocab: int) -> Dict:
         md[f"{a}.expert_used_count"] = spec.n_expert_used
     if a == "qwen2":  # (Qwen2 files carry no rope.dimension_count: head_dim = n_embd / n_head)
         del md[f"{a}.rope.dimension_count"]
+    if a == ARCH_QWEN3:  # the head width is a key of its own, for keys and for values
+        del md[f"{a}.rope.dimension_count"]
+        md[f"{a}.{KEY_ATTN_KEY_LENGTH}"] = spec.head_dim
+        md[f"{a}.{KEY_ATTN_VALUE_LENGTH}"] = spec.head_dim
     return md
 
 
@@ -516,7 +549,10 @@ def write_synthetic_gguf(spec, path: str, seed: int = 0, log=None, extra_metadat
         if name == "output.weight" and untie_output and spec.tied_output:
             w.write_tensor_data(embd)
             continue
-        if name.endswith("norm.weight"):
+        if name.endswith((TENSOR_ATTN_Q_NORM, TENSOR_ATTN_K_NORM)):
+            # far from ones, so that a dropped or unpermuted QK-norm weight shows
+            data = (1.0 + 0.5 * rng.standard_normal(n)).astype(np.float32)
+        elif name.endswith("norm.weight"):
             data = (1.0 + 0.1 * rng.standard_normal(n)).astype(np.float32)
         elif name.endswith(".bias"):
             # four times the standard deviation of the projection's own output on a normed input

@@ -17,6 +17,12 @@ runs the upstream ``llm_build_llama`` op sequence in float32:
 and V projections (added before RoPE) and NeoX RoPE pairs (i, i + head_dim/2). The reference
 rotates those pairs on the file's own weight rows - the native backends instead permute the rows
 and keep rotating adjacent pairs, so this forward is an independent check of that.
+
+``general.architecture = qwen3`` drops the biases and adds QK-norm: an RMSNorm over each head's
+head_dim values of q and of k (F32 weights blk.N.attn_{q,k}_norm.weight [head_dim]), after the
+projection and before RoPE; head_dim comes from ``attention.key_length`` and need not be
+n_embd / n_head. Here it is applied on the file's own row order with rotate-half - the native
+backends permute rows and norm weights alike.
 """
 from __future__ import annotations
 
@@ -24,6 +30,9 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional
 
 import numpy as np
+
+from ..gguf.constants import (ARCH_QWEN3, ARCH_QWEN3MOE, ARCHITECTURES, KEY_ATTN_KEY_LENGTH, KEY_ATTN_VALUE_LENGTH,
+                              KEY_ROPE_SCALING_TYPE, TENSOR_ATTN_K_NORM, TENSOR_ATTN_Q_NORM)
 
 
 @dataclass
@@ -43,6 +52,7 @@ class LlamaHParams:
     arch: str = "llama"
     rope_neox: bool = False      # RoPE pairs (i, i + head_dim/2) instead of (2i, 2i+1)
     qkv_bias: bool = False       # blk.N.attn_{q,k,v}.bias present (set by the loaders from the tensors)
+    qk_norm: bool = False        # blk.N.attn_{q,k}_norm.weight present (qwen3; set by the loaders likewise)
 
     @property
     def n_embd_kv(self) -> int:
@@ -55,23 +65,33 @@ class LlamaHParams:
     @classmethod
     def from_metadata(cls, md: Dict) -> "LlamaHParams":
         arch = md.get("general.architecture", "llama")
-        if arch not in ("llama", "mistral", "mixtral", "qwen2"):
+        if arch == ARCH_QWEN3MOE:
+            raise NotImplementedError(f"architecture {arch!r} is not supported (the Qwen3 MoE models are not served)")
+        if arch not in ARCHITECTURES:
             raise NotImplementedError(f"architecture {arch!r} is not supported")
         g = lambda k, d=None: md.get(f"{arch}.{k}", d)
-        if arch == "qwen2" and g("rope.scaling.type", "none") not in (None, "none"):
-            raise NotImplementedError(f"{arch}.rope.scaling.type = {g('rope.scaling.type')!r}: RoPE scaling "
+        if arch in ("qwen2", ARCH_QWEN3) and g(KEY_ROPE_SCALING_TYPE, "none") not in (None, "none"):
+            raise NotImplementedError(f"{arch}.{KEY_ROPE_SCALING_TYPE} = {g(KEY_ROPE_SCALING_TYPE)!r}: RoPE scaling "
                                       "is not supported")
         n_embd = int(g("embedding_length"))
         n_head = int(g("attention.head_count"))
         n_vocab = int(g("vocab_size", 0) or len(md.get("tokenizer.ggml.tokens", [])))
+        head_dim = int(g("rope.dimension_count", n_embd // n_head))
+        if arch == ARCH_QWEN3:
+            head_dim = int(g(KEY_ATTN_KEY_LENGTH, head_dim))
+            if int(g(KEY_ATTN_VALUE_LENGTH, head_dim)) != head_dim:
+                raise NotImplementedError(f"{arch}.{KEY_ATTN_VALUE_LENGTH} differs from {arch}.{KEY_ATTN_KEY_LENGTH}")
+            if head_dim not in (64, 128):
+                raise NotImplementedError(f"{arch}.{KEY_ATTN_KEY_LENGTH} (head_dim) = {head_dim}: 64 or 128")
         return cls(n_vocab=n_vocab, n_embd=n_embd, n_layer=int(g("block_count")), n_head=n_head,
                    n_head_kv=int(g("attention.head_count_kv", n_head)),
-                   head_dim=int(g("rope.dimension_count", n_embd // n_head)),
+                   head_dim=head_dim,
                    n_ff=int(g("feed_forward_length")), n_expert=int(g("expert_count", 0) or 0),
                    n_expert_used=int(g("expert_used_count", 0) or 0),
                    rope_base=float(g("rope.freq_base", 10000.0)),
                    rms_eps=float(g("attention.layer_norm_rms_epsilon", 1e-5)),
-                   n_ctx_train=int(g("context_length", 2048)), arch=arch, rope_neox=arch == "qwen2")
+                   n_ctx_train=int(g("context_length", 2048)), arch=arch,
+                   rope_neox=arch in ("qwen2", ARCH_QWEN3))
 
 
 def rope_tables(hp: LlamaHParams, n_pos: int):
@@ -108,9 +128,10 @@ class ReferenceLlama:
     """
 
     def __init__(self, reader, n_ctx: int = 512, device: str = "cpu", rope_neox: Optional[bool] = None,
-                 qkv_bias: bool = True):
-        """``rope_neox`` overrides the architecture's RoPE pairing and ``qkv_bias=False`` drops the
-        Q|K|V biases: deliberately wrong models, for tests that show a check would catch them."""
+                 qkv_bias: bool = True, qk_norm: bool = True):
+        """``rope_neox`` overrides the architecture's RoPE pairing, ``qkv_bias=False`` drops the
+        Q|K|V biases and ``qk_norm=False`` the QK-norm: deliberately wrong models, for tests that
+        show a check would catch them."""
         import torch
         self.torch = torch
         self.reader = reader
@@ -146,6 +167,16 @@ class ReferenceLlama:
                 hp.qkv_bias = True
                 for k in have:
                     L[k + "_b"] = t(p + k + ".bias")
+            have = [k for k in (TENSOR_ATTN_Q_NORM, TENSOR_ATTN_K_NORM) if p + k in reader.tensors]
+            if have and len(have) != 2:
+                raise ValueError(f"{p}{have[0]} without the layer's other QK-norm weight")
+            if have and qk_norm:
+                hp.qk_norm = True
+                for k in have:
+                    w = t(p + k)
+                    if tuple(w.shape) != (hp.head_dim,):
+                        raise ValueError(f"{p}{k}: expected [head_dim]")
+                    L[k[:-len(".weight")]] = w
             L["_prefix"] = p
             self.layers.append(L)
         cos, sin = rope_tables(hp, n_ctx)
@@ -343,6 +374,8 @@ class ReferenceLlama:
             q = q.view(T, hp.n_head, hp.head_dim)
             k = k.view(T, hp.n_head_kv, hp.head_dim)
             v = v.view(T, hp.n_head_kv, hp.head_dim)
+            if "attn_q_norm" in L:   # qwen3: RMSNorm over each head, before RoPE (fp32 in every path)
+                q, k = self._rms(q, L["attn_q_norm"]), self._rms(k, L["attn_k_norm"])
             q, k = self._rope(q, pos), self._rope(k, pos)
             if path is not None:   # the engine's KV cache is f16
                 k, v = self._f16(k), self._f16(v)
