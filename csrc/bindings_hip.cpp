@@ -384,14 +384,15 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("store_out") = false, py::arg("dbg_clk") = 0, py::arg("tr") = -1, py::arg("ew") = 0,
      py::arg("ew_ld") = 0, py::arg("tiles_per_expert") = 0, py::arg("steps_per_expert") = 0, py::arg("zero") = 0,
      py::arg("zero_n") = 0);
-  // the gate/up + down chain in one launch (tests/test_kernels_gpu.py::test_bmm_ffn_chain_*): gate/up
-  // rows in the SwiGLU tile16 copy (wg, 2F x K), down (wd, K x F) over the f16 SwiGLU output hout
-  // [B][F]; out [B][K] accumulates; cnt >= 64 ints, zeroed by the caller
+  // the gate/up + down chain in one launch (tests/test_kernels_gpu.py::test_bmm_ffn_chain_*,
+  // tests/test_ffn_chain_gpu.py): gate/up rows in the SwiGLU tile16 copy (wg, 2F x K), down (wd, K x F)
+  // over the f16 SwiGLU output hout [B][F]; out [B][K] accumulates; cnt: chain_layout()'s ints, zeroed
+  // by the caller. err: an int32 the caller zeroed (a consumer's timed-out wait sets it); zero / zero_n:
+  // the down's zero side job. The *_supported hooks ask the predicates over the same arguments.
   m.def("chain_layout", []() { return std::make_tuple(kChainStride, kChainXcds, kChainInts); });
-  m.def("bmm_ffn_chain", [](uintptr_t wg, int tg, int F, int K, uintptr_t xh, uintptr_t xf, uintptr_t norm, float eps,
-                            uintptr_t wd, int td, uintptr_t hout, uintptr_t out, int B, uintptr_t cnt,
-                            uintptr_t stream, int tr) {
-    BmmArgs gu, dn;
+  auto chain_args = [](BmmArgs& gu, BmmArgs& dn, uintptr_t wg, int tg, int F, int K, uintptr_t xh, uintptr_t xf,
+                       uintptr_t norm, float eps, uintptr_t wd, int td, uintptr_t hout, uintptr_t out, int B, int tr,
+                       uintptr_t zero, int zero_n) {
     dn.tr = tr;
     gu.w = make_qmat(P<void>(wg), tg, 2 * F, K);
     gu.xh = P<__half>(xh); gu.ldh = K; gu.n_out = 2 * F; gu.B = B;
@@ -401,18 +402,30 @@ PYBIND11_MODULE(_hip, m) {
     }
     dn.w = make_qmat(P<void>(wd), td, K, F);
     dn.xh = P<__half>(hout); dn.ldh = F; dn.out = P<float>(out); dn.ldo = K; dn.n_out = K; dn.B = B;
+    dn.zero = P<float>(zero); dn.zero_n = zero_n;
+  };
+  m.def("bmm_ffn_chain", [chain_args](uintptr_t wg, int tg, int F, int K, uintptr_t xh, uintptr_t xf, uintptr_t norm,
+                                      float eps, uintptr_t wd, int td, uintptr_t hout, uintptr_t out, int B,
+                                      uintptr_t cnt, uintptr_t stream, int tr, uintptr_t err, uintptr_t zero,
+                                      int zero_n) {
+    BmmArgs gu, dn;
+    chain_args(gu, dn, wg, tg, F, K, xh, xf, norm, eps, wd, td, hout, out, B, tr, zero, zero_n);
     if (!bmm_ffn_chain_supported(gu, dn)) throw std::runtime_error("bmm_ffn_chain: unsupported shapes");
-    bmm_ffn_chain(gu, dn, P<int>(cnt), nullptr, S(stream));
+    bmm_ffn_chain(gu, dn, P<int>(cnt), P<int>(err), S(stream));
     hip_ok("bmm_ffn_chain");
   }, py::arg("wg"), py::arg("tg"), py::arg("F"), py::arg("K"), py::arg("xh"), py::arg("xf"), py::arg("norm"),
      py::arg("eps"), py::arg("wd"), py::arg("td"), py::arg("hout"), py::arg("out"), py::arg("B"), py::arg("cnt"),
-     py::arg("stream"), py::arg("tr") = -1);
+     py::arg("stream"), py::arg("tr") = -1, py::arg("err") = 0, py::arg("zero") = 0, py::arg("zero_n") = 0);
+  m.def("bmm_ffn_chain_supported", [chain_args](int tg, int F, int K, int td, int B, bool norm) {
+    BmmArgs gu, dn;  // (the predicate compares pointers and reads shapes: nothing is dereferenced)
+    chain_args(gu, dn, 16, tg, F, K, 16, norm ? 16 : 0, norm ? 16 : 0, 1e-5f, 16, td, 32, 48, B, -1, 0, 0);
+    return bmm_ffn_chain_supported(gu, dn);
+  }, py::arg("tg"), py::arg("F"), py::arg("K"), py::arg("td"), py::arg("B"), py::arg("norm") = false);
   // Wo -> gate/up -> down in one launch (tests/test_kernels_gpu.py::test_bmm_wo_ffn_chain_*): Wo adds
   // W_o . xa into the residual rows `resid`, the gate/up stages norm(resid), the down adds into resid
-  m.def("bmm_wo_ffn_chain", [](uintptr_t wo, int to, int Kwo, uintptr_t xa, uintptr_t wg, int tg, int F, int K,
-                               uintptr_t norm, float eps, uintptr_t wd, int td, uintptr_t xh, uintptr_t hout,
-                               uintptr_t resid, int B, uintptr_t cnt, uintptr_t stream, int tr) {
-    BmmArgs o, gu, dn;
+  auto chain3_args = [](BmmArgs& o, BmmArgs& gu, BmmArgs& dn, uintptr_t wo, int to, int Kwo, uintptr_t xa, uintptr_t wg,
+                        int tg, int F, int K, uintptr_t norm, float eps, uintptr_t wd, int td, uintptr_t xh,
+                        uintptr_t hout, uintptr_t resid, int B, int tr, uintptr_t zero, int zero_n) {
     o.tr = dn.tr = tr;
     o.w = make_qmat(P<void>(wo), to, K, Kwo);
     o.xh = P<__half>(xa); o.ldh = Kwo; o.out = P<float>(resid); o.ldo = K; o.n_out = K; o.B = B;
@@ -422,12 +435,26 @@ PYBIND11_MODULE(_hip, m) {
     gu.xf = P<float>(resid); gu.ldxf = K; gu.norm_w = P<float>(norm); gu.eps = eps;
     dn.w = make_qmat(P<void>(wd), td, K, F);
     dn.xh = P<__half>(hout); dn.ldh = F; dn.out = P<float>(resid); dn.ldo = K; dn.n_out = K; dn.B = B;
+    dn.zero = P<float>(zero); dn.zero_n = zero_n;
+  };
+  m.def("bmm_wo_ffn_chain", [chain3_args](uintptr_t wo, int to, int Kwo, uintptr_t xa, uintptr_t wg, int tg, int F, int K,
+                                          uintptr_t norm, float eps, uintptr_t wd, int td, uintptr_t xh, uintptr_t hout,
+                                          uintptr_t resid, int B, uintptr_t cnt, uintptr_t stream, int tr, uintptr_t err,
+                                          uintptr_t zero, int zero_n) {
+    BmmArgs o, gu, dn;
+    chain3_args(o, gu, dn, wo, to, Kwo, xa, wg, tg, F, K, norm, eps, wd, td, xh, hout, resid, B, tr, zero, zero_n);
     if (!bmm_wo_ffn_chain_supported(o, gu, dn)) throw std::runtime_error("bmm_wo_ffn_chain: unsupported shapes");
-    bmm_wo_ffn_chain(o, gu, dn, P<int>(cnt), nullptr, S(stream));
+    bmm_wo_ffn_chain(o, gu, dn, P<int>(cnt), P<int>(err), S(stream));
     hip_ok("bmm_wo_ffn_chain");
   }, py::arg("wo"), py::arg("to"), py::arg("Kwo"), py::arg("xa"), py::arg("wg"), py::arg("tg"), py::arg("F"),
      py::arg("K"), py::arg("norm"), py::arg("eps"), py::arg("wd"), py::arg("td"), py::arg("xh"), py::arg("hout"),
-     py::arg("resid"), py::arg("B"), py::arg("cnt"), py::arg("stream"), py::arg("tr") = -1);
+     py::arg("resid"), py::arg("B"), py::arg("cnt"), py::arg("stream"), py::arg("tr") = -1, py::arg("err") = 0,
+     py::arg("zero") = 0, py::arg("zero_n") = 0);
+  m.def("bmm_wo_ffn_chain_supported", [chain3_args](int to, int Kwo, int tg, int F, int K, int td, int B) {
+    BmmArgs o, gu, dn;
+    chain3_args(o, gu, dn, 16, to, Kwo, 16, 16, tg, F, K, 16, 1e-5f, 16, td, 16, 32, 48, B, -1, 0, 0);
+    return bmm_wo_ffn_chain_supported(o, gu, dn);
+  });
   // Q|K|V of a batched decode step as Engine::enqueue_batch_layer launches it when the split-K form
   // is off (tests/test_qkv_paths_gpu.py): up to three tile16 matrices (base, type, rows) over xh
   // [B][ldh], or over xf / norm / eps (the folded norm), split into runs of equal tile16 format.

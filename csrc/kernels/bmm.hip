@@ -2246,12 +2246,25 @@ void bmm(const BmmArgs& a0, hipStream_t s) {
   LFK_DISPATCH(LFK_TYPES_T16, a.w.type, throw std::runtime_error("bmm: unsupported weight type"), launch_bmm<QT>(a, s));
 }
 
-bool bmm_ffn_chain_supported(const BmmArgs& gu, const BmmArgs& dn) {
-  return gu.swiglu_epi && !gu.ew && !gu.qkv_epi && gu.nseg == 1 && gu.B <= 8 && (!gu.xf || gu.w.K == 4096) &&
+// K parts of a split-K role as its launcher will plan them (wt_config on a copy)
+static int wt_k_parts(const BmmArgs& a0) {
+  BmmArgs a = a0;
+  size_t lds = 0;
+  wt_config(a, true, lds);
+  return a.kparts;
+}
+
+static bool ffn_chain_shapes(const BmmArgs& gu, const BmmArgs& dn) {
+  return gu.swiglu_epi && !gu.ew && !gu.qkv_epi && gu.nseg == 1 && gu.B >= 1 && gu.B <= 8 && (!gu.xf || gu.w.K == 4096) &&
          !dn.swiglu_epi && !dn.ew && !dn.qkv_epi && !dn.xf && !dn.one_part && !dn.store_out && dn.nseg == 1 &&
          dn.B == gu.B && t16_kernel_type(gu.w.type) == T_Q4_K &&
          (t16_kernel_type(dn.w.type) == T_Q4_K || dn.w.type == T_Q6_K) &&
-         dn.xh == gu.h_out && dn.ldh == gu.ldh_out && dn.w.K == gu.n_out / 2;
+         dn.xh == gu.h_out && dn.ldh == gu.ldh_out && dn.w.K == gu.n_out / 2 && dn.w.K >= 256;
+}
+
+bool bmm_ffn_chain_supported(const BmmArgs& gu, const BmmArgs& dn) {
+  // (the part count last: the plan asks the device for its CU count)
+  return ffn_chain_shapes(gu, dn) && wt_k_parts(dn) <= kChainStagedPart;
 }
 
 void bmm_ffn_chain(const BmmArgs& gu0, const BmmArgs& dn0, int* cnt, int* err, hipStream_t s) {
@@ -2284,9 +2297,13 @@ void bmm_ffn_chain(const BmmArgs& gu0, const BmmArgs& dn0, int* cnt, int* err, h
 }
 
 bool bmm_wo_ffn_chain_supported(const BmmArgs& wo, const BmmArgs& gu, const BmmArgs& dn) {
-  return bmm_il() && bmm_ffn_chain_supported(gu, dn) && gu.xf && t16_kernel_type(wo.w.type) == T_Q4_K && !wo.ew && !wo.xf &&
-         !wo.swiglu_epi && !wo.qkv_epi && !wo.one_part && !wo.store_out && !wo.zero && wo.nseg == 1 && wo.B == gu.B &&
-         wo.out == gu.xf && wo.ldo == gu.ldxf && wo.n_out == gu.w.K;
+  if (!(bmm_il() && ffn_chain_shapes(gu, dn) && gu.xf && t16_kernel_type(wo.w.type) == T_Q4_K && !wo.ew && !wo.xf &&
+        !wo.swiglu_epi && !wo.qkv_epi && !wo.one_part && !wo.store_out && !wo.zero && wo.nseg == 1 && wo.B == gu.B &&
+        wo.out == gu.xf && wo.ldo == gu.ldxf && wo.n_out == gu.w.K && wo.w.K >= 256))
+    return false;
+  // Wo and the down split K (their blocks publish / wait per part); the down's parts stay below Wo's counter
+  const int pd = wt_k_parts(dn);
+  return wt_k_parts(wo) >= 2 && pd >= 2 && pd <= kChainWoPart;
 }
 
 void bmm_wo_ffn_chain(const BmmArgs& wo0, const BmmArgs& gu0, const BmmArgs& dn0, int* cnt, int* err, hipStream_t s) {

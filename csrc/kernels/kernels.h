@@ -241,10 +241,16 @@ constexpr int kChainStagedPart = kChainMaxParts - 1;  // the last part's counter
 constexpr int kChainWoPart = kChainMaxParts - 2;      // ... the one before: Wo blocks done (bmm_wo_ffn_chain)
 // BmmArgs::chain_role bits
 constexpr int kChainProduce = 1, kChainConsume = 2, kChainWoDone = 4, kChainWaitWo = 8;
+// true when the launcher takes the pair: the roles' forms and types, and the down's K parts as
+// its launch plans them (the split-K rule over this device's CUs) within the counters - at most
+// kChainStagedPart (15) parts. d = 2048, F = 8192 plans 16 parts of 2 steps on 256 CUs: false, and the
+// caller launches gate/up and down separately. (Asks the device for its CU count.)
 bool bmm_ffn_chain_supported(const BmmArgs& gu, const BmmArgs& dn);
 void bmm_ffn_chain(const BmmArgs& gu, const BmmArgs& dn, int* cnt, int* err, hipStream_t s);
 // ... with the Wo projection (wo: split-K into the residual rows gu stages) in the same launch: the
-// gate/up blocks issue their first weight steps, wait until every Wo block is done, then stage x
+// gate/up blocks issue their first weight steps, wait until every Wo block is done, then stage x.
+// Supported: as above, with Wo and the down both split into at least 2 K parts and the down's parts
+// at most kChainWoPart (14) - the counters of part 14 count the finished Wo blocks.
 bool bmm_wo_ffn_chain_supported(const BmmArgs& wo, const BmmArgs& gu, const BmmArgs& dn);
 void bmm_wo_ffn_chain(const BmmArgs& wo, const BmmArgs& gu, const BmmArgs& dn, int* cnt, int* err, hipStream_t s);
 bool bmm_qkv2(const BmmArgs& a, const BmmArgs& b, hipStream_t s);
