@@ -26,6 +26,10 @@ using namespace lfk;
 template <class T>
 static T* P(uintptr_t p) { return reinterpret_cast<T*>(p); }
 static hipStream_t S(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
+// the folded RMSNorm of a bmm form (xf == 0: none)
+static BmmNorm fold(uintptr_t xf, int ldxf, uintptr_t norm, float eps) {
+  return xf ? BmmNorm{P<float>(xf), ldxf, P<float>(norm), eps} : BmmNorm{};
+}
 
 static void hip_ok(const char* what) {
   hipError_t e = hipGetLastError();
@@ -201,6 +205,27 @@ PYBIND11_MODULE(_hip, m) {
              std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(float));
              return a;
            })
+      // the path every layer of a batched step over B rows takes (BatchLayerPlan, read-only: tests and
+      // inspection; the serving path never reads it): one dict per layer
+      .def("batch_plan",
+           [](Engine& e, int B) {
+             py::list out;
+             for (const BatchLayerPlan& p : e.batch_plan(B)) {
+               py::dict d;
+               d["qkv"] = to_string(p.qkv);
+               d["qkv_norm_folded"] = p.qkv_norm_folded;
+               d["qkv_two_launch"] = p.qkv_two_launch;
+               d["finish"] = to_string(p.finish);
+               d["sk_defers_rope"] = p.sk_defers_rope;
+               d["ffn"] = to_string(p.ffn);
+               d["ffn_norm_folded"] = p.ffn_norm_folded;
+               d["wo_rows"] = p.wo_rows;
+               d["tp"] = to_string(p.tp);
+               d["zero_qkv"] = to_string(p.zero_qkv);
+               out.append(d);
+             }
+             return out;
+           })
       .def("step_clk", [](Engine& e) {
         std::vector<long long> v;
         {
@@ -359,23 +384,27 @@ PYBIND11_MODULE(_hip, m) {
                   uintptr_t stream, int debug, uintptr_t h_out, int ldh_out, uintptr_t xf, int ldxf,
                   uintptr_t norm, float eps, bool store_out, uintptr_t dbg_clk, int tr, uintptr_t ew, int ew_ld,
                   int tiles_per_expert, int steps_per_expert, uintptr_t zero, int zero_n) {
+    const QMat wm = make_qmat(P<void>(w), type, rows, K);
+    const BmmNorm nm = fold(xf, ldxf, norm, eps);  // RMSNorm folded into the staging (fp32 rows xf, weights norm)
+    // h_out: the SwiGLU epilogue (gate/up rows in 32-row groups), else a projection into out. ew: the
+    // MoE experts as one matrix (tests/test_moe_paths_gpu.py), routing weights ew [B][ew_ld], the
+    // stacked gate/up's tiles per expert or the K-concatenated down's steps per expert
     BmmArgs a;
+    if (h_out && ew)
+      a = bmm_moe_gate_up_args(wm, P<__half>(xh), ldh, nm, B, P<__half>(h_out), ldh_out, P<float>(ew), ew_ld,
+                               tiles_per_expert);
+    else if (h_out) a = bmm_gate_up_args(wm, P<__half>(xh), ldh, nm, B, P<__half>(h_out), ldh_out);
+    else if (ew)
+      a = bmm_moe_down_args(wm, P<__half>(xh), ldh, P<float>(out), ldo, B, P<float>(zero), zero_n, P<float>(ew), ew_ld,
+                            steps_per_expert);
+    else a = bmm_down_args(wm, P<__half>(xh), ldh, P<float>(out), ldo, B, P<float>(zero), zero_n);
+    if (!h_out) {  // (a test-only form: the head's store epilogue, with or without the folded norm)
+      bmm_fold_norm(a, nm);
+      a.store_out = store_out;
+    }
     a.debug = debug;
     a.tr = tr;
     a.dbg_clk = P<long long>(dbg_clk);
-    a.w = make_qmat(P<void>(w), type, rows, K);
-    // MoE experts as one matrix (tests/test_moe_paths_gpu.py): routing weights ew [B][ew_ld], the
-    // stacked gate/up's tiles per expert or the K-concatenated down's steps per expert
-    a.ew = P<float>(ew); a.ew_ld = ew_ld; a.tiles_per_expert = tiles_per_expert; a.steps_per_expert = steps_per_expert;
-    a.zero = P<float>(zero); a.zero_n = zero_n;
-    a.xh = P<__half>(xh); a.ldh = ldh; a.out = P<float>(out); a.ldo = ldo; a.n_out = rows; a.B = B;
-    if (h_out) {  // SwiGLU epilogue (gate/up rows in 32-row groups)
-      a.swiglu_epi = true; a.h_out = P<__half>(h_out); a.ldh_out = ldh_out;
-    }
-    if (xf) {     // RMSNorm folded into the staging (fp32 rows xf, weights norm)
-      a.xf = P<float>(xf); a.ldxf = ldxf; a.norm_w = P<float>(norm); a.eps = eps;
-    }
-    a.store_out = store_out;
     bmm(a, S(stream));
     hip_ok("bmm");
   }, py::arg("w"), py::arg("type"), py::arg("rows"), py::arg("K"), py::arg("xh"), py::arg("ldh"), py::arg("out"),
@@ -393,16 +422,10 @@ PYBIND11_MODULE(_hip, m) {
   auto chain_args = [](BmmArgs& gu, BmmArgs& dn, uintptr_t wg, int tg, int F, int K, uintptr_t xh, uintptr_t xf,
                        uintptr_t norm, float eps, uintptr_t wd, int td, uintptr_t hout, uintptr_t out, int B, int tr,
                        uintptr_t zero, int zero_n) {
+    gu = bmm_gate_up_args(make_qmat(P<void>(wg), tg, 2 * F, K), P<__half>(xh), K, fold(xf, K, norm, eps), B,
+                          P<__half>(hout), F);
+    dn = bmm_down_args(make_qmat(P<void>(wd), td, K, F), P<__half>(hout), F, P<float>(out), K, B, P<float>(zero), zero_n);
     dn.tr = tr;
-    gu.w = make_qmat(P<void>(wg), tg, 2 * F, K);
-    gu.xh = P<__half>(xh); gu.ldh = K; gu.n_out = 2 * F; gu.B = B;
-    gu.swiglu_epi = true; gu.h_out = P<__half>(hout); gu.ldh_out = F;
-    if (xf) {
-      gu.xf = P<float>(xf); gu.ldxf = K; gu.norm_w = P<float>(norm); gu.eps = eps;
-    }
-    dn.w = make_qmat(P<void>(wd), td, K, F);
-    dn.xh = P<__half>(hout); dn.ldh = F; dn.out = P<float>(out); dn.ldo = K; dn.n_out = K; dn.B = B;
-    dn.zero = P<float>(zero); dn.zero_n = zero_n;
   };
   m.def("bmm_ffn_chain", [chain_args](uintptr_t wg, int tg, int F, int K, uintptr_t xh, uintptr_t xf, uintptr_t norm,
                                       float eps, uintptr_t wd, int td, uintptr_t hout, uintptr_t out, int B,
@@ -426,16 +449,11 @@ PYBIND11_MODULE(_hip, m) {
   auto chain3_args = [](BmmArgs& o, BmmArgs& gu, BmmArgs& dn, uintptr_t wo, int to, int Kwo, uintptr_t xa, uintptr_t wg,
                         int tg, int F, int K, uintptr_t norm, float eps, uintptr_t wd, int td, uintptr_t xh,
                         uintptr_t hout, uintptr_t resid, int B, int tr, uintptr_t zero, int zero_n) {
+    o = bmm_proj_args(make_qmat(P<void>(wo), to, K, Kwo), P<__half>(xa), Kwo, P<float>(resid), K, B);
+    gu = bmm_gate_up_args(make_qmat(P<void>(wg), tg, 2 * F, K), P<__half>(xh), K, fold(resid, K, norm, eps), B,
+                          P<__half>(hout), F);
+    dn = bmm_down_args(make_qmat(P<void>(wd), td, K, F), P<__half>(hout), F, P<float>(resid), K, B, P<float>(zero), zero_n);
     o.tr = dn.tr = tr;
-    o.w = make_qmat(P<void>(wo), to, K, Kwo);
-    o.xh = P<__half>(xa); o.ldh = Kwo; o.out = P<float>(resid); o.ldo = K; o.n_out = K; o.B = B;
-    gu.w = make_qmat(P<void>(wg), tg, 2 * F, K);
-    gu.xh = P<__half>(xh); gu.ldh = K; gu.n_out = 2 * F; gu.B = B;
-    gu.swiglu_epi = true; gu.h_out = P<__half>(hout); gu.ldh_out = F;
-    gu.xf = P<float>(resid); gu.ldxf = K; gu.norm_w = P<float>(norm); gu.eps = eps;
-    dn.w = make_qmat(P<void>(wd), td, K, F);
-    dn.xh = P<__half>(hout); dn.ldh = F; dn.out = P<float>(resid); dn.ldo = K; dn.n_out = K; dn.B = B;
-    dn.zero = P<float>(zero); dn.zero_n = zero_n;
   };
   m.def("bmm_wo_ffn_chain", [chain3_args](uintptr_t wo, int to, int Kwo, uintptr_t xa, uintptr_t wg, int tg, int F, int K,
                                           uintptr_t norm, float eps, uintptr_t wd, int td, uintptr_t xh, uintptr_t hout,
@@ -469,42 +487,18 @@ PYBIND11_MODULE(_hip, m) {
                       uintptr_t bias, bool two_launch) {
     const int n = (int)mats.size();
     if (n < 1 || n > 3) throw std::runtime_error("bmm_qkv: 1 to 3 matrices");
+    if (B > kBmmMaxRows) throw std::runtime_error("bmm_qkv: one row group (B <= 16)");
     QMat mt[3];
-    int off[3] = {0, 0, 0};  // first column of each matrix's rows in an out / bias row
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i)
       mt[i] = make_qmat(P<void>(std::get<0>(mats[i])), std::get<1>(mats[i]), std::get<2>(mats[i]), K);
-      if (i + 1 < n) off[i + 1] = off[i] + mt[i].rows;
-    }
-    std::vector<BmmArgs> rl;
-    for (int i = 0; i < n;) {
-      int j = i + 1;
-      while (j < n && t16_format(mt[j].type) == t16_format(mt[i].type)) ++j;
-      BmmArgs a;
-      a.w = mt[i]; a.xh = P<__half>(xh); a.ldh = ldh;
-      a.out = P<float>(out) + off[i]; a.ldo = ldo; a.n_out = mt[i].rows; a.B = B;
-      a.nseg = j - i;
-      for (int k = 1; k < a.nseg; ++k) {
-        a.seg_base[k] = mt[i + k].base; a.seg_rows[k] = mt[i + k].rows; a.seg_out[k] = P<float>(out) + off[i + k];
-      }
-      if (xf) {
-        a.xf = P<float>(xf); a.ldxf = ldxf; a.norm_w = P<float>(norm); a.eps = eps;
-      }
-      if (fused) {
-        a.qkv_epi = true;
-        for (int k = 0; k < a.nseg; ++k) a.qkv.kind[k] = i + k;
-        a.qkv.q_out = P<float>(q_out); a.qkv.q_ld = q_ld;
-        a.qkv.k_cache = P<__half>(k_cache); a.qkv.v_cache = P<__half>(v_cache); a.qkv.slot_stride = slot_stride;
-        a.qkv.n_ctx = n_ctx; a.qkv.head_dim = head_dim;
-        a.qkv.pos = P<int>(pos); a.qkv.slots = P<int>(slots); a.qkv.rope = P<float2>(rope);
-        if (bias)
-          for (int k = 0; k < a.nseg; ++k) a.qkv.bias[k] = P<float>(bias) + off[i + k];
-      }
-      rl.push_back(a);
-      i = j;
-    }
-    const bool one = two_launch && rl.size() == 2 && bmm_qkv2(rl[0], rl[1], S(stream));
-    if (!one)
-      for (const BmmArgs& a : rl) bmm(a, S(stream));
+    BmmArgs::Qkv epi;
+    epi.q_out = P<float>(q_out); epi.q_ld = q_ld;
+    epi.k_cache = P<__half>(k_cache); epi.v_cache = P<__half>(v_cache); epi.slot_stride = slot_stride;
+    epi.n_ctx = n_ctx; epi.head_dim = head_dim;
+    epi.pos = P<int>(pos); epi.slots = P<int>(slots); epi.rope = P<float2>(rope);
+    const std::vector<BmmArgs> rl = bmm_qkv_runs(mt, n, P<__half>(xh), ldh, fold(xf, ldxf, norm, eps), B, P<float>(out),
+                                                 ldo, fused ? &epi : nullptr, P<float>(bias));
+    const bool one = bmm_launch_runs(rl, two_launch, S(stream));
     hip_ok("bmm_qkv");
     return one;
   }, py::arg("mats"), py::arg("K"), py::arg("B"), py::arg("stream"), py::arg("xh") = 0, py::arg("ldh") = 0,
@@ -754,18 +748,12 @@ PYBIND11_MODULE(_hip, m) {
                          uintptr_t xf, int ldxf, uintptr_t norm, float eps, int B, uintptr_t out, int ldo,
                          uintptr_t ss_out, uintptr_t pos, uintptr_t rope, int head_dim, int n_ctx, uintptr_t stream,
                          uintptr_t zero, int zero_n, uintptr_t dbg_clk, int tr) {
-    BmmArgs a;
+    const QMat m[3] = {make_qmat(P<void>(wq), tq, nq, K), make_qmat(P<void>(wk), tk, nkv, K),
+                       make_qmat(P<void>(wv), tv, nkv, K)};
+    BmmArgs a = bmm_qkv_sk_args(m, fold(xf, ldxf, norm, eps), B, P<float>(out), ldo, P<float>(ss_out), P<int>(pos),
+                                P<float2>(rope), head_dim, n_ctx);
+    a.zero = P<float>(zero); a.zero_n = zero_n;  // (the zero side job on this launch: tests only)
     a.tr = tr;
-    a.w = make_qmat(P<void>(wq), tq, nq, K); a.n_out = nq; a.out = P<float>(out); a.ldo = ldo; a.B = B;
-    a.nseg = 3;
-    a.seg_base[1] = P<uint8_t>(wk); a.seg_rows[1] = nkv; a.seg_out[1] = P<float>(out) + nq;
-    a.seg_base[2] = P<uint8_t>(wv); a.seg_rows[2] = nkv; a.seg_out[2] = P<float>(out) + nq + nkv;
-    a.seg_split = tk != tq ? 1 : tv != tq ? 2 : 3;
-    a.type2 = tk != tq ? tk : tv != tq ? tv : 0;
-    a.qkv_sk = true;
-    a.qkv.pos = P<int>(pos); a.qkv.rope = P<float2>(rope); a.qkv.head_dim = head_dim; a.qkv.n_ctx = n_ctx;
-    a.xf = P<float>(xf); a.ldxf = ldxf; a.norm_w = P<float>(norm); a.eps = eps; a.ss_out = P<float>(ss_out);
-    a.zero = P<float>(zero); a.zero_n = zero_n;
     a.dbg_clk = P<long long>(dbg_clk);
     bmm(a, S(stream));
     hip_ok("bmm_qkv_sk");

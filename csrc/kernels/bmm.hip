@@ -2330,10 +2330,15 @@ void bmm_wo_ffn_chain(const BmmArgs& wo0, const BmmArgs& gu0, const BmmArgs& dn0
   else hipLaunchKernelGGL((bmm_chain3_kernel<T_Q4_K, T_Q4_K, T_Q4_K>), grid, dim3(512), lds, s, wo, gu, dn);
 }
 
-bool bmm_qkv2(const BmmArgs& a0, const BmmArgs& b0, hipStream_t s) {
-  if (!a0.qkv_epi || !b0.qkv_epi || a0.B != b0.B || a0.w.K != b0.w.K || a0.n_out <= 0 || b0.n_out <= 0)
-    return false;
-  if ((a0.xf == nullptr) != (b0.xf == nullptr)) return false;
+bool bmm_qkv2_supported(const BmmArgs& a, const BmmArgs& b) {
+  if (!a.qkv_epi || !b.qkv_epi || a.B != b.B || a.w.K != b.w.K || a.n_out <= 0 || b.n_out <= 0) return false;
+  if ((a.xf == nullptr) != (b.xf == nullptr)) return false;
+  const int tb = t16_kernel_type(b.w.type);
+  return t16_kernel_type(a.w.type) == T_Q4_K && (tb == T_Q6_K || tb == T_Q5_K);
+}
+
+void bmm_qkv2(const BmmArgs& a0, const BmmArgs& b0, hipStream_t s) {
+  if (!bmm_qkv2_supported(a0, b0)) throw std::runtime_error("bmm_qkv2: unsupported pair");
   BmmArgs a = a0, b = b0;
   bmm_check(a);
   bmm_check(b);
@@ -2354,11 +2359,8 @@ bool bmm_qkv2(const BmmArgs& a0, const BmmArgs& b0, hipStream_t s) {
   int nbb = std::min(tb, std::max(1, cap - na));
   a.nb1 = na;
   const dim3 grid(na + nbb), blk(512);
-  const int ta_ = t16_kernel_type(a.w.type), tb_ = t16_kernel_type(b.w.type);
-  if (ta_ == T_Q4_K && tb_ == T_Q6_K) hipLaunchKernelGGL((bmm_kernel<T_Q4_K, 8, 1, T_Q6_K>), grid, blk, lds, s, a, b);
-  else if (ta_ == T_Q4_K && tb_ == T_Q5_K) hipLaunchKernelGGL((bmm_kernel<T_Q4_K, 8, 1, T_Q5_K>), grid, blk, lds, s, a, b);
-  else return false;
-  return true;
+  if (t16_kernel_type(b.w.type) == T_Q6_K) hipLaunchKernelGGL((bmm_kernel<T_Q4_K, 8, 1, T_Q6_K>), grid, blk, lds, s, a, b);
+  else hipLaunchKernelGGL((bmm_kernel<T_Q4_K, 8, 1, T_Q5_K>), grid, blk, lds, s, a, b);
 }
 
 // ---------------------------------------------------------------- prefill GEMM on the tile16 copy

@@ -10,6 +10,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "../common.h"
 
@@ -226,9 +227,6 @@ bool bmm_supported(int type, int K);
 bool bmm_qkv_fits(int K, int B);   // the Q|K|V epilogue needs one K part (x slice in LDS)
 bool bmm_norm_fits(int K, int B);  // one K part + the folded RMSNorm's staging shape
 void bmm(const BmmArgs& a, hipStream_t s);
-// two one-part Q|K|V runs of different weight types (Q|K Q4_K + V Q6_K / Q5_K: the bumped
-// layers of the K-quant mixes) in one launch; false = unsupported pair or shape (caller
-// launches them one by one)
 // The dense SwiGLU gate/up (gu, swiglu_epi) and the down projection over its output (dn) in ONE
 // launch with a per-K-part in-launch hand-off (BmmArgs::chain_*). cnt: kChainInts ints, zero
 // before the launch (kChainXcds counters per K part, each on a 128-B line of its own); err: host-mapped
@@ -253,7 +251,47 @@ void bmm_ffn_chain(const BmmArgs& gu, const BmmArgs& dn, int* cnt, int* err, hip
 // at most kChainWoPart (14) - the counters of part 14 count the finished Wo blocks.
 bool bmm_wo_ffn_chain_supported(const BmmArgs& wo, const BmmArgs& gu, const BmmArgs& dn);
 void bmm_wo_ffn_chain(const BmmArgs& wo, const BmmArgs& gu, const BmmArgs& dn, int* cnt, int* err, hipStream_t s);
-bool bmm_qkv2(const BmmArgs& a, const BmmArgs& b, hipStream_t s);
+// two one-part Q|K|V runs of different weight types (Q|K Q4_K + V Q6_K / Q5_K: the bumped
+// layers of the K-quant mixes) in one launch; unsupported pair or shape: the caller launches
+// them one by one
+bool bmm_qkv2_supported(const BmmArgs& a, const BmmArgs& b);
+void bmm_qkv2(const BmmArgs& a, const BmmArgs& b, hipStream_t s);  // throws unless bmm_qkv2_supported
+// ---- the BmmArgs of a batched decode layer's projections (bmm_args.cpp), one builder per form.
+// The engine calls them with its buffers, the test bindings with the test's pointers; dbg_clk,
+// tr and debug are the caller's to set on what they return.
+struct BmmNorm {                   // RMSNorm folded into the x staging (xf == nullptr: none, xh is read)
+  const float* xf = nullptr;
+  int ldxf = 0;
+  const float* norm_w = nullptr;
+  float eps = 1e-5f;
+};
+void bmm_fold_norm(BmmArgs& a, const BmmNorm& norm);
+// split-K Q|K|V (qkv_sk) over m = {Q, K, V}: RoPE'd partial sums into out [B][ldo] (Q at 0, K at
+// Q's rows, V after K's), the rows' sums of squares into ss_out; seg_split / type2 from t16_format
+BmmArgs bmm_qkv_sk_args(const QMat m[3], const BmmNorm& norm, int B, float* out, int ldo, float* ss_out,
+                        const int* pos, const float2* rope, int head_dim, int n_ctx);
+// one-part / unfused Q|K|V over n <= 3 matrices: one run per stretch of equal tile16 format and row
+// group of kBmmMaxRows, in launch order. epi == nullptr: the runs accumulate into out [B][ldo]
+// (matrix i at the rows before it). Else the one-part epilogue: *epi holds row 0's q_out / pos /
+// slots, the caches, rope and sizes - kind, the row groups' offsets and the segments' slices of
+// `bias` (one f32 vector laid out as an out row, or null) are filled in here.
+std::vector<BmmArgs> bmm_qkv_runs(const QMat* m, int n, const __half* xh, int ldh, const BmmNorm& norm, int B,
+                                  float* out, int ldo, const BmmArgs::Qkv* epi, const float* bias);
+// launches a run list: two runs in one launch (bmm_qkv2) when try_two and it takes them - the
+// return value - else one bmm per run
+bool bmm_launch_runs(const std::vector<BmmArgs>& runs, bool try_two, hipStream_t s);
+// plain split-K projection into out (Wo, one row group of a wider batch), n_out = w.rows
+BmmArgs bmm_proj_args(const QMat& w, const __half* xh, int ldh, float* out, int ldo, int B);
+// dense gate/up on the SwiGLU epilogue: silu(gate) * up as f16 into h_out [B][ldh_out]
+BmmArgs bmm_gate_up_args(const QMat& w, const __half* xh, int ldh, const BmmNorm& norm, int B, __half* h_out,
+                         int ldh_out);
+// down projection, with the optional zero side job (zero == nullptr: none)
+BmmArgs bmm_down_args(const QMat& w, const __half* xh, int ldh, float* out, int ldo, int B, float* zero, int zero_n);
+// MoE: the experts' stacked gate/up and K-concatenated down, routed by ew [B][ew_ld]
+BmmArgs bmm_moe_gate_up_args(const QMat& w, const __half* xh, int ldh, const BmmNorm& norm, int B, __half* h_out,
+                             int ldh_out, const float* ew, int ew_ld, int tiles_per_expert);
+BmmArgs bmm_moe_down_args(const QMat& w, const __half* xh, int ldh, float* out, int ldo, int B, float* zero,
+                          int zero_n, const float* ew, int ew_ld, int steps_per_expert);
 // the split-K Q|K|V leaves its sums un-RoPE'd (the batched attention rotates q and the new key:
 // AttnDecodeArgs::rope) - the interleaved-step kernels, whose loop then loads weights only
 bool bmm_qkv_sk_defers_rope();

@@ -1211,29 +1211,13 @@ void Engine::begin_slot_state(int slot, const std::vector<int>& prompt, const Sa
 }
 
 // bmm over B rows: groups of kBmmMaxRows columns (one more weight stream per group)
-void Engine::bmm_rows(const QMat& w, const __half* xh, int ldh, float* out, int ldo, int n_out, int B,
-                      hipStream_t s, long long* dbg) {
+void Engine::bmm_rows(const QMat& w, const __half* xh, int ldh, float* out, int ldo, int B, hipStream_t s,
+                      long long* dbg) {
   for (int b0 = 0; b0 < B; b0 += kBmmMaxRows) {
-    BmmArgs a;
+    BmmArgs a = bmm_proj_args(w, xh + (size_t)b0 * ldh, ldh, out + (size_t)b0 * ldo, ldo, std::min(kBmmMaxRows, B - b0));
     a.dbg_clk = b0 == 0 ? dbg : nullptr;
-    a.w = w; a.xh = xh + (size_t)b0 * ldh; a.ldh = ldh;
-    a.out = out + (size_t)b0 * ldo; a.ldo = ldo; a.n_out = n_out;
-    a.B = std::min(kBmmMaxRows, B - b0);
     bmm(a, s);
   }
-}
-
-// the down projection (split-K into the residual); with the split-K Q|K|V (`zero_qkv`) its blocks
-// also re-zero qkv_b_ / ss_b_ for the next layer (the attention, their only reader, has finished)
-void Engine::down_rows(const QMat& w, const __half* xh, int ldh, float* out, int B, hipStream_t s, bool zero_qkv,
-                       long long* dbg) {
-  const int d = hp_.n_embd;
-  BmmArgs a;
-  a.w = w; a.xh = xh; a.ldh = ldh; a.out = out; a.ldo = d; a.n_out = d; a.B = B; a.dbg_clk = dbg;
-  if (zero_qkv) {
-    a.zero = qkv_b_; a.zero_n = (int)qkv_b_zero_n();
-  }
-  bmm(a, s);
 }
 
 void Engine::bprep_rows(const float* x, int ldx, bool swiglu, const float* norm_w, int K, int B, float* zero,
@@ -1245,12 +1229,13 @@ void Engine::bprep_rows(const float* x, int ldx, bool swiglu, const float* norm_
   bprep(p, s);
 }
 
-// One layer of batch_step on the MFMA batched projections (bmm.hip). Every projection input
-// is prepared once (bprep: norm / SwiGLU, f16) and that launch also zeroes the split-K output
-// of the projection it feeds (qkv_, gu_b_); Wo and down accumulate into the residual x_.
-void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
+// Which path layer l of a batched step over B rows takes: every predicate, option and environment
+// switch of the batched layer is asked here and nowhere else (docs/DESIGN.md tabulates the values).
+BatchLayerPlan Engine::plan_batch_layer(int l, int B) const {
+  using P = BatchLayerPlan;
   const Layer& L = layers_[l];
-  const int d = hp_.n_embd, hd = hp_.head_dim, ncol = nq_ + 2 * nkvd_;
+  const int d = hp_.n_embd;
+  P p;
   // row-parallel Wo / down under TP: accumulate this rank's partial into tmp_ (holding the
   // residual on rank 0, zeros elsewhere), then all-reduce into x_
   // P2P path: the partials go to tmp_b_, which the accumulating all-reduce (x_ += sum) leaves zeroed
@@ -1258,101 +1243,158 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
   // rank 0's tmp_, zeros the others', and the all-reduce stores the sum into x_.
   const bool tp = tp_on_;
   const bool tp_acc = tp && tmp_b_ && p2p_ && p2p_->ready() && (size_t)B * d <= (size_t)p2p_->max_n();
-  float* acc = tp_acc ? tmp_b_ : tp ? tmp_ : x_;
-  auto tp_begin = [&]() {
-    if (!tp || tp_acc) return;
-    if (opt_.tp_rank == 0) HIPCHK(hipMemcpyAsync(tmp_, x_, sizeof(float) * B * d, hipMemcpyDeviceToDevice, s));
-    else HIPCHK(hipMemsetAsync(tmp_, 0, sizeof(float) * B * d, s));
-  };
-  auto tp_end = [&]() {
-    if (tp_acc) p2p_->allreduce_add(tmp_b_, x_, B * d, s);
-    else if (tp) allreduce_into(tmp_, x_, (size_t)B * d, s);
-  };
-  const size_t kv_layer = (size_t)nkv_l_ * opt_.n_ctx * hd;
-  __half* kcl = kc_ + kv_layer * (l - opt_.layer_begin);  // slot 0's layer l; the kernels add slot * slot_stride_
-  __half* vcl = vc_ + kv_layer * (l - opt_.layer_begin);
+  p.tp = tp_acc ? P::Tp::p2p_accumulate : tp ? P::Tp::rccl : P::Tp::none;
   // RoPE + KV append in the Q|K|V epilogue when the whole K fits one LDS-staged part
   const bool fused = B <= kBmmMaxRows && bmm_qkv_fits(d, B);
   // attention / FFN RMSNorm folded into the one-part projections' x staging (no prep launch)
   const bool fnorm = fused && bmm_norm_fits(d, B);
-  // the Q|K|V side of both, which a QK-norm layer (qwen3) declines: the epilogue's tile holds 16 rows
-  // of a head, never the head - such a layer takes bprep + bmm + the head-norm kernel as a model
-  // too wide for one part does (its FFN keeps `fused` / `fnorm`)
-  const bool qepi = fused && !L.qkn, qfnorm = fnorm && !L.qkn;
   // Q|K|V split over K (the default at B <= 8): RoPE'd partial sums into qkv_b_, normalised and
   // appended to the caches by the attention
   // (Q|K|V biases: only with the RoPE deferred to the attention, which adds them to the normalised
   // sums before rotating; the form with rotated partials takes the one-part / unfused path)
   const bool sk = qkv_sk_ && bmm_qkv_sk_supported(L.t_wq.type, L.t_wk.type, L.t_wv.type, d, B) &&
                   (!(L.bqkv || L.qkn) || bmm_qkv_sk_defers_rope());
-  // FFN paths without the down projection's zero side job: a memset node re-zeroes qkv_b_ / ss_b_
-  auto zero_qkv = [&]() {
-    if (sk) HIPCHK(hipMemsetAsync(qkv_b_, 0, sizeof(float) * qkv_b_zero_n(), s));
-  };
   if (sk) {
-    BmmArgs a;
-    a.w = L.t_wq; a.n_out = L.t_wq.rows; a.out = qkv_b_; a.ldo = ncol; a.B = B;
-    a.nseg = 3;
-    a.seg_base[1] = L.t_wk.base; a.seg_rows[1] = L.t_wk.rows; a.seg_out[1] = qkv_b_ + nq_;
-    a.seg_base[2] = L.t_wv.base; a.seg_rows[2] = L.t_wv.rows; a.seg_out[2] = qkv_b_ + nq_ + nkvd_;
-    // runs of equal tile16 format (Q4_0 / Q4_1 copies are in the Q4_K format, Q5_0 / Q5_1 in Q5_K's)
-    const int tq = t16_format(L.t_wq.type), tk = t16_format(L.t_wk.type), tv = t16_format(L.t_wv.type);
-    a.seg_split = tk != tq ? 1 : tv != tq ? 2 : 3;
-    a.type2 = tk != tq ? tk : tv != tq ? tv : 0;
-    a.qkv_sk = true;
-    a.qkv.pos = bpos_; a.qkv.rope = rope_; a.qkv.head_dim = hd; a.qkv.n_ctx = opt_.n_ctx;
-    a.xf = x_; a.ldxf = d; a.norm_w = L.attn_norm; a.eps = hp_.rms_eps; a.ss_out = ss_b_;
-    a.dbg_clk = clk_of(l, 0);
-    bmm(a, s);
+    p.qkv = P::Qkv::split_k;
+    p.qkv_norm_folded = true;
+    p.sk_defers_rope = bmm_qkv_sk_defers_rope();
   } else {
-    if (!qfnorm) bprep_rows(x_, d, false, L.attn_norm, d, B, qepi ? nullptr : qkv_, qepi ? 0 : B * ncol, s);
-    // Q|K|V: one launch per run of equal weight type (Q4_K_M: one, or Q|K + V on bumped layers;
-    // a side-stream graph branch for the V run measured no gain)
-    const QMat* m[3] = {&L.t_wq, &L.t_wk, &L.t_wv};
-    float* o[3] = {qkv_, qkv_ + nq_, qkv_ + nq_ + nkvd_};
-    std::vector<BmmArgs> rl;
-    for (int i = 0; i < 3;) {
-      int j = i + 1;
-      while (j < 3 && t16_format(m[j]->type) == t16_format(m[i]->type)) ++j;
-      for (int b0 = 0; b0 < B; b0 += kBmmMaxRows) {
-        BmmArgs a;
-        a.w = *m[i]; a.xh = xh_b_ + (size_t)b0 * d; a.ldh = d;
-        a.out = o[i] + (size_t)b0 * ncol; a.ldo = ncol; a.n_out = m[i]->rows;
-        a.B = std::min(kBmmMaxRows, B - b0);
-        a.nseg = j - i;
-        for (int k = 1; k < a.nseg; ++k) {
-          a.seg_base[k] = m[i + k]->base; a.seg_rows[k] = m[i + k]->rows; a.seg_out[k] = o[i + k] + (size_t)b0 * ncol;
-        }
-        if (qfnorm) {
-          a.xf = x_ + (size_t)b0 * d; a.ldxf = d; a.norm_w = L.attn_norm; a.eps = hp_.rms_eps;
-        }
-        if (rl.empty() && b0 == 0) a.dbg_clk = clk_of(l, 0);
-        if (qepi) {
-          a.qkv_epi = true;
-          for (int k = 0; k < a.nseg; ++k) a.qkv.kind[k] = i + k;
-          a.qkv.q_out = q_ + (size_t)b0 * nq_; a.qkv.q_ld = nq_;
-          a.qkv.k_cache = kcl; a.qkv.v_cache = vcl; a.qkv.slot_stride = slot_stride_;
-          a.qkv.n_ctx = opt_.n_ctx; a.qkv.head_dim = hd;
-          a.qkv.pos = bpos_ + b0; a.qkv.slots = bslots_ + b0; a.qkv.rope = rope_;
-          if (L.bqkv) {
-            const float* bias[3] = {L.bqkv, L.bqkv + nq_, L.bqkv + nq_ + nkvd_};
-            for (int k = 0; k < a.nseg; ++k) a.qkv.bias[k] = bias[i + k];
-          }
-        }
-        rl.push_back(a);
-      }
-      i = j;
-    }
+    // a QK-norm layer (qwen3) declines the epilogue and its folded norm: the epilogue's tile holds 16
+    // rows of a head, never the head - such a layer takes bprep + bmm + the head-norm kernel as a
+    // model too wide for one part does (its FFN keeps `fused` / `fnorm`)
+    const bool qepi = fused && !L.qkn;
+    p.qkv = qepi ? P::Qkv::epilogue : P::Qkv::unfused;
+    p.qkv_norm_folded = fnorm && !L.qkn;
+    p.finish = L.qkn ? P::Finish::qk_norm_rope_kv : qepi ? P::Finish::none : P::Finish::rope_kv_prefill;
     // bumped layers (Q|K Q4_K + V Q6_K): both runs in one launch
-    if (!(rl.size() == 2 && B <= kBmmMaxRows && bmm_qkv2(rl[0], rl[1], s)))
-      for (const BmmArgs& a : rl) bmm(a, s);
-    if (L.qkn)
+    if (qepi) {
+      const std::vector<BmmArgs> rl = batch_qkv_runs(l, B, p);
+      p.qkv_two_launch = rl.size() == 2 && bmm_qkv2_supported(rl[0], rl[1]);
+    }
+  }
+  const bool moe = moe_b_ && fused, dense = !moe && bg_ffn_ && fused;
+  p.wo_rows = B > kBmmMaxRows;
+  // the down projection's blocks re-zero qkv_b_ / ss_b_ for the next layer as a side job (the attention,
+  // their only reader, has finished); the grouped FFN has no such down: a memset node does it
+  p.zero_qkv = !sk ? P::ZeroQkv::nobody : moe || bg_ffn_ ? P::ZeroQkv::down : P::ZeroQkv::memset;
+  if (dense) {
+    p.ffn = P::Ffn::swiglu;
+    p.ffn_norm_folded = fnorm;
+    const BatchFfnArgs a = batch_ffn_args(l, B, p);
+    // (under TP with more than two ranks on ONE GPU - the eight-rank rehearsal - the chain's down
+    // blocks, waiting on their gate/up, and the peers' spinning collectives can hold each other's
+    // CUs: a 2 s chain timeout in r5; the same rule as tp_epilogue's)
+    const bool tp_chain = tp_acc && !(p2p_->shared_device() && p2p_->world() > 2);
+    if (ffn_chain_ >= 2 && !tp && fnorm && bmm_wo_ffn_chain_supported(a.wo, a.gu, a.dn)) p.ffn = P::Ffn::wo_ffn_chain;
+    else if (ffn_chain_ >= 1 && (!tp || tp_chain) && bmm_ffn_chain_supported(a.gu, a.dn)) p.ffn = P::Ffn::ffn_chain;
+  } else if (moe) {
+    p.ffn = P::Ffn::moe_stacked;
+    p.ffn_norm_folded = fnorm;
+  } else {
+    // MoE without the stacked copies (or unsupported FFN types): the grouped-GEMM FFN of the prompt path
+    p.ffn = bg_ffn_ ? P::Ffn::prep : P::Ffn::grouped;
+  }
+  return p;
+}
+
+std::vector<BatchLayerPlan> Engine::batch_plan(int B) {
+  ExecGuard g(this);
+  if (!bg_ || B < 1 || B > bmax_) throw std::runtime_error("batch_plan: no batched step of that many rows");
+  std::vector<BatchLayerPlan> v;
+  for (int l = 0; l < hp_.n_layer; ++l) v.push_back(plan_batch_layer(l, B));
+  return v;
+}
+
+// the one-part / unfused Q|K|V runs of layer l over the engine's buffers
+std::vector<BmmArgs> Engine::batch_qkv_runs(int l, int B, const BatchLayerPlan& p) const {
+  const Layer& L = layers_[l];
+  const int d = hp_.n_embd, ncol = nq_ + 2 * nkvd_;
+  const QMat m[3] = {L.t_wq, L.t_wk, L.t_wv};
+  BmmNorm norm;
+  if (p.qkv_norm_folded) norm = {x_, d, L.attn_norm, hp_.rms_eps};
+  BmmArgs::Qkv epi;
+  epi.q_out = q_; epi.q_ld = nq_;
+  epi.k_cache = batch_kv(kc_, l); epi.v_cache = batch_kv(vc_, l); epi.slot_stride = slot_stride_;
+  epi.n_ctx = opt_.n_ctx; epi.head_dim = hp_.head_dim;
+  epi.pos = bpos_; epi.slots = bslots_; epi.rope = rope_;
+  return bmm_qkv_runs(m, 3, xh_b_, d, norm, B, qkv_, ncol, p.qkv == BatchLayerPlan::Qkv::epilogue ? &epi : nullptr,
+                      L.bqkv);
+}
+
+// Wo and, on the SwiGLU epilogue paths (dense or stacked MoE), gate/up and down of layer l
+Engine::BatchFfnArgs Engine::batch_ffn_args(int l, int B, const BatchLayerPlan& p) const {
+  using P = BatchLayerPlan;
+  const Layer& L = layers_[l];
+  const int d = hp_.n_embd, E = hp_.n_expert;
+  float* acc = batch_acc(p);
+  float* zero =p.zero_qkv == P::ZeroQkv::down ? qkv_b_ : nullptr;
+  const int zero_n = (int)qkv_b_zero_n();
+  BmmNorm norm;
+  if (p.ffn_norm_folded) norm = {x_, d, L.ffn_norm, hp_.rms_eps};
+  BatchFfnArgs a;
+  if (!p.wo_rows) a.wo = bmm_proj_args(L.t_wo, xh_b_, nq_, acc, d, B);
+  a.wo.dbg_clk = clk_of(l, 2);
+  if (p.ffn == P::Ffn::moe_stacked) {
+    a.gu = bmm_moe_gate_up_args(L.t_gu, xh_b_, d, norm, B, hh_b_, E * F_l_, ew_b_, E, 2 * F_l_ / 16);
+    a.dn = bmm_moe_down_args(L.t_down, hh_b_, E * F_l_, acc, d, B, zero, zero_n, ew_b_, E, F_l_ / 256);
+  } else if (p.ffn == P::Ffn::prep) {
+    a.dn = bmm_down_args(L.t_down, xh_b_, F_l_, acc, d, B, zero, zero_n);
+  } else if (p.ffn != P::Ffn::grouped) {
+    // SwiGLU in the gate/up epilogue: one K part, silu(gate) * up straight to the down
+    // projection's f16 input (hh_b_; xh_b_ is still being read by other blocks)
+    a.gu = bmm_gate_up_args(L.t_gu, xh_b_, d, norm, B, hh_b_, F_l_);
+    a.gu.dbg_clk = clk_of(l, 3);
+    a.dn = bmm_down_args(L.t_down, hh_b_, F_l_, acc, d, B, zero, zero_n);
+    a.dn.dbg_clk = clk_of(l, 4);
+  }
+  return a;
+}
+
+// One layer of batch_step on the MFMA batched projections (bmm.hip), as plan_batch_layer decided:
+// Q|K|V, attention, Wo + FFN. Every projection input that is not folded into its projection is
+// prepared once (bprep: norm / SwiGLU, f16) and that launch also zeroes the split-K output of
+// the projection it feeds (qkv_, gu_b_); Wo and down accumulate into the residual x_.
+void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
+  using P = BatchLayerPlan;
+  const P p = plan_batch_layer(l, B);
+  const Layer& L = layers_[l];
+  const int d = hp_.n_embd, hd = hp_.head_dim, ncol = nq_ + 2 * nkvd_;
+  __half* kcl = batch_kv(kc_, l);
+  __half* vcl = batch_kv(vc_, l);
+  // ---- Q|K|V
+  switch (p.qkv) {
+    case P::Qkv::split_k: {
+      const QMat m[3] = {L.t_wq, L.t_wk, L.t_wv};
+      BmmArgs a = bmm_qkv_sk_args(m, {x_, d, L.attn_norm, hp_.rms_eps}, B, qkv_b_, ncol, ss_b_, bpos_, rope_, hd,
+                                  opt_.n_ctx);
+      a.dbg_clk = clk_of(l, 0);
+      bmm(a, s);
+      break;
+    }
+    case P::Qkv::epilogue:
+    case P::Qkv::unfused: {
+      const bool epi = p.qkv == P::Qkv::epilogue;
+      if (!p.qkv_norm_folded) bprep_rows(x_, d, false, L.attn_norm, d, B, epi ? nullptr : qkv_, epi ? 0 : B * ncol, s);
+      // one launch per run of equal weight type (Q4_K_M: one, or Q|K + V on bumped layers; a
+      // side-stream graph branch for the V run measured no gain)
+      std::vector<BmmArgs> rl = batch_qkv_runs(l, B, p);
+      rl[0].dbg_clk = clk_of(l, 0);
+      bmm_launch_runs(rl, p.qkv_two_launch, s);
+      break;
+    }
+  }
+  switch (p.finish) {
+    case P::Finish::none: break;
+    case P::Finish::qk_norm_rope_kv:
       qk_norm_rope_kv(qkv_, B, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, kcl, vcl, s, bpos_, bslots_,
                       slot_stride_);
-    else if (!fused)
+      break;
+    case P::Finish::rope_kv_prefill:
       rope_kv_prefill(qkv_, B, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, bpos_, bslots_, slot_stride_,
                       L.bqkv);
+      break;
   }
+  // ---- attention
   AttnDecodeArgs aa;
   aa.q = q_; aa.k_cache = kcl; aa.v_cache = vcl; aa.pos = bpos_;
   aa.n_ctx = opt_.n_ctx; aa.n_head = nh_l_; aa.n_kv_head = nkv_l_; aa.head_dim = hd;
@@ -1363,10 +1405,10 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
   aa.part_stride = attn_decode_workspace_floats(opt_.n_ctx, nh_l_, hd);
   aa.out_h = xh_b_; aa.out_h_stride = nq_;   // the Wo input, already in bmm's f16 layout
   aa.out = nullptr;                          // (nothing reads an f32 copy of it)
-  if (sk) {
+  if (p.qkv == P::Qkv::split_k) {
     aa.qkv_raw = qkv_b_; aa.qkv_ld = ncol; aa.k_off = nq_; aa.v_off = nq_ + nkvd_;
     aa.ss = ss_b_; aa.inv_k = 1.f / (float)d; aa.eps = hp_.rms_eps;
-    if (bmm_qkv_sk_defers_rope()) aa.rope_freq = rope_freq_;
+    if (p.sk_defers_rope) aa.rope_freq = rope_freq_;
     aa.qkv_bias = L.bqkv;
     aa.qk_norm = L.qkn; aa.qkn_eps = hp_.rms_eps;
   }
@@ -1377,100 +1419,66 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
   // ms, r4: the in-launch hand-off costs what the boundary did and the weight stream slowed the
   // attention's K / V loads)
   attn_decode(aa, s);
-  // dense FFN on the SwiGLU epilogue path: its gate/up and down (and, ffn_chain_ 2, Wo before them)
-  BmmArgs wo, gu, dn;
-  wo.w = L.t_wo; wo.xh = xh_b_; wo.ldh = nq_; wo.out = acc; wo.ldo = d; wo.n_out = d; wo.B = B;
-  wo.dbg_clk = clk_of(l, 2);
-  const bool dense_ffn = !(moe_b_ && fused) && bg_ffn_ && fused;
-  if (dense_ffn) {
-    if (fnorm) {
-      gu.xf = x_; gu.ldxf = d; gu.norm_w = L.ffn_norm; gu.eps = hp_.rms_eps;
-    }
-    gu.w = L.t_gu; gu.xh = xh_b_; gu.ldh = d;
-    gu.out = nullptr; gu.ldo = 0; gu.n_out = 2 * F_l_; gu.B = B;
-    gu.swiglu_epi = true; gu.h_out = hh_b_; gu.ldh_out = F_l_;
-    gu.dbg_clk = clk_of(l, 3);
-    dn.w = L.t_down; dn.xh = hh_b_; dn.ldh = F_l_; dn.out = acc; dn.ldo = d; dn.n_out = d; dn.B = B;
-    dn.dbg_clk = clk_of(l, 4);
-    if (sk) {  // (the down projection re-zeroes the split-K Q|K|V rows for the next layer)
-      dn.zero = qkv_b_; dn.zero_n = (int)qkv_b_zero_n();
-    }
-    // Wo, gate/up and down in ONE launch: the gate/up blocks start on the CUs the Wo frees and issue
-    // their weights while the last Wo partials land (bmm_wo_ffn_chain)
-    if (ffn_chain_ >= 2 && !tp && fnorm && B <= kBmmMaxRows && bmm_wo_ffn_chain_supported(wo, gu, dn)) {
-      bmm_wo_ffn_chain(wo, gu, dn, chain_cnt_ + kChainInts * l, chain_err_, s);
-      return;
-    }
-  }
-  tp_begin();
-  if (B <= kBmmMaxRows) bmm(wo, s);
-  else bmm_rows(L.t_wo, xh_b_, nq_, acc, d, d, B, s, clk_of(l, 2));
-  tp_end();
-  if (moe_b_ && fused) {
-    // MoE: dense per-row expert weights (f32 router on the normed rows), then every expert's
-    // SwiGLU rows in ONE gate/up launch (epilogue scaled by the row's weight for that expert,
-    // 0 when unrouted) and ONE down launch over the K-concatenated experts (parts of unrouted
-    // experts skipped): two weight streams per layer instead of a GEMM pair per expert
-    const int E = hp_.n_expert;
-    moe_router_rows(x_, d, B, L.ffn_norm, hp_.rms_eps, reinterpret_cast<const float*>(L.router.base), d, E,
-                    hp_.n_expert_used, ew_b_, E, s);
-    BmmArgs a;
-    if (fnorm) {
-      a.xf = x_; a.ldxf = d; a.norm_w = L.ffn_norm; a.eps = hp_.rms_eps;
-    } else {
-      bprep_rows(x_, d, false, L.ffn_norm, d, B, nullptr, 0, s);
-    }
-    a.w = L.t_gu; a.xh = xh_b_; a.ldh = d;
-    a.out = nullptr; a.ldo = 0; a.n_out = L.t_gu.rows; a.B = B;
-    a.swiglu_epi = true; a.h_out = hh_b_; a.ldh_out = E * F_l_;
-    a.ew = ew_b_; a.ew_ld = E; a.tiles_per_expert = 2 * F_l_ / 16;
-    bmm(a, s);
+  // ---- Wo + FFN
+  const BatchFfnArgs f = batch_ffn_args(l, B, p);
+  auto tp_begin = [&]() {
+    if (p.tp != P::Tp::rccl) return;
+    if (opt_.tp_rank == 0) HIPCHK(hipMemcpyAsync(tmp_, x_, sizeof(float) * B * d, hipMemcpyDeviceToDevice, s));
+    else HIPCHK(hipMemsetAsync(tmp_, 0, sizeof(float) * B * d, s));
+  };
+  auto tp_end = [&]() {
+    if (p.tp == P::Tp::p2p_accumulate) p2p_->allreduce_add(tmp_b_, x_, B * d, s);
+    else if (p.tp == P::Tp::rccl) allreduce_into(tmp_, x_, (size_t)B * d, s);
+  };
+  if (p.ffn != P::Ffn::wo_ffn_chain) {
     tp_begin();
-    BmmArgs dn;
-    dn.w = L.t_down; dn.xh = hh_b_; dn.ldh = E * F_l_;
-    dn.out = acc; dn.ldo = d; dn.n_out = d; dn.B = B;
-    dn.ew = ew_b_; dn.ew_ld = E; dn.steps_per_expert = F_l_ / 256;
-    if (sk) {  // (the wave-owned down re-zeroes the split-K Q|K|V rows as a side job)
-      dn.zero = qkv_b_; dn.zero_n = (int)qkv_b_zero_n();
-    }
-    bmm(dn, s);
+    if (p.wo_rows) bmm_rows(L.t_wo, xh_b_, nq_, batch_acc(p), d, B, s, clk_of(l, 2));
+    else bmm(f.wo, s);
     tp_end();
-    return;
   }
-  if (dense_ffn) {
-    // SwiGLU in the gate/up epilogue: one K part, silu(gate) * up straight to the down
-    // projection's f16 input (hh_b_; xh_b_ is still being read by other blocks)
-    if (!fnorm) bprep_rows(x_, d, false, L.ffn_norm, d, B, nullptr, 0, s);
-    // gate/up and down in ONE launch, the down blocks waiting per K part on the gate/up tiles
-    // they read (bmm_ffn_chain): the down weight stream starts under the gate/up's last tiles
-    // instead of after a kernel boundary
-    // (under TP with more than two ranks on ONE GPU - the eight-rank rehearsal - the chain's down
-    // blocks, waiting on their gate/up, and the peers' spinning collectives can hold each other's
-    // CUs: a 2 s chain timeout in r5; the same rule as tp_epilogue's)
-    const bool tp_chain = tp_acc && !(p2p_->shared_device() && p2p_->world() > 2);
-    if (ffn_chain_ >= 1 && (!tp || tp_chain) && bmm_ffn_chain_supported(gu, dn)) {
-      bmm_ffn_chain(gu, dn, chain_cnt_ + kChainInts * l, chain_err_, s);
+  int* cnt = chain_cnt_ + kChainInts * l;
+  switch (p.ffn) {
+    case P::Ffn::wo_ffn_chain:
+      // Wo, gate/up and down in ONE launch: the gate/up blocks start on the CUs the Wo frees and issue
+      // their weights while the last Wo partials land
+      bmm_wo_ffn_chain(f.wo, f.gu, f.dn, cnt, chain_err_, s);
+      break;
+    case P::Ffn::ffn_chain:
+      // gate/up and down in ONE launch, the down blocks waiting per K part on the gate/up tiles
+      // they read: the down weight stream starts under the gate/up's last tiles instead of after a
+      // kernel boundary (P2P TP: the partials accumulate into tmp_b_, so nothing seeds them first)
+      if (!p.ffn_norm_folded) bprep_rows(x_, d, false, L.ffn_norm, d, B, nullptr, 0, s);
+      bmm_ffn_chain(f.gu, f.dn, cnt, chain_err_, s);
       tp_end();
-      return;
-    }
-    bmm(gu, s);
-    tp_begin();
-    bmm(dn, s);
-    tp_end();
-    return;
+      break;
+    case P::Ffn::moe_stacked:
+      // MoE: dense per-row expert weights (f32 router on the normed rows), then every expert's
+      // SwiGLU rows in ONE gate/up launch (epilogue scaled by the row's weight for that expert,
+      // 0 when unrouted) and ONE down launch over the K-concatenated experts (parts of unrouted
+      // experts skipped): two weight streams per layer instead of a GEMM pair per expert
+      moe_router_rows(x_, d, B, L.ffn_norm, hp_.rms_eps, reinterpret_cast<const float*>(L.router.base), d,
+                      hp_.n_expert, hp_.n_expert_used, ew_b_, hp_.n_expert, s);
+      [[fallthrough]];
+    case P::Ffn::swiglu:
+      if (!p.ffn_norm_folded) bprep_rows(x_, d, false, L.ffn_norm, d, B, nullptr, 0, s);
+      bmm(f.gu, s);
+      tp_begin();
+      bmm(f.dn, s);
+      tp_end();
+      break;
+    case P::Ffn::prep:
+      bprep_rows(x_, d, false, L.ffn_norm, d, B, gu_b_, B * 2 * F_l_, s);
+      bmm_rows(L.t_gu, xh_b_, d, gu_b_, 2 * F_l_, B, s);
+      bprep_rows(gu_b_, 2 * F_l_, true, nullptr, F_l_, B, nullptr, 0, s, /*swiglu_group=*/8);  // t_gu: SwiGLU copy
+      tp_begin();
+      bmm(f.dn, s);
+      tp_end();
+      break;
+    case P::Ffn::grouped:
+      enqueue_rows_ffn(l, B, s);
+      if (p.zero_qkv == P::ZeroQkv::memset) HIPCHK(hipMemsetAsync(qkv_b_, 0, sizeof(float) * qkv_b_zero_n(), s));
+      break;
   }
-  if (bg_ffn_) {
-    bprep_rows(x_, d, false, L.ffn_norm, d, B, gu_b_, B * 2 * F_l_, s);
-    bmm_rows(L.t_gu, xh_b_, d, gu_b_, 2 * F_l_, 2 * F_l_, B, s);
-    bprep_rows(gu_b_, 2 * F_l_, true, nullptr, F_l_, B, nullptr, 0, s, /*swiglu_group=*/8);  // t_gu: SwiGLU copy
-    tp_begin();
-    down_rows(L.t_down, xh_b_, F_l_, acc, B, s, sk);
-    tp_end();
-    return;
-  }
-  // MoE (or unsupported FFN types): the grouped-GEMM FFN of the prompt path over the B rows
-  enqueue_rows_ffn(l, B, s);
-  zero_qkv();
 }
 
 // The device work of one batch step over B rows (slots / positions / tokens are read from

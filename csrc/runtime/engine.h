@@ -76,6 +76,58 @@ struct Layer {
   QMat t_wq, t_wk, t_wv, t_wo, t_gu, t_down;
 };
 
+// Every path decision of one layer of a batched decode step over B rows (Engine::plan_batch_layer
+// makes them, Engine::enqueue_batch_layer only follows them; docs/DESIGN.md has the table).
+struct BatchLayerPlan {
+  enum class Qkv {
+    split_k,    // one split-K launch, the attention normalises, rotates and appends
+    epilogue,   // one K part, RoPE and KV append in the epilogue
+    unfused,    // bprep + bmm, then the finishing kernel
+  };
+  enum class Finish { none, rope_kv_prefill, qk_norm_rope_kv };
+  enum class Ffn {
+    wo_ffn_chain,  // Wo, gate/up and down in one launch
+    ffn_chain,     // Wo; gate/up and down in one launch
+    swiglu,        // Wo; gate/up on the SwiGLU epilogue; down
+    moe_stacked,   // Wo; router; the experts' stacked gate/up; their K-concatenated down
+    prep,          // Wo; bprep, gate/up, SwiGLU prep, down
+    grouped,       // Wo; the prompt path's grouped-GEMM FFN (enqueue_rows_ffn)
+  };
+  enum class Tp { none, p2p_accumulate, rccl };
+  enum class ZeroQkv { nobody, down, memset };  // who re-zeroes the split-K Q|K|V sums for the next layer
+  Qkv qkv = Qkv::unfused;
+  bool qkv_norm_folded = false;  // attention RMSNorm in the projection's x staging (no bprep)
+  bool qkv_two_launch = false;   // two runs of different tile16 formats in one launch (bmm_qkv2)
+  Finish finish = Finish::none;
+  bool sk_defers_rope = false;   // split_k: the sums stay unrotated, the attention applies the RoPE
+  Ffn ffn = Ffn::grouped;
+  bool ffn_norm_folded = false;  // FFN RMSNorm in the gate/up's x staging (no bprep)
+  bool wo_rows = false;          // Wo in row groups of kBmmMaxRows (else one bmm, or inside the chain)
+  Tp tp = Tp::none;
+  ZeroQkv zero_qkv = ZeroQkv::nobody;
+};
+// the names Engine.batch_plan reports, in the enumerators' order
+inline const char* to_string(BatchLayerPlan::Qkv v) {
+  static constexpr const char* n[] = {"split_k", "epilogue", "unfused"};
+  return n[(int)v];
+}
+inline const char* to_string(BatchLayerPlan::Finish v) {
+  static constexpr const char* n[] = {"none", "rope_kv_prefill", "qk_norm_rope_kv"};
+  return n[(int)v];
+}
+inline const char* to_string(BatchLayerPlan::Ffn v) {
+  static constexpr const char* n[] = {"wo_ffn_chain", "ffn_chain", "swiglu", "moe_stacked", "prep", "grouped"};
+  return n[(int)v];
+}
+inline const char* to_string(BatchLayerPlan::Tp v) {
+  static constexpr const char* n[] = {"none", "p2p_accumulate", "rccl"};
+  return n[(int)v];
+}
+inline const char* to_string(BatchLayerPlan::ZeroQkv v) {
+  static constexpr const char* n[] = {"nobody", "down", "memset"};
+  return n[(int)v];
+}
+
 class Engine : public SlotBackend {
  public:
   Engine(const std::string& path, const EngineOptions& opts);
@@ -187,6 +239,8 @@ class Engine : public SlotBackend {
   void batch_launch(const std::vector<int>& slots) override;
   std::vector<int> batch_collect() override;
   std::vector<float> batch_logits(int B);  // test hook: logits [B][n_vocab] of the last batch_step
+  // inspection hook (tests): the plan of every layer for a batched step over B rows; queues no work
+  std::vector<BatchLayerPlan> batch_plan(int B);
 
  private:
   // Every public entry point that runs device work takes this guard: it serialises the
@@ -270,12 +324,24 @@ class Engine : public SlotBackend {
   void enqueue_rows_ffn(int l, int T, hipStream_t s, bool t16 = false);
   void enqueue_head(const float* xrow, int advance_pos, hipStream_t s, int slot = 0);
   // batch_step on the MFMA batched projections (bmm.hip): one layer over the B decode rows
+  // (plan_batch_layer: every decision, no device work, safe inside graph capture; the two *_args
+  // helpers hand the engine's buffers to the builders of kernels.h as the plan says)
+  BatchLayerPlan plan_batch_layer(int l, int B) const;
   void enqueue_batch_layer(int l, int B, hipStream_t s);
   void enqueue_batch_step(int B, hipStream_t s);
-  void bmm_rows(const QMat& w, const __half* xh, int ldh, float* out, int ldo, int n_out, int B, hipStream_t s,
+  struct BatchFfnArgs {
+    BmmArgs wo, gu, dn;
+  };
+  std::vector<BmmArgs> batch_qkv_runs(int l, int B, const BatchLayerPlan& p) const;
+  BatchFfnArgs batch_ffn_args(int l, int B, const BatchLayerPlan& p) const;
+  float* batch_acc(const BatchLayerPlan& p) const {  // where Wo and the down add: the residual, or the TP partials
+    return p.tp == BatchLayerPlan::Tp::p2p_accumulate ? tmp_b_ : p.tp == BatchLayerPlan::Tp::rccl ? tmp_ : x_;
+  }
+  __half* batch_kv(__half* cache, int l) const {  // slot 0's layer l; the kernels add slot * slot_stride_
+    return cache + (size_t)nkv_l_ * opt_.n_ctx * hp_.head_dim * (l - opt_.layer_begin);
+  }
+  void bmm_rows(const QMat& w, const __half* xh, int ldh, float* out, int ldo, int B, hipStream_t s,
                 long long* dbg = nullptr);
-  void down_rows(const QMat& w, const __half* xh, int ldh, float* out, int B, hipStream_t s, bool zero_qkv,
-                 long long* dbg = nullptr);
   void bprep_rows(const float* x, int ldx, bool swiglu, const float* norm_w, int K, int B, float* zero, int zero_n,
                   hipStream_t s, int swiglu_group = 32);
   void setup_batch_mfma();

@@ -31,7 +31,7 @@ EXT = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 HIP_SOURCES = ["kernels/gemv.hip", "kernels/gemv_legacy.hip", "kernels/attention.hip", "kernels/sampler.hip", "kernels/gemm.hip",
                "kernels/misc.hip", "kernels/bmm.hip",
                "kernels/moe.hip", "kernels/p2p_allreduce.hip"]
-HOST_HIP_SOURCES = ["runtime/engine.cpp", "runtime/p2p.cpp", "runtime/scheduler.cpp",
+HOST_HIP_SOURCES = ["runtime/engine.cpp", "runtime/p2p.cpp", "runtime/scheduler.cpp", "kernels/bmm_args.cpp",
                     "bindings_hip.cpp"]     # host code against the HIP runtime
 HOST_SOURCES = ["runtime/gguf.cpp", "runtime/repack.cpp", "runtime/tp_channel.cpp"]          # plain C++ (+OpenMP)
 CPU_SOURCES = ["cpu/cpu_backend.cpp", "runtime/gguf.cpp", "runtime/repack.cpp", "runtime/scheduler.cpp",

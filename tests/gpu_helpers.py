@@ -52,6 +52,23 @@ def rmsnorm(x, w, eps=1e-5):
     return (x / np.sqrt(np.mean(x * x) + eps) * w).astype(np.float32)
 
 
+def dense_ffn_path(path, layer, B, chain=1):
+    """The Wo + FFN path (Engine.batch_plan's "ffn") that the bindings' predicates give dense layer
+    `layer` of the GGUF at `path` on the SwiGLU epilogue at B rows; chain: the LFK_FFN_CHAIN level
+    (the engine's default is 1). One GPU, no tensor parallelism."""
+    from llama_fastapi_k8s_gpu_amd.gguf.reader import GGUFReader
+    t = GGUFReader(path).tensors
+    wo, gate, down = (t[f"blk.{layer}.{n}.weight"] for n in ("attn_output", "ffn_gate", "ffn_down"))
+    (kwo, d), F = wo.shape, down.shape[0]
+    to, tg, td = int(wo.ggml_type), int(gate.ggml_type), int(down.ggml_type)
+    norm = hip().bmm_norm_fits(d, B)
+    if chain >= 2 and norm and hip().bmm_wo_ffn_chain_supported(to, kwo, tg, F, d, td, B):
+        return "wo_ffn_chain"
+    if chain >= 1 and hip().bmm_ffn_chain_supported(tg, F, d, td, B, norm):
+        return "ffn_chain"
+    return "swiglu"
+
+
 def rel_err(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)

@@ -83,6 +83,11 @@ def test_batch_step_d4096_fused_paths(tmp_path):
     from llama_fastapi_k8s_gpu_amd.runtime import load_hip
     path = write_synthetic_gguf("pd-llama-g4", str(tmp_path / "g4.gguf"))
     eng = load_hip().Engine(path, n_ctx=128, n_batch=64, device=0, use_graph=True, n_slots=4)
+    # the paths the docstring names, as the engine plans them for both row counts below
+    for B in (3, 2):
+        for l, p in enumerate(eng.batch_plan(B)):
+            assert p["qkv_norm_folded"] and p["ffn_norm_folded"], (B, l, p)
+            assert p["ffn"] in ("wo_ffn_chain", "ffn_chain", "swiglu"), (B, l, p)  # the SwiGLU-epilogue family
     ref = ReferenceLlama(GGUFReader(path), n_ctx=128)
     emu = ReferenceLlama(GGUFReader(path), n_ctx=128)
     rng = np.random.default_rng(5)
@@ -106,6 +111,27 @@ def test_batch_step_d4096_fused_paths(tmp_path):
             assert toks[b] == int(np.argmax(logits[b]))
             seqs[s].append(toks[b])
     assert eng.healthy, eng.last_error
+
+
+def test_batch_plan_d4096_bumped_layers_take_one_launch(tmp_path, monkeypatch):
+    """The same model without the split-K Q|K|V (LFK_QKV_SK=0): every layer plans the one-part epilogue
+    with the folded norm, and the bumped layers (Q|K Q4_K + V Q6_K: two runs; layers 2 and 3 of the
+    four under the Q4_K_M rule) the two-run launch - the others hold one run. The plan only: the
+    launch itself is tests/test_qkv_paths_gpu.py's."""
+    from llama_fastapi_k8s_gpu_amd.gguf.constants import GGMLType
+    from llama_fastapi_k8s_gpu_amd.gguf.reader import GGUFReader
+    from llama_fastapi_k8s_gpu_amd.gguf.synthetic import write_synthetic_gguf
+    from llama_fastapi_k8s_gpu_amd.runtime import load_hip
+    path = write_synthetic_gguf("pd-llama-g4", str(tmp_path / "g4.gguf"))
+    t = GGUFReader(path).tensors
+    bumped = [l for l in range(4) if t[f"blk.{l}.attn_v.weight"].ggml_type == GGMLType.Q6_K]
+    assert 0 < len(bumped) < 4, bumped   # both kinds of layer are in the model
+    monkeypatch.setenv("LFK_QKV_SK", "0")
+    eng = load_hip().Engine(path, n_ctx=128, n_batch=64, device=0, use_graph=True, n_slots=4)
+    for l, p in enumerate(eng.batch_plan(3)):
+        assert (p["qkv"], p["finish"], p["qkv_norm_folded"]) == ("epilogue", "none", True), (l, p)
+        assert p["qkv_two_launch"] == (l in bumped), (l, p)
+        assert p["zero_qkv"] == "nobody", (l, p)
 
 
 @pytest.mark.parametrize("joint_rows", ["default", "0"])
@@ -288,6 +314,12 @@ def test_batch_step_six_rows_d8192(tmp_path):
     from llama_fastapi_k8s_gpu_amd.runtime import load_hip
     path = write_synthetic_gguf("tiny-llama3-d8k", str(tmp_path / "d8k.gguf"))
     eng = load_hip().Engine(path, n_ctx=128, n_batch=64, device=0, use_graph=True, n_slots=7)
+    # the paths the docstring names; four rows - the most that stage whole rows of this width - leave prep
+    assert load_hip().bmm_qkv_fits(8192, 4) and not load_hip().bmm_qkv_fits(8192, 5)
+    for p in eng.batch_plan(6):
+        assert (p["qkv"], p["ffn"], p["zero_qkv"]) == ("split_k", "prep", "down"), p
+    for p in eng.batch_plan(4):
+        assert p["qkv"] == "split_k" and p["ffn"] != "prep", p
     ref = ReferenceLlama(GGUFReader(path), n_ctx=128)
     rng = np.random.default_rng(9)
     greedy = {"temperature": 0.0, "top_k": 1, "repeat_penalty": 1.0}

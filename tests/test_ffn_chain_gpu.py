@@ -17,7 +17,7 @@ tests/test_ffn_chain_ref.py)."""
 import numpy as np
 import pytest
 
-from gpu_helpers import dev_bytes, hip, rel_err, stream, to_planar
+from gpu_helpers import dense_ffn_path, dev_bytes, hip, rel_err, stream, to_planar
 import ffn_chain_ref as cr
 import moe_ref as mr
 
@@ -255,6 +255,11 @@ def test_batch_step_16_part_down_takes_the_separate_launches(tmp_path):
     spec = ModelSpec("llama-d2048-ff8192-1l", 2048, 1, 16, 4, 8192, 0, 500000.0, "bpe", "q4_k_m", n_ctx_train=1024)
     path = write_synthetic_gguf(spec, str(tmp_path / "ff8192.gguf"))
     eng = load_hip().Engine(path, n_ctx=128, n_batch=64, device=0, use_graph=True, n_slots=4)
+    # the engine's plan is the separate launches, and that is the predicate's answer over this layer's
+    # own types and shapes on this device (no CU count spelled here)
+    for B in (3, 2):
+        (p,) = eng.batch_plan(B)
+        assert p["ffn"] == "swiglu" and p["ffn"] == dense_ffn_path(path, 0, B), (B, p)
     ref = ReferenceLlama(GGUFReader(path), n_ctx=128)
     emu = ReferenceLlama(GGUFReader(path), n_ctx=128)
     rng = np.random.default_rng(6)

@@ -329,13 +329,22 @@ def _batch_case(path):
         want = ReferenceLlama(GGUFReader(path), n_ctx=256).forward(seqs[s][:plen[s] + 3], 0).numpy()
         vs_ref.append(rel_err(rows[s][2], want))
     return {"vs_single": vs_single, "vs_ref": vs_ref, "picks_ok": bool(picks_ok), "healthy": bool(eng.healthy),
-            "defers_rope": bool(hip().bmm_qkv_sk_defers_rope())}
+            "defers_rope": bool(hip().bmm_qkv_sk_defers_rope()), "plan": eng.batch_plan(len(slots))}
 
 
-def _check_batch(r, what):
+def _check_batch(r, what, path, split_k):
+    """The errors of _batch_case, and the Q|K|V path its engine planned for every (biased) layer:
+    split-K with the RoPE and the biases left to the attention, or - split_k False - the one-part
+    epilogue where B = 3 rows of this width fit one LDS-staged part, else bprep + bmm + rope_kv_prefill."""
+    from llama_fastapi_k8s_gpu_amd.gguf.reader import GGUFReader
     assert r["healthy"] and r["picks_ok"], (what, r)
     assert max(r["vs_ref"]) < 5e-2, (what, r)
     assert max(r["vs_single"]) < TIGHT, (what, r)
+    fits = hip().bmm_qkv_fits(int(GGUFReader(path).metadata["qwen2.embedding_length"]), 3)
+    want = ("split_k", "none") if split_k else ("epilogue", "none") if fits else ("unfused", "rope_kv_prefill")
+    for l, p in enumerate(r["plan"]):
+        assert (p["qkv"], p["finish"]) == want, (what, l, p)
+        assert p["sk_defers_rope"] == split_k, (what, l, p)
 
 
 def _split_k_capable(path, B=3):
@@ -360,10 +369,10 @@ def test_batch_step_rows_match_single_row_decode(models, spec, split_k, monkeypa
     # the default form: split-K Q|K|V (where the types allow), RoPE and biases in the batched attention
     r = _batch_case(models[spec])
     assert r["defers_rope"]
-    _check_batch(r, "default")
+    _check_batch(r, "default", models[spec], split_k)
     # the one-part Q|K|V epilogue (or, where the rows do not fit it, the unfused RoPE / KV-append kernel)
     monkeypatch.setenv("LFK_QKV_SK", "0")
-    _check_batch(_batch_case(models[spec]), "LFK_QKV_SK=0")
+    _check_batch(_batch_case(models[spec]), "LFK_QKV_SK=0", models[spec], False)
 
 
 @pytest.mark.parametrize("spec", ["tiny-qwen2-g7", "tiny-qwen2-g6-hd64", "tiny-qwen2-g5"])
@@ -376,7 +385,7 @@ def test_batch_step_without_deferred_rope_in_a_child(models, spec):
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     r = json.loads(p.stdout.strip().splitlines()[-1])
     assert not r["defers_rope"]
-    _check_batch(r, "LFK_BMM_IL=0")
+    _check_batch(r, "LFK_BMM_IL=0", models[spec], False)
 
 
 @pytest.mark.parametrize("joint_rows", ["default", "0"])

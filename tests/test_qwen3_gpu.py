@@ -363,14 +363,21 @@ def _batch_case(path):
         want = ReferenceLlama(GGUFReader(path), n_ctx=256).forward(seqs[s][:plen[s] + 3], 0).numpy()
         vs_ref.append(rel_err(rows[s][2], want))
     return {"vs_single": vs_single, "vs_ref": vs_ref, "picks_ok": bool(picks_ok), "healthy": bool(eng.healthy),
-            "defers_rope": bool(hip().bmm_qkv_sk_defers_rope())}
+            "defers_rope": bool(hip().bmm_qkv_sk_defers_rope()), "plan": eng.batch_plan(len(slots))}
 
 
-def _check_batch(r, what):
+def _check_batch(r, what, split_k):
+    """The errors of _batch_case, and the Q|K|V path its engine planned for every (QK-norm) layer:
+    split-K with the head norm and the RoPE left to the attention, or - split_k False - bprep + bmm +
+    the head-norm kernel: such a layer declines the one-part epilogue and its folded norm."""
     print("batch", what, "vs_ref / 5e-2", max(r["vs_ref"]) / 5e-2, "vs_single / TIGHT", max(r["vs_single"]) / TIGHT)
     assert r["healthy"] and r["picks_ok"], (what, r)
     assert max(r["vs_ref"]) < 5e-2, (what, r)
     assert max(r["vs_single"]) < TIGHT, (what, r)
+    want = ("split_k", "none", True) if split_k else ("unfused", "qk_norm_rope_kv", False)
+    for l, p in enumerate(r["plan"]):
+        assert (p["qkv"], p["finish"], p["qkv_norm_folded"]) == want, (what, l, p)
+        assert p["sk_defers_rope"] == split_k, (what, l, p)
 
 
 def _split_k_capable(path, B=3):
@@ -394,9 +401,9 @@ def test_batch_step_rows_match_single_row_decode(models, spec, split_k, monkeypa
     assert _split_k_capable(models[spec]) == split_k, spec
     r = _batch_case(models[spec])       # the default: split-K Q|K|V (where the types allow), norm + RoPE in the attention
     assert r["defers_rope"]
-    _check_batch(r, "default")
+    _check_batch(r, "default", split_k)
     monkeypatch.setenv("LFK_QKV_SK", "0")   # no split-K: a QK-norm layer declines the one-part epilogue too
-    _check_batch(_batch_case(models[spec]), "LFK_QKV_SK=0")
+    _check_batch(_batch_case(models[spec]), "LFK_QKV_SK=0", False)
 
 
 @pytest.mark.parametrize("spec", ["tiny-qwen3-g2-hd128", "tiny-qwen3-g4-hd64", "tiny-qwen3-g5"])
@@ -409,7 +416,7 @@ def test_batch_step_without_deferred_rope_in_a_child(models, spec):
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     r = json.loads(p.stdout.strip().splitlines()[-1])
     assert not r["defers_rope"]
-    _check_batch(r, "LFK_BMM_IL=0")
+    _check_batch(r, "LFK_BMM_IL=0", False)
 
 
 @pytest.mark.parametrize("spec", ["tiny-qwen3-g2-hd128", "tiny-qwen3-g4-hd64"])
