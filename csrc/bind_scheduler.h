@@ -26,7 +26,19 @@ inline SamplingOpts sampling_opts_from(pybind11::dict sp) {
   if (sp.contains("logit_bias"))
     for (auto kv : sp["logit_bias"].cast<py::dict>())
       o.logit_bias.emplace_back(kv.first.cast<int>(), kv.second.cast<float>());
+  o.n_probs = sp.contains("n_probs") ? sp["n_probs"].cast<int>() : 0;
   return o;
+}
+
+// (log p(token), [(id, log p)] top-n): the shape of engine/sampling.py:token_logprobs
+inline pybind11::object logprob_entry_py(const LogprobEntry& e) {
+  return pybind11::make_tuple((double)e.logprob, e.top);
+}
+// one per token; None for a token whose request did not ask
+inline pybind11::list logprob_entries_py(const std::vector<LogprobEntry>& v) {
+  pybind11::list out;
+  for (const LogprobEntry& e : v) out.append(e.top.empty() ? pybind11::object(pybind11::none()) : logprob_entry_py(e));
+  return out;
 }
 
 // Backend: the pybind-registered class of the slot engine the scheduler is built over.
@@ -53,6 +65,7 @@ void bind_scheduler(pybind11::module_& m) {
              }
              py::dict d;
              d["tokens"] = p.tokens;
+             d["logprobs"] = logprob_entries_py(p.logprobs);  // of exactly these tokens ([] if not asked)
              d["done"] = p.done;
              d["finish"] = p.finish;
              d["error"] = p.error;

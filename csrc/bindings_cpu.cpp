@@ -41,7 +41,7 @@ class FakeSlotEngine : public SlotBackend {
  public:
   FakeSlotEngine(int n_slots, int max_batch, int n_ctx, int vocab, int step_us)
       : n_slots_(n_slots), max_batch_(max_batch), n_ctx_(n_ctx), vocab_(vocab), step_us_(step_us),
-        kv_(n_slots), cur_(n_slots, 0) {}
+        kv_(n_slots), cur_(n_slots, 0), n_probs_(n_slots, 0) {}
   int n_slots() const override { return n_slots_; }
   int max_batch() const override { return max_batch_; }
   int n_ctx() const override { return n_ctx_; }
@@ -50,9 +50,24 @@ class FakeSlotEngine : public SlotBackend {
     for (int t : seq) h = (h ^ (unsigned)t) * 1099511628211ull;
     return (int)(h % (unsigned long long)vocab);
   }
-  int slot_begin(int slot, const std::vector<int>& prompt, int n_keep, const SamplingOpts&) override {
+  // Log-probability entries are a function of (slot, position, token) alone: the token at position
+  // p of slot s has log p = -(1000 s + p) / 1024 and top-j (token + j mod vocab, log p - j), so a
+  // test can tell from an entry which step of which row it belongs to.
+  LogprobEntry entry(int slot) const {
+    LogprobEntry e;
+    if (n_probs_[slot] <= 0) return e;
+    e.logprob = -(float)(1000 * slot + (int)kv_[slot].size()) / 1024.f;
+    for (int j = 0; j < n_probs_[slot]; ++j) e.top.emplace_back((cur_[slot] + j) % vocab_, e.logprob - (float)j);
+    return e;
+  }
+  std::vector<LogprobEntry> step_logprobs() override {
+    std::lock_guard<std::mutex> g(mu_);
+    return last_lp_;
+  }
+  int slot_begin(int slot, const std::vector<int>& prompt, int n_keep, const SamplingOpts& sp) override {
     std::lock_guard<std::mutex> g(mu_);
     if (slot < 0 || slot >= n_slots_) throw std::runtime_error("fake: slot out of range");
+    n_probs_[slot] = sp.n_probs;
     std::vector<int>& kv = kv_[slot];
     if (n_keep > (int)kv.size()) throw std::runtime_error("fake: reused prefix is not resident");
     for (int i = 0; i < n_keep; ++i)
@@ -60,14 +75,32 @@ class FakeSlotEngine : public SlotBackend {
     kv.assign(prompt.begin(), prompt.end());
     prefilled_ += (long long)prompt.size() - n_keep;
     cur_[slot] = next_token(kv, vocab_);
+    last_lp_.assign(sp.n_probs > 0 ? 1 : 0, entry(slot));
     return cur_[slot];
+  }
+  std::vector<int> slots_begin(const std::vector<int>& slots, const std::vector<std::vector<int>>& prompts,
+                               const std::vector<int>& n_keep, const std::vector<SamplingOpts>& sps) override {
+    std::vector<int> out;
+    std::vector<LogprobEntry> lps;
+    bool ask = false;
+    for (size_t i = 0; i < slots.size(); ++i) {
+      out.push_back(slot_begin(slots[i], prompts[i], n_keep[i], sps[i]));
+      lps.push_back(last_lp_.empty() ? LogprobEntry{} : last_lp_[0]);
+      ask = ask || sps[i].n_probs > 0;
+    }
+    std::lock_guard<std::mutex> g(mu_);
+    if (!ask) lps.clear();
+    last_lp_ = std::move(lps);
+    return out;
   }
   // chunked admission: the prompt enters the slot's KV part by part (a reused prefix first)
   int prefill_part_tokens() const override { return chunk_; }
   int slot_begin_part(int slot, const std::vector<int>& prompt, int n_keep, int n_done, int n,
-                      const SamplingOpts&) override {
+                      const SamplingOpts& sp) override {
     std::lock_guard<std::mutex> g(mu_);
     if (slot < 0 || slot >= n_slots_) throw std::runtime_error("fake: slot out of range");
+    n_probs_[slot] = sp.n_probs;
+    last_lp_.clear();
     std::vector<int>& kv = kv_[slot];
     if (n_done == n_keep) {  // first part: the reused prefix must be resident
       if (n_keep > (int)kv.size()) throw std::runtime_error("fake: reused prefix is not resident");
@@ -82,6 +115,7 @@ class FakeSlotEngine : public SlotBackend {
     ++parts_;
     if (end < (int)prompt.size()) return -1;
     cur_[slot] = next_token(kv, vocab_);
+    last_lp_.assign(sp.n_probs > 0 ? 1 : 0, entry(slot));
     return cur_[slot];
   }
   void set_prefill_chunk(int n) { chunk_ = n; }
@@ -91,12 +125,16 @@ class FakeSlotEngine : public SlotBackend {
     std::lock_guard<std::mutex> g(mu_);
     if ((int)slots.size() > max_batch_) throw std::runtime_error("fake: too many rows");
     std::vector<int> out;
+    bool ask = false;
+    for (int s : slots) ask = ask || n_probs_[s] > 0;
+    last_lp_.clear();
     for (int s : slots) {
       std::vector<int>& kv = kv_[s];
       if ((int)kv.size() >= n_ctx_) throw std::runtime_error("fake: KV write past n_ctx");
       kv.push_back(cur_[s]);
       cur_[s] = next_token(kv, vocab_);
       out.push_back(cur_[s]);
+      if (ask) last_lp_.push_back(entry(s));
     }
     ++steps_;
     max_rows_ = std::max(max_rows_, (int)slots.size());
@@ -111,12 +149,15 @@ class FakeSlotEngine : public SlotBackend {
     std::lock_guard<std::mutex> g(mu_);
     if (queued_.size() >= 2) throw std::runtime_error("fake: two steps already in flight");
     queued_.push_back(std::move(out));
+    queued_lp_.push_back(last_lp_);
   }
   std::vector<int> batch_collect() override {
     std::lock_guard<std::mutex> g(mu_);
     if (queued_.empty()) throw std::runtime_error("fake: no step in flight");
     std::vector<int> out = std::move(queued_.front());
     queued_.pop_front();
+    last_lp_ = std::move(queued_lp_.front());  // the entries travel with their step's tokens
+    queued_lp_.pop_front();
     return out;
   }
   void set_pipeline(bool on) { pipeline_ = on; }
@@ -135,6 +176,9 @@ class FakeSlotEngine : public SlotBackend {
   int max_rows_ = 0;
   bool pipeline_ = false;
   std::deque<std::vector<int>> queued_;
+  std::vector<int> n_probs_;
+  std::vector<LogprobEntry> last_lp_;
+  std::deque<std::vector<LogprobEntry>> queued_lp_;
 };
 
 PYBIND11_MODULE(_cpu, m) {

@@ -70,19 +70,23 @@ PYBIND11_MODULE(_hip, m) {
       .def(
           "generate",
           [](Engine& e, const std::vector<int>& prompt, int n_keep, int max_new, py::dict sp,
-             const std::vector<int>& stop_ids, py::object poll, py::object on_token) {
+             const std::vector<int>& stop_ids, py::object poll, py::object on_token, py::object on_logprob) {
             const SamplingOpts o = sampling_opts(sp);
             std::function<bool()> pf;
             std::function<void(int)> tf;
+            std::function<void(const LogprobEntry&)> lf;
             if (!poll.is_none()) pf = [poll]() { py::gil_scoped_acquire g; return poll().cast<bool>(); };
             if (!on_token.is_none()) tf = [on_token](int t) { py::gil_scoped_acquire g; on_token(t); };
+            if (!on_logprob.is_none())
+              lf = [on_logprob](const LogprobEntry& l) { py::gil_scoped_acquire g; on_logprob(logprob_entry_py(l)); };
             GenOut r;
             {
               py::gil_scoped_release nogil;
-              r = e.generate(prompt, n_keep, max_new, o, stop_ids, pf, tf);
+              r = e.generate(prompt, n_keep, max_new, o, stop_ids, pf, tf, lf);
             }
             py::dict d;
             d["tokens"] = r.tokens;
+            d["logprobs"] = logprob_entries_py(r.logprobs);  // one per token with n_probs > 0, else []
             d["finish"] = r.finish;
             d["n_evaluated"] = r.n_evaluated;
             d["n_prefilled"] = r.n_prefilled;
@@ -91,7 +95,7 @@ PYBIND11_MODULE(_hip, m) {
             return d;
           },
           py::arg("prompt"), py::arg("n_keep"), py::arg("max_new"), py::arg("sampling"), py::arg("stop_ids"),
-          py::arg("poll") = py::none(), py::arg("on_token") = py::none())
+          py::arg("poll") = py::none(), py::arg("on_token") = py::none(), py::arg("on_logprob") = py::none())
       .def("eval_logits",
            [](Engine& e, const std::vector<int>& tokens, int pos0) {
              std::vector<float> v;
@@ -197,6 +201,18 @@ PYBIND11_MODULE(_hip, m) {
              py::gil_scoped_release nogil;
              return e.batch_collect();
            })
+      // entries of the tokens the last slot_begin / slots_begin / batch_step / batch_collect returned
+      // (None for a slot that did not ask; [] when none did)
+      .def("step_logprobs",
+           [](Engine& e) {
+             std::vector<LogprobEntry> v;
+             {
+               py::gil_scoped_release nogil;
+               v = e.step_logprobs();
+             }
+             return logprob_entries_py(v);
+           })
+      .def_property_readonly("logprob_launches", &Engine::logprob_launches)
       .def_property_readonly("can_pipeline", &Engine::can_pipeline)
       .def("batch_logits",
            [](Engine& e, int B) {
@@ -825,6 +841,21 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("out_tokens"), py::arg("out_cap"), py::arg("advance"), py::arg("stream"), py::arg("dbg_clk") = 0,
      py::arg("vocab_off") = 0, py::arg("V_glob") = 0, py::arg("V_span") = 0, py::arg("cand_all") = 0,
      py::arg("world") = 1, py::arg("stage") = 3);
+  m.attr("MAX_LOGPROBS") = kMaxLogprobs;
+  m.attr("LOGPROB_REC_WORDS") = kLogprobRecWords;
+  m.def("logprob_part_words", &logprob_part_words);
+  // token log-probabilities of raw logits (kernels.h LogprobArgs); batch > 0: the batched form
+  m.def("logprobs", [](uintptr_t logits, int V, uintptr_t n_probs, uintptr_t state, uintptr_t part, uintptr_t rec,
+                       uintptr_t stream, int batch, uintptr_t slots, size_t logits_ld, int stage) {
+    LogprobArgs a;
+    a.logits = P<const float>(logits); a.V = V; a.n_probs = P<const int>(n_probs); a.state = P<const int>(state);
+    a.part = P<float>(part); a.rec = P<unsigned>(rec);
+    a.batch = batch; a.slots = P<const int>(slots); a.logits_ld = logits_ld;
+    if (stage & 1) logprobs_stage1(a, S(stream));
+    if (stage & 2) logprobs_stage2(a, S(stream));
+    hip_ok("logprobs");
+  }, py::arg("logits"), py::arg("V"), py::arg("n_probs"), py::arg("state"), py::arg("part"), py::arg("rec"),
+     py::arg("stream"), py::arg("batch") = 0, py::arg("slots") = 0, py::arg("logits_ld") = 0, py::arg("stage") = 3);
   m.def("sampler_params_bytes", [](int top_k, float top_p, float min_p, float temp, float rp, float fp, float pp,
                                    int last_n, unsigned long long seed, int greedy, float tfs_z, float typical_p,
                                    py::dict logit_bias) {

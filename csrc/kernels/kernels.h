@@ -650,6 +650,32 @@ void sample_stage1(const SamplerArgs& a, hipStream_t s);
 void sample_stage2(const SamplerArgs& a, hipStream_t s);
 void sample(const SamplerArgs& a, hipStream_t s);  // both stages (world 1)
 
+// Token log-probabilities of the RAW logits a step left behind (before bias, penalties, temperature
+// or any filter), world 1 only: natural-log probability of the token the sampler's stage 2 just wrote
+// to state[S_TOKEN], and the n = min(n_probs, kMaxLogprobs, V) most probable tokens with theirs,
+// ordered by value descending, ties by ascending id. One record of kLogprobRecWords 4-byte words per
+// row: [lp(token) f32][n i32][ids i32 x kMaxLogprobs][lps f32 x kMaxLogprobs] (entries past n: -1 / 0).
+// Stage 1 uses the sampler's stage-1 grid and only reads the logits; stage 2 is one block per row.
+static constexpr int kMaxLogprobs = 20;  // OpenAI's top_logprobs limit
+static constexpr int kLogprobRecWords = 2 + 2 * kMaxLogprobs;
+struct LogprobArgs {
+  const float* logits = nullptr;   // [V] raw logits of the row
+  int V = 0;
+  const int* n_probs = nullptr;    // entries the row asks for; 0: the row does no work, its record stays
+  const int* state = nullptr;      // [S_NSTATE] of the row (S_TOKEN: the sampled token)
+  float* part = nullptr;           // stage-1 output [rows][logprob_part_words(V)]
+  unsigned* rec = nullptr;         // [rows][kLogprobRecWords]
+  // batched (batch > 0), as SamplerArgs: row b reads logits + b*logits_ld, n_probs[slots[b]] and
+  // state + S_NSTATE*slots[b], and writes part / record b
+  int batch = 0;
+  const int* slots = nullptr;
+  size_t logits_ld = 0;
+};
+size_t logprob_part_words(int V);
+void logprobs_stage1(const LogprobArgs& a, hipStream_t s);
+void logprobs_stage2(const LogprobArgs& a, hipStream_t s);
+void logprobs(const LogprobArgs& a, hipStream_t s);  // both stages
+
 // ---------------------------------------------------------------- synthetic fill
 // Random valid quant blocks generated on device (for synthetic models without a file).
 void fill_random_planar(uint8_t* base, int type, size_t rows, size_t K, float std, unsigned long long seed,

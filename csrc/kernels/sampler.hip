@@ -512,4 +512,185 @@ void sample(const SamplerArgs& a, hipStream_t s) {
   sample_stage2(a, s);
 }
 
+// ---------------------------------------------------------------- token log-probabilities
+// log p of the sampled token and the n <= kMaxLogprobs most probable tokens, of the RAW logits
+// the step left in HBM (engine/sampling.py:token_logprobs). Same grid as the sampler: stage 1 one
+// wave per 1024-logit slice (slice maximum, sum of exp, a top-n superset), stage 2 one block per
+// row (log-sum-exp over the slices, the n best by (value descending, id ascending), the record).
+// A row whose n_probs is 0 returns at once in both stages.
+static constexpr int LP_HDR = 4;  // words ahead of a slice's candidates: [m_s][sum_s][count][-]
+__host__ __device__ __forceinline__ size_t lp_part_words(int nb) { return (size_t)nb * (LP_HDR + 2 * KMAX); }
+
+// re-bases the row's pointers as batch_row does; returns how many entries the row asks for
+__device__ __forceinline__ int logprob_row(LogprobArgs& a, int b) {
+  if (a.batch > 0) {
+    const int slot = a.slots[b];
+    a.logits += (size_t)b * a.logits_ld;
+    a.n_probs += slot;
+    a.state += (size_t)S_NSTATE * slot;
+  }
+  return min(min(*a.n_probs, kMaxLogprobs), a.V);
+}
+
+// wave-ordered compaction behind `base`: the values above T (eq == false) or equal to it
+template <int NE>
+__device__ __forceinline__ int logprob_collect(const float (&v)[NE], const int (&idx)[NE], float T, bool eq, int base,
+                                               float* ov, int* oi) {
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    const bool f = v[e] > -FLT_MAX && (eq ? v[e] == T : v[e] > T);
+    const unsigned long long m = __ballot(f);
+    if (f) {
+      const int p = base + lanes_below(m);
+      if (p < KMAX) { ov[p] = v[e]; oi[p] = idx[e]; }
+    }
+    base += __popcll(m);
+  }
+  return min(base, KMAX);
+}
+
+__global__ __launch_bounds__(64) void logprobs_stage1_kernel(LogprobArgs a) {
+  const int K = logprob_row(a, blockIdx.y);
+  if (K <= 0) return;
+  const int nb = gridDim.x;
+  float* blk = a.part + (size_t)blockIdx.y * lp_part_words(nb) + (size_t)blockIdx.x * (LP_HDR + 2 * KMAX);
+  const int lane = threadIdx.x;
+  const int lo = blockIdx.x * SLICE;
+  float v[NE1];
+  int idx[NE1];
+  float m = -FLT_MAX;
+#pragma unroll
+  for (int e = 0; e < NE1; ++e) {
+    const int i = lo + 64 * e + lane;
+    v[e] = i < a.V ? a.logits[i] : -FLT_MAX;  // logits past V count for nothing
+    idx[e] = i;
+    m = fmaxf(m, v[e]);
+  }
+  m = wave_max_fast(m);
+  float sum = 0.f;
+#pragma unroll
+  for (int e = 0; e < NE1; ++e) sum += lo + 64 * e + lane < a.V ? expf(v[e] - m) : 0.f;
+  sum = wave_sum_fast(sum);
+  // top-K superset. The threshold search cannot split ties: with more than 64 values >= T the K best
+  // are the values above T and then the lowest ids among those equal to it, so T first climbs to the
+  // next distinct value while K or more lie above it, and the two groups are collected in that order
+  float T = wave_superset_threshold<NE1>(v, K);
+  for (int it = 0; it < 64; ++it) {
+    int c = 0;
+    float nxt = FLT_MAX;
+#pragma unroll
+    for (int e = 0; e < NE1; ++e)
+      if (v[e] > T) { ++c; nxt = fminf(nxt, v[e]); }
+    if ((int)wave_sum_fast((float)c) < K) break;
+    T = -wave_max_fast(-nxt);
+  }
+  float* ov = blk + LP_HDR;
+  int* oi = reinterpret_cast<int*>(blk + LP_HDR + KMAX);
+  int cnt = logprob_collect<NE1>(v, idx, T, false, 0, ov, oi);
+  cnt = logprob_collect<NE1>(v, idx, T, true, cnt, ov, oi);
+  if (lane == 0) {
+    blk[0] = m;
+    blk[1] = sum;
+    reinterpret_cast<int*>(blk)[2] = cnt;
+  }
+}
+
+// the better of two candidates by (value descending, id ascending)
+__device__ __forceinline__ bool logprob_before(float v, int id, float w, int jd) { return v > w || (v == w && id < jd); }
+
+__global__ __launch_bounds__(256) void logprobs_stage2_kernel(LogprobArgs a, int nb) {
+  const int brow = blockIdx.x;
+  const int n = logprob_row(a, brow);
+  if (n <= 0) return;
+  const float* part = a.part + (size_t)brow * lp_part_words(nb);
+  unsigned* rec = a.rec + (size_t)brow * kLogprobRecWords;
+  __shared__ float redv[4];
+  __shared__ int redi[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  // ---- lse = M + log(sum_s sum_s * exp(m_s - M))
+  float M = -FLT_MAX;
+  for (int g = tid; g < nb; g += 256) M = fmaxf(M, part[(size_t)g * (LP_HDR + 2 * KMAX)]);
+  M = wave_max_fast(M);
+  if (lane == 0) redv[w] = M;
+  __syncthreads();
+  M = fmaxf(fmaxf(redv[0], redv[1]), fmaxf(redv[2], redv[3]));
+  __syncthreads();
+  float S = 0.f;
+  for (int g = tid; g < nb; g += 256) {
+    const float* h = part + (size_t)g * (LP_HDR + 2 * KMAX);
+    S += h[1] * expf(h[0] - M);
+  }
+  S = wave_sum_fast(S);
+  if (lane == 0) redv[w] = S;
+  __syncthreads();
+  const float lse = M + logf((redv[0] + redv[1]) + (redv[2] + redv[3]));
+  // ---- the n best of the slices' candidates: n rounds, each the best one after the previous pick
+  float pv = FLT_MAX;
+  int pid = -1;
+  for (int r = 0; r < n; ++r) {
+    float bv = -FLT_MAX;
+    int bid = 0x7fffffff;
+    for (int i = tid; i < nb * KMAX; i += 256) {
+      const int g = i >> 6, j = i & 63;
+      const float* h = part + (size_t)g * (LP_HDR + 2 * KMAX);
+      if (j >= reinterpret_cast<const int*>(h)[2]) continue;
+      const float cv = h[LP_HDR + j];
+      const int cid = reinterpret_cast<const int*>(h)[LP_HDR + KMAX + j];
+      if ((r == 0 || logprob_before(pv, pid, cv, cid)) && logprob_before(cv, cid, bv, bid)) { bv = cv; bid = cid; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bid, o);
+      if (logprob_before(ov, oi, bv, bid)) { bv = ov; bid = oi; }
+    }
+    __syncthreads();  // (the previous round's reads of redv / redi are done)
+    if (lane == 0) { redv[w] = bv; redi[w] = bid; }
+    __syncthreads();
+    bv = redv[0];
+    bid = redi[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+      if (logprob_before(redv[k], redi[k], bv, bid)) { bv = redv[k]; bid = redi[k]; }
+    pv = bv;
+    pid = bid;
+    if (tid == 0) {
+      rec[2 + r] = (unsigned)bid;
+      rec[2 + kMaxLogprobs + r] = __float_as_uint(bv - lse);
+    }
+  }
+  if (tid == 0) {
+    const int tok = min(max(a.state[S_TOKEN], 0), a.V - 1);
+    rec[0] = __float_as_uint(a.logits[tok] - lse);
+    rec[1] = (unsigned)n;
+    for (int r = n; r < kMaxLogprobs; ++r) {
+      rec[2 + r] = 0xffffffffu;
+      rec[2 + kMaxLogprobs + r] = 0u;
+    }
+  }
+}
+
+size_t logprob_part_words(int V) { return lp_part_words(sampler_blocks(V)); }
+
+static void logprob_check(const LogprobArgs& a) {
+  if (!a.logits || a.V < 1 || !a.n_probs || !a.state || !a.part || !a.rec)
+    throw std::runtime_error("logprobs: missing buffers / empty vocabulary");
+  if (a.batch > 0 && (!a.slots || a.logits_ld < (size_t)a.V)) throw std::runtime_error("logprobs: bad batched arguments");
+}
+
+void logprobs_stage1(const LogprobArgs& a, hipStream_t s) {
+  logprob_check(a);
+  hipLaunchKernelGGL(logprobs_stage1_kernel, dim3(sampler_blocks(a.V), a.batch > 0 ? a.batch : 1), dim3(64), 0, s, a);
+}
+
+void logprobs_stage2(const LogprobArgs& a, hipStream_t s) {
+  logprob_check(a);
+  hipLaunchKernelGGL(logprobs_stage2_kernel, dim3(a.batch > 0 ? a.batch : 1), dim3(256), 0, s, a, sampler_blocks(a.V));
+}
+
+void logprobs(const LogprobArgs& a, hipStream_t s) {
+  logprobs_stage1(a, s);
+  logprobs_stage2(a, s);
+}
+
 }  // namespace lfk

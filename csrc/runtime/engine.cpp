@@ -185,6 +185,7 @@ Engine::~Engine() {
     if (bev_[i]) hipEventDestroy(bev_[i]);
   }
   if (h_rmeta_) hipHostFree(h_rmeta_);
+  if (h_lp_) hipHostFree(h_lp_);
   if (wo_err_h_) hipHostFree(wo_err_h_);
   if (chain_err_h_) hipHostFree(chain_err_h_);
   for (auto& e : step_ev_) if (e) hipEventDestroy(e);
@@ -436,6 +437,19 @@ void Engine::alloc_buffers() {
     HIPCHK(hipHostMalloc((void**)&h_rmeta_, sizeof(int) * 3 * B, hipHostMallocDefault));
   }
   HIPCHK(hipMemset(out_tokens_, 0, sizeof(int) * 64));
+  // token log-probabilities (one rank, the stage that holds the head)
+  h_nprobs_.assign(NS, 0);
+  if (!tp_on_ && has_head()) {
+    lp_rows_ = std::max(bmax_, 1);
+    const size_t words = lp_off_first(NS);
+    nprobs_ = (int*)dalloc(sizeof(int) * NS);
+    lp_part_ = (float*)dalloc(sizeof(float) * lp_rows_ * logprob_part_words(hp_.n_vocab));
+    lp_rec_ = (unsigned*)dalloc(sizeof(unsigned) * words);
+    HIPCHK(hipMemset(nprobs_, 0, sizeof(int) * NS));
+    HIPCHK(hipMemset(lp_rec_, 0, sizeof(unsigned) * words));
+    HIPCHK(hipHostMalloc((void**)&h_lp_, sizeof(unsigned) * words, hipHostMallocDefault));
+    std::memset(h_lp_, 0, sizeof(unsigned) * words);
+  }
   // P2P messages: a decode step's hidden rows and the sampler's candidate blocks; in "ipc"
   // mode (no RCCL) also prefill chunks and the test hooks' logit gathers
   {
@@ -741,6 +755,60 @@ void Engine::enqueue_sample(const float* logits, int rows, size_t ld, int slot, 
     sa.world = opt_.tp_size;
   }
   sample_stage2(sa, s);
+}
+
+// The two log-probability launches over the logits a step's sampler just read, and the copy of
+// their records to the pinned mirror. Never captured: the callers queue it behind a step's graph
+// (stream order puts it before the next step overwrites the logits), so a step in which nobody
+// asks launches what it always did.
+void Engine::enqueue_logprobs(const float* logits, int rows, size_t ld, int slot, size_t off, hipStream_t s) {
+  if (!lp_rec_) throw std::runtime_error("logprobs: not available on this engine (one rank, head stage)");
+  LogprobArgs a;
+  a.logits = logits;
+  a.V = hp_.n_vocab;
+  a.part = lp_part_;
+  a.rec = lp_rec_ + off;
+  if (rows > 0) {
+    a.n_probs = nprobs_; a.state = state_;
+    a.batch = rows; a.slots = bslots_; a.logits_ld = ld;
+  } else {
+    a.n_probs = nprobs_ + slot; a.state = state_ + (size_t)S_NSTATE * slot;
+  }
+  logprobs(a, s);
+  HIPCHK(hipMemcpyAsync(h_lp_ + off, lp_rec_ + off, sizeof(unsigned) * kLogprobRecWords * std::max(rows, 1),
+                        hipMemcpyDeviceToHost, s));
+  ++lp_launches_;
+}
+
+LogprobEntry Engine::read_logprob(size_t off) const {
+  const unsigned* r = h_lp_ + off;
+  LogprobEntry e;
+  std::memcpy(&e.logprob, r, sizeof(float));
+  const int n = std::min(std::max((int)r[1], 0), kMaxLogprobs);
+  for (int i = 0; i < n; ++i) {
+    float lp;
+    std::memcpy(&lp, r + 2 + kMaxLogprobs + i, sizeof(float));
+    e.top.emplace_back((int)r[2 + i], lp);
+  }
+  return e;
+}
+
+std::vector<int> Engine::asking(const std::vector<int>& slots) const {
+  std::vector<int> ask(slots.size(), 0);
+  bool any = false;
+  for (size_t b = 0; b < slots.size(); ++b) any |= (ask[b] = h_nprobs_[slots[b]]) > 0;
+  return any ? ask : std::vector<int>{};
+}
+
+void Engine::collect_logprobs(int par, const std::vector<int>& ask) {
+  last_lp_.clear();
+  for (size_t b = 0; b < ask.size(); ++b)
+    last_lp_.push_back(ask[b] > 0 ? read_logprob(lp_off_flight(par, (int)b)) : LogprobEntry{});
+}
+
+std::vector<LogprobEntry> Engine::step_logprobs() {
+  ExecGuard guard(this);
+  return last_lp_;
 }
 
 void Engine::enqueue_layer_decode(int l, hipStream_t s) {
@@ -1173,6 +1241,8 @@ void Engine::launch_step(int slot) {
 // ------------------------------------------------------------------------ generation
 SamplerParamsDev Engine::make_sparams(const SamplingOpts& sp) const {
   if (sp.top_k < 0 || sp.top_k > 64) throw std::runtime_error("GPU sampler: top_k must be in [0, 64]");
+  if (sp.n_probs > kMaxLogprobs) throw std::runtime_error("GPU sampler: at most 20 logprobs per token");
+  if (sp.n_probs > 0 && !lp_rec_) throw std::runtime_error("GPU sampler: logprobs need one rank holding the head");
   SamplerParamsDev p;
   p.greedy = sp.temp <= 0.f ? 1 : 0;
   p.top_k = p.greedy ? 1 : (sp.top_k == 0 ? 64 : sp.top_k);
@@ -1207,6 +1277,10 @@ void Engine::begin_slot_state(int slot, const std::vector<int>& prompt, const Sa
   HIPCHK(hipMemcpyAsync(sparams_ + slot, &p, sizeof(p), hipMemcpyHostToDevice, stream_));
   HIPCHK(hipMemcpyAsync(ring_ + 64 * slot, hring, sizeof(hring), hipMemcpyHostToDevice, stream_));
   HIPCHK(hipMemcpyAsync(state_ + (size_t)S_NSTATE * slot, hstate, sizeof(hstate), hipMemcpyHostToDevice, stream_));
+  const int n_probs = std::max(sp.n_probs, 0);
+  if (nprobs_ && n_probs != h_nprobs_[slot])
+    HIPCHK(hipMemcpyAsync(nprobs_ + slot, &n_probs, sizeof(int), hipMemcpyHostToDevice, stream_));
+  h_nprobs_[slot] = n_probs;
   HIPCHK(hipStreamSynchronize(stream_));  // the host arrays are on this stack frame
 }
 
@@ -1698,6 +1772,7 @@ void Engine::prefill_chunk(int slot, const int* toks, int T, int pos, bool head)
     HIPCHK(hipMemcpyAsync(tokens_, h_tokens_, sizeof(int) * T, hipMemcpyHostToDevice, stream_));
     enqueue_prefill(T, pos, stream_);
     if (head) enqueue_head(x_ + (size_t)(T - 1) * hp_.n_embd, 0, stream_, slot);
+    if (head && h_nprobs_[slot] > 0) enqueue_logprobs(logits_, 0, 0, slot, lp_off_first(slot), stream_);
     HIPCHK(hipStreamSynchronize(stream_));  // h_tokens_ is reused by the next chunk
   } catch (...) {
     kv_slot_ = 0;
@@ -1743,10 +1818,12 @@ int Engine::slot_begin_part(int slot, const std::vector<int>& prompt, int n_keep
     prefill_chunk(slot, prompt.data() + pos, T, pos, pos + T == n_prompt);
     pos += T;
   }
+  last_lp_.clear();
   if (end < n_prompt) return -1;
   int tok = 0;
   HIPCHK(hipMemcpy(&tok, state_ + (size_t)S_NSTATE * slot + S_TOKEN, sizeof(int), hipMemcpyDeviceToHost));
   check_device_err();
+  if (h_nprobs_[slot] > 0) last_lp_.push_back(read_logprob(lp_off_first(slot)));
   return tok;
 }
 
@@ -1762,6 +1839,8 @@ int Engine::slot_begin_impl(int slot, const std::vector<int>& prompt, int n_keep
   int tok = 0;
   HIPCHK(hipMemcpy(&tok, state_ + (size_t)S_NSTATE * slot + S_TOKEN, sizeof(int), hipMemcpyDeviceToHost));
   check_device_err();
+  last_lp_.clear();
+  if (h_nprobs_[slot] > 0) last_lp_.push_back(read_logprob(lp_off_first(slot)));
   return tok;
 }
 
@@ -1820,7 +1899,10 @@ std::vector<int> Engine::slots_begin_impl(const std::vector<int>& slots, const s
     }
     segs_ = nullptr;
     for (const PrefillSeg& g : segs)
-      if (g.last) enqueue_head(x_ + (size_t)(g.row + g.n - 1) * d, 0, stream_, g.slot);
+      if (g.last) {
+        enqueue_head(x_ + (size_t)(g.row + g.n - 1) * d, 0, stream_, g.slot);
+        if (h_nprobs_[g.slot] > 0) enqueue_logprobs(logits_, 0, 0, g.slot, lp_off_first(g.slot), stream_);
+      }
     HIPCHK(hipStreamSynchronize(stream_));  // the pinned row metadata is rewritten next
     segs.clear();
     rows = 0;
@@ -1847,6 +1929,10 @@ std::vector<int> Engine::slots_begin_impl(const std::vector<int>& slots, const s
   for (size_t i = 0; i < n; ++i)
     HIPCHK(hipMemcpy(&out[i], state_ + (size_t)S_NSTATE * slots[i] + S_TOKEN, sizeof(int), hipMemcpyDeviceToHost));
   check_device_err();
+  last_lp_.clear();
+  if (!asking(slots).empty())
+    for (size_t i = 0; i < n; ++i)
+      last_lp_.push_back(h_nprobs_[slots[i]] > 0 ? read_logprob(lp_off_first(slots[i])) : LogprobEntry{});
   return out;
 }
 
@@ -1889,6 +1975,7 @@ void Engine::batch_launch_impl(const std::vector<int>& slots) {
     ~Par() { p = 0; }
   } par{launch_par_};
   launch_par_ = i;
+  fl_ask_[i] = asking(slots);
   enqueue_batch_launch(slots, h_btok2_[i]);
   HIPCHK(hipEventRecord(bev_[i], stream_));
   fl_B_[i] = B;
@@ -1917,6 +2004,7 @@ std::vector<int> Engine::batch_collect_impl() {
   check_device_err();
   last_batch_ = fl_B_[i];
   last_b1_ = fl_b1_[i];
+  collect_logprobs(i, fl_ask_[i]);
   return std::vector<int>(h_btok2_[i], h_btok2_[i] + fl_B_[i]);
 }
 
@@ -1941,6 +2029,7 @@ std::vector<int> Engine::batch_step_impl(const std::vector<int>& slots) {
   HIPCHK(hipGetLastError());
   check_device_err();
   last_batch_ = B;
+  collect_logprobs(0, asking(slots));
   return std::vector<int>(dst, dst + B);
 }
 
@@ -1952,6 +2041,7 @@ void Engine::enqueue_batch_launch(const std::vector<int>& slots, int* h_dst) {
     launch_step(slots[0]);
     HIPCHK(hipMemcpyAsync(h_dst, state_ + (size_t)S_NSTATE * slots[0] + S_TOKEN, sizeof(int),
                           hipMemcpyDeviceToHost, stream_));
+    if (h_nprobs_[slots[0]] > 0) enqueue_logprobs(logits_, 0, 0, slots[0], lp_off_flight(launch_par_, 0), stream_);
     last_b1_ = true;
     return;
   }
@@ -1984,11 +2074,13 @@ void Engine::enqueue_batch_launch(const std::vector<int>& slots, int* h_dst) {
       }
     }
     HIPCHK(hipGraphLaunch(launch_par_ ? bgraph2_[B] : bgraph_[B], stream_));
-    if (h_dst == h_btok2_[launch_par_ ? 1 : 0]) return;  // (the graph's sampler stored them there)
   } else {
     enqueue_batch_step(B, stream_);
   }
-  HIPCHK(hipMemcpyAsync(h_dst, btok_out_, sizeof(int) * B, hipMemcpyDeviceToHost, stream_));
+  // (the graph's sampler stored the tokens in its own parity's host-mapped buffer)
+  if (!opt_.use_graph || h_dst != h_btok2_[launch_par_ ? 1 : 0])
+    HIPCHK(hipMemcpyAsync(h_dst, btok_out_, sizeof(int) * B, hipMemcpyDeviceToHost, stream_));
+  if (!asking(slots).empty()) enqueue_logprobs(logits_b_, B, V_pad_, 0, lp_off_flight(launch_par_, 0), stream_);
 }
 
 // Rows [0, B) of a logits buffer with row pitch ld_src holding this rank's vocabulary shard
@@ -2045,7 +2137,8 @@ std::vector<float> Engine::batch_logits_impl(int B) {
 
 GenOut Engine::generate(const std::vector<int>& prompt, int n_keep, int max_new, const SamplingOpts& sp,
                         const std::vector<int>& stop_ids, const std::function<bool()>& poll,
-                        const std::function<void(int)>& on_token) {
+                        const std::function<void(int)>& on_token,
+                        const std::function<void(const LogprobEntry&)>& on_logprob) {
   if (!has_head()) throw std::runtime_error("generate: this layer-split stage holds no head (eval_stage)");
   ExecGuard guard(this);
   GenOut out;
@@ -2090,6 +2183,7 @@ GenOut Engine::generate(const std::vector<int>& prompt, int n_keep, int max_new,
     for (int s : stop_ids) if (s == t) return true;
     return false;
   };
+  const bool lp = sp.n_probs > 0;
   // one decode step: the followers replay exactly the steps rank 0 launches, so a stop
   // token, a cancel or max_new on rank 0 ends every rank at the same step
   auto step = [&](int k) {
@@ -2099,11 +2193,19 @@ GenOut Engine::generate(const std::vector<int>& prompt, int n_keep, int max_new,
       mirror(m);
     }
     launch_step();
+    // (step k's record goes to the buffer of its parity: the host has read step k - 2's by then)
+    if (lp) enqueue_logprobs(logits_, 0, 0, 0, lp_off_gen(k % kDepth), stream_);
     HIPCHK(hipEventRecord(step_ev_[k % kDepth], stream_));
+  };
+  auto emit_logprob = [&](size_t off) {
+    if (!lp) return;
+    out.logprobs.push_back(read_logprob(off));
+    if (on_logprob) on_logprob(out.logprobs.back());
   };
   RoctxRange decode_range("lfk.decode");
   int tok = h_ring_[0];
   out.tokens.push_back(tok);
+  emit_logprob(lp_off_first(0));
   if (on_token) on_token(tok);
   out.finish = "length";
   const int max_steps = std::min(max_new - 1, opt_.n_ctx - n_prompt);
@@ -2116,6 +2218,7 @@ GenOut Engine::generate(const std::vector<int>& prompt, int n_keep, int max_new,
       HIPCHK(hipEventSynchronize(step_ev_[(i - 1) % kDepth]));
       tok = h_ring_[i & 63];
       out.tokens.push_back(tok);
+      emit_logprob(lp_off_gen((i - 1) % kDepth));
       if (on_token) on_token(tok);
       if (is_stop(tok)) { out.finish = "stop"; break; }
       if (poll && (i & 3) == 0 && poll()) { out.finish = "cancelled"; break; }

@@ -62,6 +62,7 @@ struct GenOut {
   int n_evaluated = 0;
   int n_prefilled = 0;
   double prefill_s = 0, decode_s = 0;
+  std::vector<LogprobEntry> logprobs;  // one per token when SamplingOpts::n_probs > 0, else empty
 };
 
 struct Layer {
@@ -137,7 +138,8 @@ class Engine : public SlotBackend {
 
   GenOut generate(const std::vector<int>& prompt, int n_keep, int max_new, const SamplingOpts& sp,
                   const std::vector<int>& stop_ids, const std::function<bool()>& poll,
-                  const std::function<void(int)>& on_token);
+                  const std::function<void(int)>& on_token,
+                  const std::function<void(const LogprobEntry&)>& on_logprob = {});  // called before on_token
   // test hooks (numerics vs the reference model)
   std::vector<float> eval_logits(const std::vector<int>& tokens, int pos0);  // prefill path
   std::vector<float> decode_logits(int token, int pos);                      // decode path (eager)
@@ -238,6 +240,12 @@ class Engine : public SlotBackend {
   bool can_pipeline() const override { return bmax_ > 0; }
   void batch_launch(const std::vector<int>& slots) override;
   std::vector<int> batch_collect() override;
+  // Token log-probabilities on the device (sampler.hip logprobs; one rank only): every place a
+  // token is sampled queues the two launches on the stream right behind that step when a slot of
+  // it asks (SamplingOpts::n_probs), outside the captured graphs, and reads the records back with
+  // the step's tokens. logprob_launches counts those queued pairs (0 while nobody asks).
+  std::vector<LogprobEntry> step_logprobs() override;
+  long long logprob_launches() const { return lp_launches_.load(); }
   std::vector<float> batch_logits(int B);  // test hook: logits [B][n_vocab] of the last batch_step
   // inspection hook (tests): the plan of every layer for a batched step over B rows; queues no work
   std::vector<BatchLayerPlan> batch_plan(int B);
@@ -448,6 +456,28 @@ class Engine : public SlotBackend {
   int fl_head_ = 0, fl_n_ = 0;
   void check_batch_rows(const std::vector<int>& slots) const;
   void enqueue_batch_launch(const std::vector<int>& slots, int* h_dst);
+  // ---- token log-probabilities. Records live in lp_rec_ (device) and its pinned mirror h_lp_, in
+  // three regions of kLogprobRecWords-word records: [2][lp_rows_] one per row of the batch step of
+  // each flight parity (two steps are in flight), [2] generate()'s steps by parity (it may run
+  // while the scheduler has steps queued), [n_slots] each slot's first token (prefill).
+  int lp_rows_ = 1;
+  size_t lp_off_flight(int par, int row) const { return ((size_t)par * lp_rows_ + row) * kLogprobRecWords; }
+  size_t lp_off_gen(int par) const { return ((size_t)2 * lp_rows_ + par) * kLogprobRecWords; }
+  size_t lp_off_first(int slot) const { return ((size_t)2 * lp_rows_ + 2 + slot) * kLogprobRecWords; }
+  int* nprobs_ = nullptr;          // [n_slots] device: entries each slot's request asks for
+  std::vector<int> h_nprobs_;      // ... and what the host knows of it
+  float* lp_part_ = nullptr;       // [lp_rows_][logprob_part_words(n_vocab)] stage-1 output
+  unsigned* lp_rec_ = nullptr;
+  unsigned* h_lp_ = nullptr;
+  std::atomic<long long> lp_launches_{0};
+  std::vector<int> fl_ask_[2];     // per flight parity: n_probs of each row at its launch (0: none)
+  std::vector<LogprobEntry> last_lp_;
+  // rows == 0: the single row `slot` of `logits`; else rows of the batch (bslots_). The records go
+  // to word offset `off` of lp_rec_ and from there to h_lp_ (no sync)
+  void enqueue_logprobs(const float* logits, int rows, size_t ld, int slot, size_t off, hipStream_t s);
+  LogprobEntry read_logprob(size_t off) const;
+  std::vector<int> asking(const std::vector<int>& slots) const;  // n_probs per row; empty: nobody asks
+  void collect_logprobs(int par, const std::vector<int>& ask);   // -> last_lp_
   void batch_launch_impl(const std::vector<int>& slots);
   std::vector<int> batch_collect_impl();
   int bslots_n_ = -1;         // rows of the row -> slot map last uploaded to bslots_

@@ -70,6 +70,7 @@ SchedPoll BatchScheduler::wait(int64_t id, size_t have, int timeout_ms) {
                    [&] { return r->done || r->tokens.size() > have; });
   SchedPoll p;
   if (r->tokens.size() > have) p.tokens.assign(r->tokens.begin() + have, r->tokens.end());
+  if (r->lps.size() > have) p.logprobs.assign(r->lps.begin() + have, r->lps.end());
   p.done = r->done;
   p.finish = r->finish;
   p.error = r->error;
@@ -124,8 +125,9 @@ void BatchScheduler::finish(Req& r, const char* reason) {
 // caller holds mu_. The KV of the row now holds every token but the newest one, which the
 // next batch_step feeds; a row ends on a stop id, max_new, a cancel, or when that next
 // step would write past the context.
-void BatchScheduler::push_token(Req& r, int tok) {
+void BatchScheduler::push_token(Req& r, int tok, const LogprobEntry* lp) {
   r.tokens.push_back(tok);
+  if (r.sp.n_probs > 0) r.lps.push_back(lp ? *lp : LogprobEntry{});
   if (std::find(r.stop_ids.begin(), r.stop_ids.end(), tok) != r.stop_ids.end()) return finish(r, "stop");
   if ((int)r.tokens.size() >= r.max_new) return finish(r, "length");
   if ((int)(r.prompt.size() + r.tokens.size()) - 1 >= eng_.n_ctx()) return finish(r, "length");
@@ -220,10 +222,12 @@ void BatchScheduler::loop() {
         }
         std::string err;
         std::vector<int> toks;
+        std::vector<LogprobEntry> lps;
         lk.unlock();
         try {
           toks = adm.size() == 1 ? std::vector<int>{eng_.slot_begin(a_slot[0], prompts[0], a_keep[0], sps[0])}
                                  : eng_.slots_begin(a_slot, prompts, a_keep, sps);
+          lps = eng_.step_logprobs();
         } catch (const std::exception& e) {
           err = e.what();
         }
@@ -242,7 +246,7 @@ void BatchScheduler::loop() {
           st_.reused_tokens += a_keep[i];
           r.n_prefilled = (int)r.prompt.size() - a_keep[i];
           slot_hist_[a_slot[i]] = r.prompt;
-          push_token(r, toks[i]);
+          push_token(r, toks[i], i < lps.size() ? &lps[i] : nullptr);
         }
         if (adm.size() > 1) ++st_.joint_admissions;
         cv_out_.notify_all();  // the first tokens reach their waiters now, not after the next step
@@ -262,9 +266,11 @@ void BatchScheduler::loop() {
         SamplingOpts sp = r->sp;
         std::string err;
         int tok = -1;
+        std::vector<LogprobEntry> lps;
         lk.unlock();
         try {
           tok = eng_.slot_begin_part(slot, prompt, keep, done, n, sp);
+          if (tok >= 0) lps = eng_.step_logprobs();
         } catch (const std::exception& e) {
           err = e.what();
         }
@@ -285,7 +291,7 @@ void BatchScheduler::loop() {
           st_.reused_tokens += keep;
           r->n_prefilled = (int)prompt.size() - keep;
           slot_hist_[slot] = prompt;
-          push_token(*r, tok);
+          push_token(*r, tok, lps.empty() ? nullptr : &lps[0]);
           cv_out_.notify_all();
         }
       }
@@ -305,12 +311,14 @@ void BatchScheduler::loop() {
       }
     if (rows.empty() && flights.empty()) continue;
     std::vector<int> out;
+    std::vector<LogprobEntry> out_lp;  // the step's entries, row by row (empty: nobody asked)
     std::string err;
     Flight cur;
     lk.unlock();
     try {
       if (!pipeline_) {
         out = eng_.batch_step(rows);
+        out_lp = eng_.step_logprobs();
         cur.rows = rows;
         cur.req = row_req;
       } else {
@@ -341,6 +349,7 @@ void BatchScheduler::loop() {
         cur = flights.front();
         flights.pop_front();
         out = eng_.batch_collect();
+        out_lp = eng_.step_logprobs();
       }
     } catch (const std::exception& e) {
       err = e.what();
@@ -372,7 +381,7 @@ void BatchScheduler::loop() {
       }
       if (r.done) continue;  // finished (or cancelled) after this step was queued: its token is dropped
       slot_hist_[cur.rows[b]].push_back(r.tokens.back());  // the token this step fed is now in the KV
-      push_token(r, out[b]);
+      push_token(r, out[b], b < out_lp.size() ? &out_lp[b] : nullptr);
     }
     cv_out_.notify_all();
   }

@@ -38,6 +38,7 @@ namespace lfk {
 
 struct SchedPoll {
   std::vector<int> tokens;   // tokens [have, have + n) of the request
+  std::vector<LogprobEntry> logprobs;  // ... and their entries, when the request asked (n_probs > 0)
   bool done = false;
   std::string finish;        // "stop" | "length" | "cancelled" | "error" once done
   std::string error;
@@ -82,6 +83,7 @@ class BatchScheduler {
     SamplingOpts sp;
     std::vector<int> stop_ids;
     std::vector<int> tokens;
+    std::vector<LogprobEntry> lps;  // one per token when sp.n_probs > 0 (else empty)
     int slot = -1;
     int n_prefilled = 0;
     int n_keep = 0;
@@ -92,7 +94,9 @@ class BatchScheduler {
   };
   void loop();
   void finish(Req& r, const char* reason);
-  void push_token(Req& r, int tok);       // append one sampled token; may finish the row
+  // append one sampled token (and, for a request that asked, its entry of the engine's
+  // step_logprobs); may finish the row
+  void push_token(Req& r, int tok, const LogprobEntry* lp = nullptr);
   int pick_slot(const std::vector<int>& prompt, int* lcp);
 
   SlotBackend& eng_;

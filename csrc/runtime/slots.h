@@ -16,6 +16,15 @@ struct SamplingOpts {
   unsigned long long seed = 0;
   float tfs_z = 1.f, typical_p = 1.f;
   std::vector<std::pair<int, float>> logit_bias;  // distinct tokens, at most kMaxLogitBias
+  int n_probs = 0;  // > 0: log-probabilities of every generated token, with the n_probs most probable ones
+};
+
+// One generated token's log-probabilities of the raw logits (engine/sampling.py:token_logprobs):
+// its own, and the most probable tokens by (value descending, id ascending). `top` is empty for a
+// token whose request did not ask.
+struct LogprobEntry {
+  float logprob = 0.f;
+  std::vector<std::pair<int, float>> top;
 };
 
 class SlotBackend {
@@ -55,6 +64,11 @@ class SlotBackend {
   }
   virtual void batch_launch(const std::vector<int>& slots) { (void)slots; }
   virtual std::vector<int> batch_collect() { return {}; }
+  // Log-probability entries of the tokens the LAST slot_begin / slots_begin / completing
+  // slot_begin_part / batch_step / batch_collect returned, one per token in the same order (an
+  // entry with an empty `top` for a slot that did not ask). None at all: no slot asked, or the
+  // backend computes none.
+  virtual std::vector<LogprobEntry> step_logprobs() { return {}; }
 };
 
 }  // namespace lfk

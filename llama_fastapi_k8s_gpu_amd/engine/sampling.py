@@ -78,13 +78,14 @@ class SamplingParams:
     def greedy(self) -> bool:
         return self.temperature <= 0.0
 
-    def gpu_compatible(self, vocab: int) -> bool:
+    def gpu_compatible(self, vocab: int, max_logprobs: int = 0) -> bool:
         """Whether the on-device chain (csrc/kernels/sampler.hip) computes exactly this
         chain: top-k within its 64-candidate window, few enough bias entries, no
-        mirostat, no host-side log-probabilities."""
+        mirostat, and no more log-probabilities per token than the backend computes on
+        the device (``max_logprobs``; 0: none, such requests take the host route)."""
         if self.mirostat_mode and not self.greedy():
             return False
-        if self.n_probs > 0 or self.logits_processor is not None or self.grammar is not None \
+        if self.n_probs > max_logprobs or self.logits_processor is not None or self.grammar is not None \
                 or len(self.logit_bias) > GPU_MAX_LOGIT_BIAS:
             return False
         if self.greedy():

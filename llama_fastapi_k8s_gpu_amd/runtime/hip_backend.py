@@ -74,8 +74,14 @@ def gpu_sampling_dict(params: SamplingParams, n_vocab: int) -> dict:
             "temperature": params.temperature, "repeat_penalty": params.repeat_penalty,
             "frequency_penalty": params.frequency_penalty, "presence_penalty": params.presence_penalty,
             "last_n": params.last_n, "seed": params.seed & 0xFFFFFFFFFFFFFFFF, "tfs_z": params.tfs_z,
-            "typical_p": params.typical_p,
+            "typical_p": params.typical_p, "n_probs": max(0, int(params.n_probs)),
             "logit_bias": {int(t): float(b) for t, b in params.logit_bias.items() if 0 <= int(t) < n_vocab}}
+
+
+def _entry(e):
+    """An engine log-probability entry in the shape of ``token_logprobs``."""
+    return float(e[0]), [(int(t), float(v)) for t, v in e[1]]
+
 
 class HipBackend:
     name = "hip"
@@ -98,6 +104,9 @@ class HipBackend:
         if device is None:
             device = local if size > 1 else (main_gpu if split_mode in ("none", "layer") and main_gpu else local)
         self.tp_rank, self.tp_size = rank, size
+        # log-probabilities per token the device computes (csrc/kernels/sampler.hip logprobs): one
+        # rank only; under tensor parallelism such requests keep the host route
+        self.max_logprobs = int(hip.MAX_LOGPROBS) if size == 1 else 0
         max_batch = max(1, int(max_batch or 1))
         self.max_batch = max_batch
         self.engine = hip.Engine(model_path, n_ctx=n_ctx, n_batch=min(n_batch, n_ctx), device=device,
@@ -146,7 +155,8 @@ class HipBackend:
 
     def health(self):
         h = {"ok": bool(self.engine.healthy), "backend": self.name, "tp": self.tp_size,
-             "error": self.engine.last_error or None}
+             "error": self.engine.last_error or None,
+             "logprob_launches": int(self.engine.logprob_launches)}
         if self.sched is not None:
             h["batching"] = dict(self.sched.stats(), max_batch=self.max_batch)
         return h
@@ -155,7 +165,7 @@ class HipBackend:
         """Whether this request runs as a row of the continuous batch (the facade then
         skips its single-sequence lock and KV prefix bookkeeping: the scheduler reuses
         prefixes per slot)."""
-        return self.sched is not None and params.gpu_compatible(self.n_vocab)
+        return self.sched is not None and params.gpu_compatible(self.n_vocab, self.max_logprobs)
 
     def close(self):
         if self.sched is not None:
@@ -174,11 +184,16 @@ class HipBackend:
                           on_token: Optional[Callable[[int], None]]) -> GenerationResult:
         rid = self.sched.submit(list(prompt), int(max_new), self._sp(params), list(stop_ids))
         toks = []
+        lps = [] if params.n_probs > 0 else None
         try:
             while True:
                 r = self.sched.wait(rid, len(toks), 20)
-                for t in r["tokens"]:
+                for i, t in enumerate(r["tokens"]):
                     toks.append(t)
+                    if lps is not None:
+                        lps.append(_entry(r["logprobs"][i]))
+                        if params.logprob_cb is not None:
+                            params.logprob_cb(lps[-1])  # before on_token, as host_generate
                     if on_token:
                         on_token(t)
                 if r["done"]:
@@ -190,20 +205,25 @@ class HipBackend:
         if r["finish"] == "error":
             raise RuntimeError(r["error"] or "batched generation failed")
         return GenerationResult(toks, r["finish"], len(prompt) + max(0, len(toks) - 1), r["prefill_s"],
-                                r["decode_s"], int(r["n_prefilled"]))
+                                r["decode_s"], int(r["n_prefilled"]), lps)
 
     def generate(self, prompt: Sequence[int], n_keep: int, max_new: int, params: SamplingParams,
                  stop_ids: Sequence[int], poll: Optional[Callable[[], bool]] = None,
                  on_token: Optional[Callable[[int], None]] = None) -> GenerationResult:
-        if not params.gpu_compatible(self.n_vocab):
+        if not params.gpu_compatible(self.n_vocab, self.max_logprobs):
             return host_generate(self._forward, prompt, n_keep, max_new, params, stop_ids, self.n_ctx, poll,
                                  on_token)
         if self.sched is not None:
             return self._generate_batched(prompt, max_new, params, stop_ids, poll, on_token)
         sp = self._sp(params)
-        r = self.engine.generate(list(prompt), int(n_keep), int(max_new), sp, list(stop_ids), poll, on_token)
+        on_lp = None
+        if params.n_probs > 0 and params.logprob_cb is not None:
+            def on_lp(e, cb=params.logprob_cb):  # the engine calls it right before on_token
+                cb(_entry(e))
+        r = self.engine.generate(list(prompt), int(n_keep), int(max_new), sp, list(stop_ids), poll, on_token, on_lp)
+        lps = [_entry(e) for e in r["logprobs"]] if params.n_probs > 0 else None
         return GenerationResult(list(r["tokens"]), r["finish"], int(r["n_evaluated"]), r["prefill_s"],
-                                r["decode_s"], int(r["n_prefilled"]))
+                                r["decode_s"], int(r["n_prefilled"]), lps)
 
     def save_kv(self, n: int, on_device: bool = False):
         """KV snapshot of positions [0, n): host bytes, or (``on_device``) an HBM buffer

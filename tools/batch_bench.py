@@ -18,6 +18,9 @@ def main():
     ap.add_argument("--prompt", type=int, default=300)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--batches", default="1,2,4,6,8")
+    ap.add_argument("--n-probs", type=int, default=0, help="> 0: also time steps whose rows ask for this many logprobs")
+    ap.add_argument("--logprob-rows", default="0,1,6", help="how many of the B = 6 rows ask (one sweep each)")
+    ap.add_argument("--reps", type=int, default=3, help="repetitions of each logprob timing")
     args = ap.parse_args()
     import numpy as np
     from llama_fastapi_k8s_gpu_amd.gguf.synthetic import cached_synthetic_gguf
@@ -59,6 +62,36 @@ def main():
             eng.batch_collect()
             ms = (time.perf_counter() - t0) * 1e3 / args.steps
             res[f"B{B}_pipelined_ms_per_step"] = round(ms, 3)
+    # cost of device log-probabilities: the same steps with R of the rows asking for --n-probs
+    # entries (the two logprob launches queued behind each such step), against R = 0 in this run
+    if args.n_probs > 0:
+        B = min(6, eng.max_batch)
+        slots = list(range(B))
+
+        def timed(rows, pipelined):
+            eng.batch_step(rows)  # warm
+            t0 = time.perf_counter()
+            if pipelined:
+                eng.batch_launch(rows)
+                for _ in range(args.steps - 1):
+                    eng.batch_launch(rows)
+                    eng.batch_collect()
+                eng.batch_collect()
+            else:
+                for _ in range(args.steps):
+                    eng.batch_step(rows)
+            return round((time.perf_counter() - t0) * 1e3 / args.steps, 3)
+        for R in [int(r) for r in args.logprob_rows.split(",")]:
+            sps = [dict(sp, n_probs=args.n_probs if s < R else 0) for s in slots]
+            eng.slots_begin(slots, prompts[:B], [0] * B, sps)
+            n0 = eng.logprob_launches
+            for rep in range(args.reps):
+                key = f"lp{args.n_probs}_rows{R}_rep{rep}"
+                res[f"{key}_B{B}_ms"] = timed(slots, False)
+                res[f"{key}_B{B}_pipelined_ms"] = timed(slots, True)
+                if R <= 1:
+                    res[f"{key}_B1_ms"] = timed([0], False)
+            res[f"lp{args.n_probs}_rows{R}_launches"] = eng.logprob_launches - n0
     print(json.dumps(res), flush=True)
 
 
