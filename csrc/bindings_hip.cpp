@@ -213,6 +213,7 @@ PYBIND11_MODULE(_hip, m) {
              return logprob_entries_py(v);
            })
       .def_property_readonly("logprob_launches", &Engine::logprob_launches)
+      .def_property_readonly("wo_fused_enqueued", &Engine::wo_fused_enqueued)
       .def_property_readonly("can_pipeline", &Engine::can_pipeline)
       .def("batch_logits",
            [](Engine& e, int B) {
@@ -349,19 +350,26 @@ PYBIND11_MODULE(_hip, m) {
 
   m.def("gemv", [](uintptr_t w, int type, int rows, int K, uintptr_t x, uintptr_t norm, float eps, uintptr_t out,
                    int n_out, int epi, uintptr_t stream, int n_slots, uintptr_t ids, size_t expert_stride,
-                   int slot_stride, uintptr_t resid, int debug, uintptr_t dbg_clk) {
+                   int slot_stride, uintptr_t resid, int debug, uintptr_t dbg_clk, uintptr_t route_w, int route_E,
+                   int route_k, uintptr_t route_ids, uintptr_t route_wts, uintptr_t route_logits) {
     GemvArgs a;
     a.debug = debug;
     a.dbg_clk = P<long long>(dbg_clk);
     a.w = make_qmat(P<void>(w), type, rows, K, expert_stride);
     a.x = P<float>(x); a.norm_w = P<float>(norm); a.eps = eps; a.out = P<float>(out); a.n_out = n_out;
     a.n_slots = n_slots; a.expert_ids = P<int>(ids); a.out_slot_stride = slot_stride; a.resid = P<float>(resid);
+    // the routed SwiGLU (tests/test_decode_fused_gpu.py): the f32 router [route_E][K], the picks
+    // and the logits that block 0 writes
+    a.route_w = P<float>(route_w); a.route_E = route_E; a.route_k = route_k;
+    a.route_ids = P<int>(route_ids); a.route_wts = P<float>(route_wts); a.route_logits = P<float>(route_logits);
     gemv(a, epi, S(stream));
     hip_ok("gemv");
   }, py::arg("w"), py::arg("type"), py::arg("rows"), py::arg("K"), py::arg("x"), py::arg("norm"), py::arg("eps"),
      py::arg("out"), py::arg("n_out"), py::arg("epi"), py::arg("stream"), py::arg("n_slots") = 1,
      py::arg("ids") = 0, py::arg("expert_stride") = 0, py::arg("slot_stride") = 0, py::arg("resid") = 0,
-     py::arg("debug") = 0, py::arg("dbg_clk") = 0);
+     py::arg("debug") = 0, py::arg("dbg_clk") = 0, py::arg("route_w") = 0, py::arg("route_E") = 0,
+     py::arg("route_k") = 0, py::arg("route_ids") = 0, py::arg("route_wts") = 0, py::arg("route_logits") = 0);
+  m.def("gemv_route_fits", &gemv_route_fits);
 
   // the row-parallel decode GEMV with its epilogue all-reduce (GemvArgs::tp_*) for ONE rank of a
   // group whose regions the caller laid out (tests/test_tp_epilogue_gpu.py: a single process
@@ -672,6 +680,15 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("x"), py::arg("ldx"), py::arg("B"), py::arg("nw"), py::arg("eps"), py::arg("W"), py::arg("d"),
      py::arg("E"), py::arg("k"), py::arg("wd"), py::arg("ld"), py::arg("stream"));
 
+  // the single-row decode router: logits [E], ids / w [k] (the form the engine launches)
+  m.def("moe_router_fused", [](uintptr_t x, uintptr_t nw, float eps, uintptr_t W, int d, int E, int k, uintptr_t logits,
+                               uintptr_t ids, uintptr_t w, uintptr_t stream) {
+    moe_router_fused(P<float>(x), P<float>(nw), eps, P<float>(W), d, E, k, P<float>(logits), P<int>(ids), P<float>(w),
+                     S(stream));
+    hip_ok("moe_router_fused");
+  });
+  m.def("moe_router_fused_ok", &moe_router_fused_ok);
+
   // layer split (split_mode=layer): the whole generation over a chain of stage engines, natively
   m.def("chain_generate",
         [](std::vector<Engine*> stages, const std::vector<int>& prompt, int n_keep, int max_new, py::dict sp,
@@ -758,6 +775,32 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("k_off") = 0, py::arg("v_off") = 0, py::arg("ss") = 0, py::arg("inv_k") = 0.f, py::arg("eps") = 1e-5f,
      py::arg("rope_freq") = 0, py::arg("qkv_bias") = 0, py::arg("live") = 0, py::arg("qk_norm") = 0,
      py::arg("qkn_eps") = 1e-6f);
+  // the single-row decode attention and its Wo GEMV in one launch, set up as
+  // Engine::enqueue_layer_decode does (tests/test_decode_fused_gpu.py): attn_decode's single-row
+  // arguments, then done (64 ints the caller zeroed), Wo planar (w, type, n_out rows, K = n_head hd),
+  // x_out [n_out] (the residual, accumulated in place) and wait_err (an int the caller zeroed).
+  // False: the shape / type is not covered and nothing was launched.
+  m.def("attn_wo1", [](uintptr_t q, uintptr_t kc, uintptr_t vc, uintptr_t pos, int n_ctx, int n_head, int n_kv, int hd,
+                       float scale, uintptr_t part, uintptr_t out, uintptr_t stream, uintptr_t counters, uintptr_t done,
+                       uintptr_t w, int type, int n_out, int K, uintptr_t x_out, uintptr_t wait_err) {
+    if (K != n_head * hd || n_kv < 1 || n_kv > 64 || n_head % n_kv)
+      throw std::runtime_error("attn_wo1: Wo reads the attention's n_head hd outputs; at most 64 kv heads");
+    AttnDecodeArgs a;
+    a.q = P<float>(q); a.k_cache = P<__half>(kc); a.v_cache = P<__half>(vc); a.pos = P<int>(pos);
+    a.n_ctx = n_ctx; a.n_head = n_head; a.n_kv_head = n_kv; a.head_dim = hd; a.scale = scale;
+    a.part = P<float>(part); a.counters = P<int>(counters); a.out = P<float>(out);
+    a.done = P<int>(done);
+    GemvArgs o;
+    o.w = make_qmat(P<void>(w), type, n_out, K);
+    o.x = a.out; o.n_out = n_out; o.out = P<float>(x_out);
+    o.wait = a.done; o.wait_cnt = n_kv; o.wait_n = 1; o.wait_err = P<int>(wait_err);
+    const bool fused = attn_wo1(a, o, S(stream));
+    hip_ok("attn_wo1");
+    return fused;
+  }, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("pos"), py::arg("n_ctx"), py::arg("n_head"), py::arg("n_kv"),
+     py::arg("hd"), py::arg("scale"), py::arg("part"), py::arg("out"), py::arg("stream"), py::arg("counters"),
+     py::arg("done"), py::arg("w"), py::arg("type"), py::arg("n_out"), py::arg("K"), py::arg("x_out"),
+     py::arg("wait_err"));
   // split-K Q|K|V (BmmArgs::qkv_sk) over tile16 copies: RoPE'd partial sums added into out [B][ldo]
   // (Q at 0, K at nq, V at nq + nkv), the rows' sums of squares into ss_out [B]
   m.def("bmm_qkv_sk", [](uintptr_t wq, int tq, int nq, uintptr_t wk, int tk, uintptr_t wv, int tv, int nkv, int K,

@@ -187,11 +187,11 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const int bid, cons
 #pragma unroll
     for (int e = 0; e < EM; ++e) rw[e] = *reinterpret_cast<const float4*>(a.route_w + (size_t)min(e, E - 1) * K + i4);
     const float4 xv = xp.v[0], wv = xp.w[0];
-    float ss = xv.x * xv.x + xv.y * xv.y + xv.z * xv.z + xv.w * xv.w;
+    float ss = route_ss4(xv);
     const float4 n = make_float4(xv.x * wv.x, xv.y * wv.y, xv.z * wv.z, xv.w * wv.w);
     float racc[EM];
 #pragma unroll
-    for (int e = 0; e < EM; ++e) racc[e] = e < E ? n.x * rw[e].x + n.y * rw[e].y + n.z * rw[e].z + n.w * rw[e].w : 0.f;
+    for (int e = 0; e < EM; ++e) racc[e] = e < E ? route_dot4(n, rw[e]) : 0.f;
     ss = wave_sum_fast(ss);
 #pragma unroll
     for (int e = 0; e < EM; ++e) racc[e] = e < E ? wave_sum_fast(racc[e]) : 0.f;
@@ -601,6 +601,13 @@ void gemv(const GemvArgs& a, int epi, hipStream_t s) {
   if (a.n_out <= 0) return;
   // a type that is not compiled here goes to gemv_legacy.hip, which refuses what it does not have either
   LFK_DISPATCH(LFK_TYPES_GEMV_MAIN, a.w.type, gemv_legacy(a, epi, s), gemv_t<QT>(a, epi, s));
+}
+
+// launch_gemv's configuration of the same launch (K = 4096): launch_gemv_cfg has the routed kernel
+// under NR * U <= 4 alone. At 8192 <= rows < 16384 the K-quants get (4, 2) and the launch throws.
+bool gemv_route_fits(int type, int n_out, int n_slots) {
+  const GemvCfg c = pick_cfg(type, 2 * n_out * n_slots, 4096 >> 5, 2);
+  return c.nr * c.u <= 4;
 }
 #endif  // LFK_GEMV_LEGACY_TU
 

@@ -114,6 +114,11 @@ struct GemvArgs {
   int grid_div = 1;
 };
 void gemv(const GemvArgs& a, int epi, hipStream_t s);
+// Whether gemv() serves the routed SwiGLU form (GemvArgs::route_w, K = 4096) for experts of this
+// type with n_out features each over n_slots slots: the routed kernel exists in the
+// one-block-per-CU configurations only (rows x passes per item <= 4), and the configuration follows
+// from the row count. False: route with moe_router_fused and launch the gate/up unrouted.
+bool gemv_route_fits(int type, int n_out, int n_slots);
 
 // Batched decode projection on MFMA (bmm.hip): out[b][row] += W xh[b] for B <= 16 rows
 // (split-K atomics: `out` holds the residual or zeros). xh rows come from bprep: f16, the

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(1024) void moe_router_fused_kernel(const float* __r
   for (int i = tid * 4; i < d; i += 4096) {
     const float4 xv = *reinterpret_cast<const float4*>(x + i);
     const float4 wv = *reinterpret_cast<const float4*>(nw + i);
-    ss += xv.x * xv.x + xv.y * xv.y + xv.z * xv.z + xv.w * xv.w;
+    ss += route_ss4(xv);
     const float4 n = make_float4(xv.x * wv.x, xv.y * wv.y, xv.z * wv.z, xv.w * wv.w);
     // every row load unconditional (clamped row, result masked): a load under a
     // runtime `e < E` branch makes hipcc drain vmcnt per row (E dependent round trips)
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(1024) void moe_router_fused_kernel(const float* __r
     for (int e = 0; e < EM; ++e) r[e] = *reinterpret_cast<const float4*>(W + (size_t)min(e, E - 1) * d + i);
 #pragma unroll
     for (int e = 0; e < EM; ++e)
-      acc[e] += e < E ? n.x * r[e].x + n.y * r[e].y + n.z * r[e].z + n.w * r[e].w : 0.f;
+      acc[e] += e < E ? route_dot4(n, r[e]) : 0.f;
   }
   ss = wave_sum_fast(ss);
 #pragma unroll

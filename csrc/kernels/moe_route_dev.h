@@ -7,6 +7,22 @@
 
 namespace lfk {
 
+// One thread's share of the router sums over its float4 of x: the sum of squares, and the product
+// of the normalised input n = x * w_norm with a router row. Spelled with fmaf: left to
+// -ffp-contract=fast, which product of a sum becomes an fma's addend is the compiler's choice per
+// call site, and the two callers' logits differed in their last bits
+// (tests/test_decode_fused_gpu.py::test_routed_gate_up). The callers' own sums (moe.hip's
+// `ss +=` / `acc[e] +=` over the d / 4096 passes) must stay OUTSIDE these helpers, as plain adds of
+// a helper's result: an add written next to a product would be fused again, per site. This moved
+// every user of moe_router_fused_kernel by a few ulp - the single-row router and the batched rows
+// (moe_router_rows) alike.
+__device__ __forceinline__ float route_ss4(float4 x) {
+  return fmaf(x.w, x.w, fmaf(x.z, x.z, fmaf(x.y, x.y, x.x * x.x)));
+}
+__device__ __forceinline__ float route_dot4(float4 n, float4 r) {
+  return fmaf(n.w, r.w, fmaf(n.z, r.z, fmaf(n.y, r.y, n.x * r.x)));
+}
+
 // red[w][e] (e < EM): wave w's router partial of expert e; red[w][EM]: its sum of squares.
 // Lane j < k returns (id_j, w_j / sum of the k picks); lane e < E returns its logit in *logit.
 template <int EM, int NW>

@@ -850,6 +850,7 @@ void Engine::enqueue_layer_decode(int l, hipStream_t s) {
     o.out = x_;
     o.wait = aa.done; o.wait_cnt = nkv_l_; o.wait_n = 1; o.wait_err = wo_err_;
     fused = attn_wo1(aa, o, s);
+    if (fused) ++wo_fused_enq_;
     if (!fused) {
       aa.done = nullptr;
       o.wait = nullptr; o.wait_cnt = 0; o.wait_n = 0; o.wait_err = nullptr;
@@ -880,9 +881,12 @@ void Engine::enqueue_layer_decode(int l, hipStream_t s) {
 
   if (hp_.n_expert > 0) {
     // the router inside the gate/up GEMV's blocks (each block routes the token itself, block 0
-    // writes the picks for the down projection): one launch and one dependent boundary less
+    // writes the picks for the down projection): one launch and one dependent boundary less -
+    // where the launcher has the routed kernel for this rank's rows (gemv_route_fits: not at
+    // 8192 <= 2 F k < 16384, e.g. Mixtral-8x7B on 4 ranks), else the router launch before it
     const bool route_in_gu = moe_route_fuse_ && moe_router_fused_ok(L.router.type, hp_.n_expert, d) &&
-                             hp_.n_expert <= 8 && d == 4096;
+                             hp_.n_expert <= 8 && d == 4096 &&
+                             gemv_route_fits(L.gu_exps.type, F_l_, hp_.n_expert_used);
     if (route_in_gu) {
       // (routing happens in the gate/up launch below)
     } else if (moe_router_fused_ok(L.router.type, hp_.n_expert, d)) {  // one launch: norm + f32 router + top-k

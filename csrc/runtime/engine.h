@@ -246,6 +246,9 @@ class Engine : public SlotBackend {
   // the step's tokens. logprob_launches counts those queued pairs (0 while nobody asks).
   std::vector<LogprobEntry> step_logprobs() override;
   long long logprob_launches() const { return lp_launches_.load(); }
+  // inspection hook (tests): single-row decode layers enqueued as the one attention + Wo launch
+  // (attn_wo1) so far - per step when eager, per capture under a graph; 0 with LFK_WO_FUSE=0
+  long long wo_fused_enqueued() const { return wo_fused_enq_.load(); }
   std::vector<float> batch_logits(int B);  // test hook: logits [B][n_vocab] of the last batch_step
   // inspection hook (tests): the plan of every layer for a batched step over B rows; queues no work
   std::vector<BatchLayerPlan> batch_plan(int B);
@@ -470,6 +473,7 @@ class Engine : public SlotBackend {
   unsigned* lp_rec_ = nullptr;
   unsigned* h_lp_ = nullptr;
   std::atomic<long long> lp_launches_{0};
+  std::atomic<long long> wo_fused_enq_{0};
   std::vector<int> fl_ask_[2];     // per flight parity: n_probs of each row at its launch (0: none)
   std::vector<LogprobEntry> last_lp_;
   // rows == 0: the single row `slot` of `logits`; else rows of the batch (bslots_). The records go
