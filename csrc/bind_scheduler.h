@@ -2,6 +2,7 @@
 // the MI355X Engine) and the _cpu module (over a deterministic stand-in used by the tests).
 // Types are module-local: each extension registers its own copy.
 #pragma once
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -77,6 +78,30 @@ void bind_scheduler(pybind11::module_& m) {
              return d;
            },
            py::arg("id"), py::arg("have") = 0, py::arg("timeout_ms") = 50)
+      .def("submit_embed",
+           [](BatchScheduler& b, const std::vector<std::vector<int>>& inputs, int pooling, bool normalize) {
+             py::gil_scoped_release nogil;
+             return b.submit_embed(inputs, pooling, normalize);
+           },
+           py::arg("inputs"), py::arg("pooling"), py::arg("normalize") = false)
+      // vectors: one list of floats per input (pooling none: the input's rows, flattened)
+      .def("wait_embed",
+           [](BatchScheduler& b, int64_t id, int timeout_ms) {
+             SchedEmbedPoll p;
+             {
+               py::gil_scoped_release nogil;
+               p = b.wait_embed(id, timeout_ms);
+             }
+             py::dict d;
+             d["done"] = p.done;
+             py::list vs;
+             for (const auto& v : p.vectors) vs.append(py::array_t<float>(v.size(), v.data()));
+             d["vectors"] = vs;
+             d["finish"] = p.finish;
+             d["error"] = p.error;
+             return d;
+           },
+           py::arg("id"), py::arg("timeout_ms") = 50)
       .def("cancel", &BatchScheduler::cancel)
       .def("release", &BatchScheduler::release)
       .def("stats",
@@ -89,6 +114,9 @@ void bind_scheduler(pybind11::module_& m) {
              d["reused_tokens"] = s.reused_tokens;
              d["joint_admissions"] = s.joint_admissions;
              d["chunked_admissions"] = s.chunked_admissions;
+             d["embed_jobs"] = s.embed_jobs;
+             d["embed_inputs"] = s.embed_inputs;
+             d["embed_tokens"] = s.embed_tokens;
              d["active"] = s.active;
              d["pending"] = s.pending;
              d["slots"] = s.slots;

@@ -11,6 +11,7 @@
 #include "runtime/tp_channel.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <deque>
 #include <mutex>
@@ -73,6 +74,7 @@ class FakeSlotEngine : public SlotBackend {
     for (int i = 0; i < n_keep; ++i)
       if (kv[i] != prompt[i]) throw std::runtime_error("fake: reused prefix differs");
     kv.assign(prompt.begin(), prompt.end());
+    events_.push_back({0, prompt[0]});
     prefilled_ += (long long)prompt.size() - n_keep;
     cur_[slot] = next_token(kv, vocab_);
     last_lp_.assign(sp.n_probs > 0 ? 1 : 0, entry(slot));
@@ -118,6 +120,59 @@ class FakeSlotEngine : public SlotBackend {
     last_lp_.assign(sp.n_probs > 0 ? 1 : 0, entry(slot));
     return cur_[slot];
   }
+  // Text embeddings: the slot's "KV" becomes the input; the vector (kEmbedDim floats; pooling none:
+  // that many per token) is a pure function of the input's tokens, pooling and normalize, so a
+  // test can tell whose vector it got. Every call's row count is recorded.
+  static constexpr int kEmbedDim = 8;
+  static std::vector<float> embed_vector(const std::vector<int>& in, int pooling, bool normalize) {
+    const size_t rows = pooling == 0 ? in.size() : 1;
+    std::vector<float> v(rows * kEmbedDim);
+    for (size_t r = 0; r < rows; ++r) {
+      // none: row r depends on the tokens up to r (causal); pooled: on all of them
+      const std::vector<int> seq(in.begin(), pooling == 0 ? in.begin() + r + 1 : in.end());
+      double ss = 0;
+      for (int k = 0; k < kEmbedDim; ++k) {
+        std::vector<int> key(seq);
+        key.push_back(1000 + pooling);
+        key.push_back(k);
+        const float f = (float)next_token(key, 2001) / 1000.f - 1.f + 1e-3f;
+        v[r * kEmbedDim + k] = f;
+        ss += (double)f * f;
+      }
+      if (normalize)
+        for (int k = 0; k < kEmbedDim; ++k) v[r * kEmbedDim + k] = (float)(v[r * kEmbedDim + k] / std::sqrt(ss));
+    }
+    return v;
+  }
+  std::vector<std::vector<float>> embed_begin(const std::vector<int>& slots, const std::vector<std::vector<int>>& inputs,
+                                              int pooling, bool normalize) override {
+    if (step_us_ > 0) std::this_thread::sleep_for(std::chrono::microseconds(step_us_));
+    std::lock_guard<std::mutex> g(mu_);
+    if (slots.size() != inputs.size() || slots.empty()) throw std::runtime_error("fake: embed sizes");
+    if (embed_fail_) throw std::runtime_error("fake: injected embed fault");
+    std::vector<std::vector<float>> out;
+    int rows = 0;
+    for (size_t i = 0; i < slots.size(); ++i) {
+      const int slot = slots[i];
+      if (slot < 0 || slot >= n_slots_) throw std::runtime_error("fake: slot out of range");
+      for (size_t j = 0; j < i; ++j)
+        if (slots[j] == slot) throw std::runtime_error("fake: duplicate slot");
+      if (inputs[i].empty() || (int)inputs[i].size() > n_ctx_) throw std::runtime_error("fake: embed input length");
+      kv_[slot] = inputs[i];
+      rows += (int)inputs[i].size();
+      out.push_back(embed_vector(inputs[i], pooling, normalize));
+    }
+    embed_calls_.push_back({(int)slots.size(), rows, steps_ > 0 ? 1 : 0});
+    embed_slots_.push_back(slots);
+    events_.push_back({1, inputs[0][0]});
+    return out;
+  }
+  void embed_fail(bool on) { std::lock_guard<std::mutex> g(mu_); embed_fail_ = on; }
+  // one [inputs, rows, a step had run before] triple per embed_begin call; and each call's slots
+  std::vector<std::vector<int>> embed_calls() { std::lock_guard<std::mutex> g(mu_); return embed_calls_; }
+  std::vector<std::vector<int>> embed_slots() { std::lock_guard<std::mutex> g(mu_); return embed_slots_; }
+  // the order of whole-prompt admissions [0, first token] and embedding passes [1, first token of the first input]
+  std::vector<std::vector<int>> events() { std::lock_guard<std::mutex> g(mu_); return events_; }
   void set_prefill_chunk(int n) { chunk_ = n; }
   long long parts() { std::lock_guard<std::mutex> g(mu_); return parts_; }
   std::vector<int> batch_step(const std::vector<int>& slots) override {
@@ -175,6 +230,8 @@ class FakeSlotEngine : public SlotBackend {
   int chunk_ = 0;
   int max_rows_ = 0;
   bool pipeline_ = false;
+  bool embed_fail_ = false;
+  std::vector<std::vector<int>> embed_calls_, embed_slots_, events_;
   std::deque<std::vector<int>> queued_;
   std::vector<int> n_probs_;
   std::vector<LogprobEntry> last_lp_;
@@ -278,6 +335,9 @@ PYBIND11_MODULE(_cpu, m) {
              }
              return py::array_t<float>(v.size(), v.data());
            })
+      .def_property_readonly("out_norm", [](const CpuEngine& e) {
+        return py::array_t<float>(e.out_norm().size(), e.out_norm().data());
+      })
       .def_property_readonly("hparams", [](const CpuEngine& e) {
         const HParams& h = e.hparams();
         py::dict d;
@@ -287,6 +347,7 @@ PYBIND11_MODULE(_cpu, m) {
         d["rope_base"] = h.rope_base; d["rms_eps"] = h.rms_eps;
         d["arch"] = h.arch; d["rope_neox"] = h.rope_neox; d["qkv_bias"] = h.qkv_bias;
         d["qk_norm"] = h.qk_norm;
+        d["pooling_type"] = h.pooling_type;
         return d;
       })
       .def_property_readonly("n_vocab", &CpuEngine::n_vocab)
@@ -327,6 +388,12 @@ PYBIND11_MODULE(_cpu, m) {
       .def("fail_at", &FakeSlotEngine::fail_at)
       .def("set_pipeline", &FakeSlotEngine::set_pipeline)
       .def("set_prefill_chunk", &FakeSlotEngine::set_prefill_chunk)
+      .def_static("embed_vector", &FakeSlotEngine::embed_vector)
+      .def("embed_fail", &FakeSlotEngine::embed_fail)
+      .def_property_readonly("embed_calls", &FakeSlotEngine::embed_calls)
+      .def_property_readonly("embed_slots", &FakeSlotEngine::embed_slots)
+      .def_property_readonly("events", &FakeSlotEngine::events)
+      .def_property_readonly_static("EMBED_DIM", [](py::object) { return FakeSlotEngine::kEmbedDim; })
       .def_property_readonly("parts", &FakeSlotEngine::parts);
   bind_scheduler<FakeSlotEngine>(m);
 

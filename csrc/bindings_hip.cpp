@@ -186,6 +186,31 @@ PYBIND11_MODULE(_hip, m) {
              py::gil_scoped_release nogil;
              return e.slots_begin(slots, prompts, n_keep, o);
            })
+      // text embeddings (Engine::embed): float32 [n][n_embd], or for pooling 0 (none) a list of
+      // [n_tokens_i][n_embd] arrays
+      .def("embed",
+           [](Engine& e, const std::vector<int>& slots, const std::vector<std::vector<int>>& inputs, int pooling,
+              bool normalize) -> py::object {
+             std::vector<std::vector<float>> v;
+             {
+               py::gil_scoped_release nogil;
+               v = e.embed(slots, inputs, pooling, normalize);
+             }
+             const py::ssize_t d = e.hparams().n_embd;
+             if (pooling == POOL_NONE) {
+               py::list rows;
+               for (const auto& r : v) {
+                 py::array_t<float> a({(py::ssize_t)r.size() / d, d});
+                 std::memcpy(a.mutable_data(), r.data(), sizeof(float) * r.size());
+                 rows.append(a);
+               }
+               return rows;
+             }
+             py::array_t<float> a({(py::ssize_t)v.size(), d});
+             for (size_t i = 0; i < v.size(); ++i) std::memcpy(a.mutable_data(i, 0), v[i].data(), sizeof(float) * d);
+             return a;
+           },
+           py::arg("slots"), py::arg("inputs"), py::arg("pooling"), py::arg("normalize") = false)
       .def("batch_step",
            [](Engine& e, const std::vector<int>& slots) {
              py::gil_scoped_release nogil;
@@ -322,6 +347,7 @@ PYBIND11_MODULE(_hip, m) {
         d["rope_base"] = h.rope_base; d["rms_eps"] = h.rms_eps;
         d["arch"] = h.arch; d["rope_neox"] = h.rope_neox; d["qkv_bias"] = h.qkv_bias;
         d["qk_norm"] = h.qk_norm;
+        d["pooling_type"] = h.pooling_type;
         return d;
       });
 
@@ -899,6 +925,27 @@ PYBIND11_MODULE(_hip, m) {
     hip_ok("logprobs");
   }, py::arg("logits"), py::arg("V"), py::arg("n_probs"), py::arg("state"), py::arg("part"), py::arg("rec"),
      py::arg("stream"), py::arg("batch") = 0, py::arg("slots") = 0, py::arg("logits_ld") = 0, py::arg("stage") = 3);
+  m.attr("POOL_SEG_INTS") = kPoolSegInts;
+  m.attr("POOL_GROUP") = kPoolGroup;
+  // the embedding epilogue over raw buffers (kernels.h PoolArgs): `segs` is the host table,
+  // `segs_dev` its device copy; stage 1 = pool_rows, 2 = pool_finish. Returns the partial rows used.
+  m.def("pool", [](uintptr_t x, int rows, int ldx, uintptr_t w, float eps, int d, int mode, bool normalize,
+                   uintptr_t segs_dev, const std::vector<int>& segs, uintptr_t part, int part_rows, uintptr_t acc,
+                   uintptr_t out, int n_inputs, uintptr_t stream, int stage) {
+    if (segs.empty() || segs.size() % kPoolSegInts) throw std::runtime_error("pool: the table holds whole segments");
+    PoolArgs a;
+    a.x = P<const float>(x); a.rows = rows; a.ldx = ldx; a.w = P<const float>(w); a.eps = eps; a.d = d;
+    a.mode = mode; a.normalize = normalize; a.segs = P<const int>(segs_dev); a.h_segs = segs.data();
+    a.n_segs = (int)(segs.size() / kPoolSegInts); a.part = P<float>(part); a.part_rows = part_rows;
+    a.acc = P<float>(acc); a.out = P<float>(out); a.n_inputs = n_inputs;
+    const int need = pool_part_rows(a);
+    if (stage & 1) pool_rows(a, S(stream));
+    if (stage & 2) pool_finish(a, S(stream));
+    hip_ok("pool");
+    return need;
+  }, py::arg("x"), py::arg("rows"), py::arg("ldx"), py::arg("w"), py::arg("eps"), py::arg("d"), py::arg("mode"),
+     py::arg("normalize"), py::arg("segs_dev"), py::arg("segs"), py::arg("part"), py::arg("part_rows"),
+     py::arg("acc"), py::arg("out"), py::arg("n_inputs"), py::arg("stream"), py::arg("stage") = 3);
   m.def("sampler_params_bytes", [](int top_k, float top_p, float min_p, float temp, float rp, float fp, float pp,
                                    int last_n, unsigned long long seed, int greedy, float tfs_z, float typical_p,
                                    py::dict logit_bias) {

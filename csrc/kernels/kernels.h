@@ -681,6 +681,49 @@ void logprobs_stage1(const LogprobArgs& a, hipStream_t s);
 void logprobs_stage2(const LogprobArgs& a, hipStream_t s);
 void logprobs(const LogprobArgs& a, hipStream_t s);  // both stages
 
+// ---------------------------------------------------------------- embedding epilogue (misc.hip)
+// Text embeddings: the model's output RMSNorm over fp32 residual rows x[rows][ldx], pooled per input,
+// optionally L2-normalised. The rows of one launch are described by a table of segments (a piece of
+// one input inside a packed prefill chunk), kPoolSegInts ints each:
+//   [first row][row count][destination input][flags: kPoolFirst | kPoolLast][tokens of the whole input]
+// An input appears in at most one segment per launch; its pieces arrive in order over the launches
+// of one call, the accumulator row acc[input][d] carrying the sum between them.
+//   pool_rows   mean: one block per group of <= kPoolGroup consecutive rows of a segment stores the
+//               partial row w[c] * sum_r scale[r] x[r][c] (rows added in row order) to part[group][d];
+//               cls / last: one block per segment stores that one normed row when the segment holds
+//               it; none: every row is written normed (and L2-normalised if asked) to out[row][d].
+//   pool_finish one block per input: adds the input's partial rows in group order onto acc[input]
+//               (a first piece starts from zero) and, on the last piece, scales by 1 / tokens,
+//               L2-normalises if asked and writes out[input][d]. Not used by `none`.
+// No floating-point atomics: a store pass and an ordered sum pass, bit-equal from run to run.
+enum PoolMode { POOL_NONE = 0, POOL_MEAN = 1, POOL_CLS = 2, POOL_LAST = 3 };
+static constexpr int kPoolSegInts = 5;
+static constexpr int kPoolFirst = 1, kPoolLast = 2;
+static constexpr int kPoolGroup = 64;
+struct PoolArgs {
+  const float* x = nullptr;   // [rows][ldx]
+  int rows = 0, ldx = 0;
+  const float* w = nullptr;   // [d] output norm weight
+  float eps = 0.f;
+  int d = 0;                  // d % 4 == 0, d <= kPoolMaxD
+  int mode = POOL_MEAN;
+  bool normalize = false;
+  const int* segs = nullptr;    // device copy of the table
+  const int* h_segs = nullptr;  // host copy: checked (bounds of every buffer) before any launch
+  int n_segs = 0;
+  float* part = nullptr;      // [part_rows][d]
+  int part_rows = 0;
+  float* acc = nullptr;       // [n_inputs][d]
+  float* out = nullptr;       // [n_inputs][d]; none: [rows][d]
+  int n_inputs = 0;
+};
+static constexpr int kPoolMaxD = 16384;
+// partial rows a table needs (mean: its groups; cls / last: one per segment; none: 0); validates the
+// arguments against the host table and throws on a violation
+int pool_part_rows(const PoolArgs& a);
+void pool_rows(const PoolArgs& a, hipStream_t s);
+void pool_finish(const PoolArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------- synthetic fill
 // Random valid quant blocks generated on device (for synthetic models without a file).
 void fill_random_planar(uint8_t* base, int type, size_t rows, size_t K, float std, unsigned long long seed,

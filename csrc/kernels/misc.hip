@@ -266,6 +266,197 @@ void add_inplace(float* x, const float* y, int n, hipStream_t s) {
 __global__ void set_i32_kernel(int* p, int v) { *p = v; }
 void set_i32(int* p, int v, hipStream_t s) { hipLaunchKernelGGL(set_i32_kernel, dim3(1), dim3(1), 0, s, p, v); }
 
+// ---------------------------------------------------------------- embedding epilogue (kernels.h PoolArgs)
+// rsqrt(mean(x^2) + eps) of one row, by one wave (every lane returns it)
+__device__ __forceinline__ float pool_row_scale(const float* xr, int d, float eps, int lane) {
+  float ss = 0.f;
+  for (int i = lane * 4; i < d; i += 256) {
+    const float4 v = *reinterpret_cast<const float4*>(xr + i);
+    ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+  }
+  return rsqrtf(wave_sum(ss) / (float)d + eps);
+}
+
+// block-wide sum of one value per thread (256 threads): waves in order, every thread returns it
+__device__ __forceinline__ float pool_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();  // (red may still be read from a previous call)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// the segment that block `b` of pool_rows works on and its group inside it; false: past the table
+__device__ __forceinline__ bool pool_find(const int* segs, int n_segs, int mode, int b, int* seg, int* grp) {
+  for (int k = 0; k < n_segs; ++k) {
+    const int n = segs[k * kPoolSegInts + 1];
+    const int g = mode == POOL_CLS || mode == POOL_LAST ? 1 : (n + kPoolGroup - 1) / kPoolGroup;
+    if (b < g) {
+      *seg = k;
+      *grp = b;
+      return true;
+    }
+    b -= g;
+  }
+  return false;
+}
+
+__global__ __launch_bounds__(256) void pool_rows_kernel(const float* x, int ldx, const float* w, float eps, int d,
+                                                        int mode, int normalize, const int* segs, int n_segs,
+                                                        float* part, float* out) {
+  __shared__ float scale[kPoolGroup];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int k, g;
+  if (!pool_find(segs, n_segs, mode, blockIdx.x, &k, &g)) return;  // block-uniform
+  const int* sg = segs + k * kPoolSegInts;
+  const int row0 = sg[0], n = sg[1], flags = sg[3];
+  if (mode == POOL_NONE) {
+    // a wave owns a row: normed, and divided by its own L2 norm if asked
+    for (int r = g * kPoolGroup + wave; r < min(n, (g + 1) * kPoolGroup); r += 4) {
+      const float* xr = x + (size_t)(row0 + r) * ldx;
+      float* o = out + (size_t)(row0 + r) * d;
+      const float sc = pool_row_scale(xr, d, eps, lane);
+      float rn = 1.f;
+      if (normalize) {
+        float ss = 0.f;
+        for (int i = lane * 4; i < d; i += 256) {
+          const float4 v = *reinterpret_cast<const float4*>(xr + i);
+          const float4 q = *reinterpret_cast<const float4*>(w + i);
+          const float a = sc * v.x * q.x, b = sc * v.y * q.y, c = sc * v.z * q.z, e = sc * v.w * q.w;
+          ss += a * a + b * b + c * c + e * e;
+        }
+        ss = wave_sum(ss);
+        rn = ss > 0.f ? rsqrtf(ss) : 0.f;  // a zero row stays zero (upstream: norm > 0 ? 1 / norm : 0)
+      }
+      for (int i = lane * 4; i < d; i += 256) {
+        const float4 v = *reinterpret_cast<const float4*>(xr + i);
+        const float4 q = *reinterpret_cast<const float4*>(w + i);
+        *reinterpret_cast<float4*>(o + i) =
+            make_float4(sc * v.x * q.x * rn, sc * v.y * q.y * rn, sc * v.z * q.z * rn, sc * v.w * q.w * rn);
+      }
+    }
+    return;
+  }
+  int r0, nr;  // the block's rows of the segment
+  if (mode == POOL_MEAN) {
+    r0 = g * kPoolGroup;
+    nr = min(kPoolGroup, n - r0);
+  } else {  // the input's first / last row, when this piece holds it
+    if (!(flags & (mode == POOL_CLS ? kPoolFirst : kPoolLast))) return;
+    r0 = mode == POOL_CLS ? 0 : n - 1;
+    nr = 1;
+  }
+  const float* xg = x + (size_t)(row0 + r0) * ldx;
+  for (int r = wave; r < nr; r += 4) {  // rows round-robin over the waves
+    const float sc = pool_row_scale(xg + (size_t)r * ldx, d, eps, lane);
+    if (lane == 0) scale[r] = sc;
+  }
+  __syncthreads();
+  // partial row of the group: a segment's groups come first to last, the segments in table order
+  int prow = g;
+  for (int j = 0; j < k; ++j)
+    prow += mode == POOL_MEAN ? (segs[j * kPoolSegInts + 1] + kPoolGroup - 1) / kPoolGroup : 1;
+  float* p = part + (size_t)prow * d;
+  for (int i = tid * 4; i < d; i += 1024) {  // a thread owns its columns; rows added in row order
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int r = 0; r < nr; ++r) {
+      const float4 v = *reinterpret_cast<const float4*>(xg + (size_t)r * ldx + i);
+      const float sc = scale[r];
+      a.x += sc * v.x; a.y += sc * v.y; a.z += sc * v.z; a.w += sc * v.w;
+    }
+    const float4 q = *reinterpret_cast<const float4*>(w + i);
+    *reinterpret_cast<float4*>(p + i) = make_float4(a.x * q.x, a.y * q.y, a.z * q.z, a.w * q.w);
+  }
+}
+
+__global__ __launch_bounds__(256) void pool_finish_kernel(int d, int mode, int normalize, const int* segs, int n_segs,
+                                                          const float* part, float* acc, float* out) {
+  __shared__ float red[4];
+  const int input = blockIdx.x, tid = threadIdx.x;
+  // the input's segment of this launch (at most one: pool_part_rows checks) and its partial rows
+  int k = -1, prow = 0;
+  for (int j = 0; j < n_segs; ++j) {
+    if (segs[j * kPoolSegInts + 2] == input) {
+      k = j;
+      break;
+    }
+    prow += mode == POOL_MEAN ? (segs[j * kPoolSegInts + 1] + kPoolGroup - 1) / kPoolGroup : 1;
+  }
+  if (k < 0) return;  // block-uniform: no piece of this input here, its rows stay
+  const int* sg = segs + k * kPoolSegInts;
+  const int n = sg[1], flags = sg[3], n_tokens = sg[4];
+  int ng = (n + kPoolGroup - 1) / kPoolGroup;
+  if (mode != POOL_MEAN) ng = (flags & (mode == POOL_CLS ? kPoolFirst : kPoolLast)) ? 1 : 0;
+  const bool first = flags & kPoolFirst, last = flags & kPoolLast;
+  const float inv_n = mode == POOL_MEAN ? 1.f / (float)n_tokens : 1.f;
+  float* ar = acc + (size_t)input * d;
+  float ss = 0.f;
+  for (int i = tid * 4; i < d; i += 1024) {
+    float4 a = first ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(ar + i);
+    for (int j = 0; j < ng; ++j) {  // group order
+      const float4 v = *reinterpret_cast<const float4*>(part + (size_t)(prow + j) * d + i);
+      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    }
+    *reinterpret_cast<float4*>(ar + i) = a;
+    a.x *= inv_n; a.y *= inv_n; a.z *= inv_n; a.w *= inv_n;
+    ss += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+  }
+  if (!last) return;
+  float rn = 1.f;
+  if (normalize) {  // a zero vector stays zero (upstream: norm > 0 ? 1 / norm : 0)
+    ss = pool_block_sum(ss, red);
+    rn = ss > 0.f ? rsqrtf(ss) : 0.f;
+  }
+  for (int i = tid * 4; i < d; i += 1024) {  // (each thread re-reads the accumulator columns it wrote)
+    const float4 a = *reinterpret_cast<const float4*>(ar + i);
+    *reinterpret_cast<float4*>(out + (size_t)input * d + i) =
+        make_float4(a.x * inv_n * rn, a.y * inv_n * rn, a.z * inv_n * rn, a.w * inv_n * rn);
+  }
+}
+
+int pool_part_rows(const PoolArgs& a) {
+  if (a.mode < POOL_NONE || a.mode > POOL_LAST) throw std::runtime_error("pool: unknown pooling mode");
+  if (a.d < 4 || a.d % 4 || a.d > kPoolMaxD) throw std::runtime_error("pool: d must be a multiple of 4 up to 16384");
+  if (a.ldx < a.d || a.ldx % 4) throw std::runtime_error("pool: ldx must be a multiple of 4, at least d");
+  if (!a.x || !a.w || !a.segs || !a.h_segs || a.n_segs < 1) throw std::runtime_error("pool: missing arguments");
+  if (reinterpret_cast<uintptr_t>(a.x) % 16 || reinterpret_cast<uintptr_t>(a.w) % 16 ||
+      reinterpret_cast<uintptr_t>(a.part) % 16 || reinterpret_cast<uintptr_t>(a.acc) % 16 ||
+      reinterpret_cast<uintptr_t>(a.out) % 16)
+    throw std::runtime_error("pool: buffers must be 16-byte aligned");
+  if (!a.out || (a.mode != POOL_NONE && (!a.part || !a.acc))) throw std::runtime_error("pool: missing buffers");
+  int need = 0;
+  for (int k = 0; k < a.n_segs; ++k) {
+    const int* g = a.h_segs + k * kPoolSegInts;
+    if (g[0] < 0 || g[1] < 1 || (long long)g[0] + g[1] > a.rows) throw std::runtime_error("pool: segment outside the rows");
+    if (a.mode != POOL_NONE && (g[2] < 0 || g[2] >= a.n_inputs)) throw std::runtime_error("pool: input index out of range");
+    if (g[3] & ~(kPoolFirst | kPoolLast)) throw std::runtime_error("pool: unknown segment flags");
+    if (g[4] < g[1]) throw std::runtime_error("pool: a segment longer than its input");
+    for (int j = 0; j < k; ++j)
+      if (a.h_segs[j * kPoolSegInts + 2] == g[2]) throw std::runtime_error("pool: one segment per input and launch");
+    need += a.mode == POOL_MEAN ? (g[1] + kPoolGroup - 1) / kPoolGroup : a.mode == POOL_NONE ? 0 : 1;
+  }
+  if (need > a.part_rows) throw std::runtime_error("pool: partial buffer too small");
+  return need;
+}
+
+void pool_rows(const PoolArgs& a, hipStream_t s) {
+  (void)pool_part_rows(a);
+  int blocks = 0;
+  for (int k = 0; k < a.n_segs; ++k) {
+    const int n = a.h_segs[k * kPoolSegInts + 1];
+    blocks += a.mode == POOL_CLS || a.mode == POOL_LAST ? 1 : (n + kPoolGroup - 1) / kPoolGroup;
+  }
+  hipLaunchKernelGGL(pool_rows_kernel, dim3(blocks), dim3(256), 0, s, a.x, a.ldx, a.w, a.eps, a.d, a.mode,
+                     (int)a.normalize, a.segs, a.n_segs, a.part, a.out);
+}
+
+void pool_finish(const PoolArgs& a, hipStream_t s) {
+  (void)pool_part_rows(a);
+  if (a.mode == POOL_NONE) return;  // pool_rows wrote the rows
+  hipLaunchKernelGGL(pool_finish_kernel, dim3(a.n_inputs), dim3(256), 0, s, a.d, a.mode, (int)a.normalize, a.segs,
+                     a.n_segs, a.part, a.acc, a.out);
+}
+
 // ---------------------------------------------------------------- synthetic weights on device
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
   z += 0x9E3779B97F4A7C15ull;

@@ -461,6 +461,17 @@ void Engine::alloc_buffers() {
   }
   HIPCHK(hipHostMalloc((void**)&h_ring_, sizeof(int) * 64, hipHostMallocDefault));
   HIPCHK(hipHostMalloc((void**)&h_tokens_, sizeof(int) * B, hipHostMallocDefault));
+  // embedding epilogue (embed): a chunk of B rows holds at most one piece per slot, so at most
+  // B / 64 + pieces groups of 64 rows
+  if (!tp_on_ && has_head() && opt_.layer_begin == 0) {
+    const int NI = std::max(NS, 1);
+    pool_part_rows_ = B / kPoolGroup + NI;
+    pool_part_ = (float*)dalloc(sizeof(float) * pool_part_rows_ * d);
+    pool_acc_ = (float*)dalloc(sizeof(float) * NI * d);
+    pool_out_ = (float*)dalloc(sizeof(float) * NI * d);
+    pool_segs_ = (int*)dalloc(sizeof(int) * NI * kPoolSegInts);
+    HIPCHK(hipHostMalloc((void**)&h_pool_segs_, sizeof(int) * NI * kPoolSegInts, hipHostMallocDefault));
+  }
 }
 
 void Engine::setup_batch_mfma() {
@@ -1877,18 +1888,17 @@ std::vector<int> Engine::slots_begin(const std::vector<int>& slots, const std::v
   return slots_begin_impl(slots, prompts, keep, sps);
 }
 
-std::vector<int> Engine::slots_begin_impl(const std::vector<int>& slots, const std::vector<std::vector<int>>& prompts,
-                                          const std::vector<int>& n_keep, const std::vector<SamplingOpts>& sps) {
+void Engine::packed_prefill(const std::vector<int>& slots, const std::vector<std::vector<int>>& prompts,
+                            const std::vector<int>& n_keep,
+                            const std::function<void(const std::vector<PrefillSeg>&)>& after_chunk) {
   const size_t n = slots.size();
-  for (size_t i = 0; i < n; ++i) begin_slot_state(slots[i], prompts[i], sps[i]);
-  const int NB = nb_cap_, d = hp_.n_embd;
+  const int NB = nb_cap_;
   int* h_tok = h_rmeta_;
   int* h_pos = h_rmeta_ + NB;
   int* h_slot = h_rmeta_ + 2 * NB;
   std::vector<PrefillSeg> segs;
   int rows = 0;
-  // one packed chunk: tokens / positions / slots up, every layer over its rows, then the
-  // logits row of each prompt that ends in it (sampled into that slot's state)
+  // one packed chunk: tokens / positions / slots up, every layer over its rows, then the caller's part
   auto flush = [&]() {
     if (!rows) return;
     HIPCHK(hipMemcpyAsync(tokens_, h_tok, sizeof(int) * rows, hipMemcpyHostToDevice, stream_));
@@ -1902,11 +1912,7 @@ std::vector<int> Engine::slots_begin_impl(const std::vector<int>& slots, const s
       throw;
     }
     segs_ = nullptr;
-    for (const PrefillSeg& g : segs)
-      if (g.last) {
-        enqueue_head(x_ + (size_t)(g.row + g.n - 1) * d, 0, stream_, g.slot);
-        if (h_nprobs_[g.slot] > 0) enqueue_logprobs(logits_, 0, 0, g.slot, lp_off_first(g.slot), stream_);
-      }
+    after_chunk(segs);
     HIPCHK(hipStreamSynchronize(stream_));  // the pinned row metadata is rewritten next
     segs.clear();
     rows = 0;
@@ -1929,6 +1935,90 @@ std::vector<int> Engine::slots_begin_impl(const std::vector<int>& slots, const s
     }
   }
   flush();
+}
+
+std::vector<std::vector<float>> Engine::embed(const std::vector<int>& slots,
+                                              const std::vector<std::vector<int>>& inputs, int pooling,
+                                              bool normalize) {
+  if (tp_on_) throw std::runtime_error("embed: tensor-parallel engines compute no embeddings");
+  if (!has_head() || opt_.layer_begin > 0) throw std::runtime_error("embed: this engine holds only a part of the layers");
+  ExecGuard guard(this);
+  const size_t n = slots.size();
+  if (pooling < POOL_NONE || pooling > POOL_LAST) throw std::runtime_error("embed: unknown pooling type");
+  if (n < 1 || (int)n > opt_.n_slots || inputs.size() != n) throw std::runtime_error("embed: 1 <= inputs <= n_slots");
+  if (!bmax_ && n != 1) throw std::runtime_error("embed: an engine with one KV slot takes one input");
+  std::vector<int> input_of(opt_.n_slots, -1);
+  for (size_t i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= opt_.n_slots) throw std::runtime_error("embed: slot out of range");
+    if (input_of[slots[i]] >= 0) throw std::runtime_error("embed: duplicate slot");
+    input_of[slots[i]] = (int)i;
+    if (inputs[i].empty()) throw std::runtime_error("embed: empty input");
+    if ((int)inputs[i].size() > opt_.n_ctx) throw std::runtime_error("embed: input exceeds context window");
+  }
+  const int d = hp_.n_embd;
+  std::vector<std::vector<float>> out(n);
+  for (size_t i = 0; i < n; ++i) out[i].resize(pooling == POOL_NONE ? inputs[i].size() * (size_t)d : (size_t)d);
+  PoolArgs a;
+  a.x = x_; a.rows = nb_cap_; a.ldx = d; a.w = out_norm_; a.eps = hp_.rms_eps; a.d = d;
+  a.mode = pooling; a.normalize = normalize; a.segs = pool_segs_; a.h_segs = h_pool_segs_;
+  a.part = pool_part_; a.part_rows = pool_part_rows_; a.acc = pool_acc_;
+  a.out = pooling == POOL_NONE ? tmp_ : pool_out_;  // none: the chunk's rows, read back chunk by chunk
+  a.n_inputs = std::max(opt_.n_slots, 1);
+  // the epilogue of one chunk, on its residual rows
+  auto pool_chunk = [&](const std::vector<PrefillSeg>& segs) {
+    a.n_segs = (int)segs.size();
+    for (size_t k = 0; k < segs.size(); ++k) {
+      const PrefillSeg& g = segs[k];
+      int* h = h_pool_segs_ + k * kPoolSegInts;
+      h[0] = g.row; h[1] = g.n; h[2] = input_of[g.slot];
+      h[3] = (g.pos == 0 ? kPoolFirst : 0) | (g.last ? kPoolLast : 0);
+      h[4] = (int)inputs[input_of[g.slot]].size();
+    }
+    (void)pool_part_rows(a);  // every bound, before anything is queued
+    HIPCHK(hipMemcpyAsync(pool_segs_, h_pool_segs_, sizeof(int) * kPoolSegInts * segs.size(), hipMemcpyHostToDevice,
+                          stream_));
+    pool_rows(a, stream_);
+    pool_finish(a, stream_);
+    if (pooling == POOL_NONE)
+      for (const PrefillSeg& g : segs)
+        HIPCHK(hipMemcpyAsync(out[input_of[g.slot]].data() + (size_t)g.pos * d, tmp_ + (size_t)g.row * d,
+                              sizeof(float) * g.n * d, hipMemcpyDeviceToHost, stream_));
+  };
+  if (bmax_) {
+    packed_prefill(slots, inputs, std::vector<int>(n, 0), pool_chunk);
+  } else {
+    const std::vector<int>& in = inputs[0];
+    const int np = (int)in.size();
+    for (int pos = 0; pos < np;) {
+      const int T = std::min(opt_.n_batch, np - pos);
+      prefill_chunk(slots[0], in.data() + pos, T, pos, /*head=*/false);
+      pool_chunk({PrefillSeg{0, T, slots[0], pos, pos + T == np}});
+      HIPCHK(hipStreamSynchronize(stream_));  // the pinned segment table is rewritten next
+      pos += T;
+    }
+  }
+  if (pooling != POOL_NONE) {
+    std::vector<float> host(n * (size_t)d);
+    HIPCHK(hipMemcpy(host.data(), pool_out_, sizeof(float) * host.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) std::copy(host.begin() + i * d, host.begin() + (i + 1) * d, out[i].begin());
+  }
+  check_device_err();
+  return out;
+}
+
+std::vector<int> Engine::slots_begin_impl(const std::vector<int>& slots, const std::vector<std::vector<int>>& prompts,
+                                          const std::vector<int>& n_keep, const std::vector<SamplingOpts>& sps) {
+  const size_t n = slots.size();
+  for (size_t i = 0; i < n; ++i) begin_slot_state(slots[i], prompts[i], sps[i]);
+  const int d = hp_.n_embd;
+  // the logits row of each prompt that ends in the chunk (sampled into that slot's state)
+  packed_prefill(slots, prompts, n_keep, [&](const std::vector<PrefillSeg>& segs) {
+    for (const PrefillSeg& g : segs)
+      if (g.last) {
+        enqueue_head(x_ + (size_t)(g.row + g.n - 1) * d, 0, stream_, g.slot);
+        if (h_nprobs_[g.slot] > 0) enqueue_logprobs(logits_, 0, 0, g.slot, lp_off_first(g.slot), stream_);
+      }
+  });
   std::vector<int> out(n);
   for (size_t i = 0; i < n; ++i)
     HIPCHK(hipMemcpy(&out[i], state_ + (size_t)S_NSTATE * slots[i] + S_TOKEN, sizeof(int), hipMemcpyDeviceToHost));

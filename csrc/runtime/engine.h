@@ -245,6 +245,21 @@ class Engine : public SlotBackend {
   // it asks (SamplingOpts::n_probs), outside the captured graphs, and reads the records back with
   // the step's tokens. logprob_launches counts those queued pairs (0 while nobody asks).
   std::vector<LogprobEntry> step_logprobs() override;
+  // Text embeddings: input i is prefilled into KV slot slots[i] from position 0 (distinct slots,
+  // 1 <= n <= n_slots; an input may fill the whole context, nothing is generated after it) - a
+  // batching engine packs the inputs into shared chunks exactly as slots_begin does, an engine with
+  // one KV slot takes one input chunk by chunk - with no lm_head and no sampler: each chunk ends in
+  // the pooling epilogue on its residual rows (kernels.h PoolArgs: output RMSNorm, pooling per input,
+  // optional L2 norm). Returns one vector of n_embd floats per input, or for pooling none (0) the
+  // input's rows [n_tokens][n_embd] flattened. OVERWRITES the KV of those slots: whatever prefix they
+  // held is gone. Touches no sampling state, no other slot. One rank, all layers.
+  std::vector<std::vector<float>> embed(const std::vector<int>& slots, const std::vector<std::vector<int>>& inputs,
+                                        int pooling, bool normalize);
+  std::vector<std::vector<float>> embed_begin(const std::vector<int>& slots,
+                                              const std::vector<std::vector<int>>& inputs, int pooling,
+                                              bool normalize) override {
+    return embed(slots, inputs, pooling, normalize);
+  }
   long long logprob_launches() const { return lp_launches_.load(); }
   // inspection hook (tests): single-row decode layers enqueued as the one attention + Wo launch
   // (attn_wo1) so far - per step when eager, per capture under a graph; 0 with LFK_WO_FUSE=0
@@ -318,6 +333,19 @@ class Engine : public SlotBackend {
     bool last;
   };
   const std::vector<PrefillSeg>* segs_ = nullptr;  // set while a packed chunk is enqueued
+  // the packing loop of a joint admission (slots_begin) and of embed: prompts[i][n_keep[i]:] into
+  // shared chunks of up to nb_cap_ rows, every layer over each chunk; after_chunk queues what the
+  // caller wants of the chunk's residual rows x_ (the stream is synchronised after it)
+  void packed_prefill(const std::vector<int>& slots, const std::vector<std::vector<int>>& prompts,
+                      const std::vector<int>& n_keep,
+                      const std::function<void(const std::vector<PrefillSeg>&)>& after_chunk);
+  // embedding epilogue (alloc_buffers; null on engines that cannot embed)
+  float* pool_part_ = nullptr;   // [pool_part_rows_][d] partial rows of one chunk
+  float* pool_acc_ = nullptr;    // [max(n_slots, 1)][d] per-input sums, carried over the chunks of a call
+  float* pool_out_ = nullptr;    // [max(n_slots, 1)][d]
+  int* pool_segs_ = nullptr;     // [max(n_slots, 1)][kPoolSegInts] the chunk's segment table
+  int* h_pool_segs_ = nullptr;   // pinned copy
+  int pool_part_rows_ = 0;
   int* rpos_ = nullptr;     // [n_batch] per-row position of a packed chunk
   int* rslots_ = nullptr;   // [n_batch] per-row KV slot
   int* h_rmeta_ = nullptr;  // pinned [3][n_batch]: tokens | positions | slots

@@ -242,6 +242,7 @@ HParams read_hparams(const GGUFFile& f) {
   h.n_ctx_train = gi("context_length", 2048);
   h.rope_base = (float)f.get_float(arch + ".rope.freq_base", 10000.0);
   h.rms_eps = (float)f.get_float(arch + ".attention.layer_norm_rms_epsilon", 1e-5);
+  h.pooling_type = f.has(arch + ".pooling_type") ? (int)f.get_int(arch + ".pooling_type", -1) : -1;
   const GGUFTensor* emb = f.find("token_embd.weight");
   if (!emb) throw std::runtime_error("missing token_embd.weight");
   h.n_vocab = (int)emb->ne[1];

@@ -84,6 +84,8 @@ struct HParams {
   // head after the projection and before RoPE. The loaders permute these weights with the map of
   // the q / k rows (neox_src_row), which leaves a head's mean square as it was
   bool qk_norm = false;
+  // {arch}.pooling_type (embedding models: 0 none, 1 mean, 2 cls, 3 last, 4 rank); -1: the key is absent
+  int pooling_type = -1;
 };
 HParams read_hparams(const GGUFFile& f);
 

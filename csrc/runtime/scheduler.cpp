@@ -82,9 +82,64 @@ SchedPoll BatchScheduler::wait(int64_t id, size_t have, int timeout_ms) {
   return p;
 }
 
+int64_t BatchScheduler::submit_embed(const std::vector<std::vector<int>>& inputs, int pooling, bool normalize) {
+  if (inputs.empty()) throw std::runtime_error("embed: no inputs");
+  if (pooling < 0 || pooling > 3) throw std::runtime_error("embed: unknown pooling type");
+  for (const auto& in : inputs) {
+    if (in.empty()) throw std::runtime_error("embed: empty input");
+    if ((int)in.size() > eng_.n_ctx()) throw std::runtime_error("embed: input exceeds context window");
+  }
+  auto j = std::make_shared<EmbedJob>();
+  j->inputs = inputs;
+  j->pooling = pooling;
+  j->normalize = normalize;
+  {
+    std::lock_guard<std::mutex> g(mu_);
+    if (stop_) throw std::runtime_error("BatchScheduler: shut down");
+    j->id = next_id_++;
+    embeds_[j->id] = j;
+    embed_q_.push_back(j);
+  }
+  cv_work_.notify_one();
+  return j->id;
+}
+
+SchedEmbedPoll BatchScheduler::wait_embed(int64_t id, int timeout_ms) {
+  std::unique_lock<std::mutex> lk(mu_);
+  auto it = embeds_.find(id);
+  if (it == embeds_.end()) throw std::runtime_error("BatchScheduler: unknown embedding job");
+  std::shared_ptr<EmbedJob> j = it->second;
+  cv_out_.wait_for(lk, std::chrono::milliseconds(std::max(0, timeout_ms)), [&] { return j->done; });
+  SchedEmbedPoll p;
+  p.done = j->done;
+  p.finish = j->finish;
+  p.error = j->error;
+  if (j->done && j->finish == "done") p.vectors = j->vectors;
+  return p;
+}
+
+// caller holds mu_
+void BatchScheduler::finish_embed(EmbedJob& j, const char* reason) {
+  if (j.done) return;
+  j.done = true;
+  j.finish = reason;
+  for (auto it = embed_q_.begin(); it != embed_q_.end(); ++it)
+    if (it->get() == &j) {
+      embed_q_.erase(it);
+      break;
+    }
+  cv_out_.notify_all();
+}
+
 void BatchScheduler::cancel(int64_t id) {
   {
     std::lock_guard<std::mutex> g(mu_);
+    auto ej = embeds_.find(id);
+    if (ej != embeds_.end()) {
+      if (!ej->second->done) ej->second->cancel = true;
+      cv_work_.notify_one();
+      return;
+    }
     auto it = reqs_.find(id);
     if (it == reqs_.end() || it->second->done) return;
     it->second->cancel = true;
@@ -95,6 +150,13 @@ void BatchScheduler::cancel(int64_t id) {
 void BatchScheduler::release(int64_t id) {
   {
     std::lock_guard<std::mutex> g(mu_);
+    auto ej = embeds_.find(id);
+    if (ej != embeds_.end()) {
+      ej->second->cancel = true;  // an abandoned job runs no further pass
+      embeds_.erase(ej);
+      cv_work_.notify_one();
+      return;
+    }
     auto it = reqs_.find(id);
     if (it == reqs_.end()) return;
     it->second->cancel = true;  // an abandoned active row leaves the batch at the next step
@@ -165,7 +227,7 @@ void BatchScheduler::loop() {
   std::deque<std::shared_ptr<Req>> prefilling;  // chunked admissions in progress, oldest first
   while (true) {
     cv_work_.wait(lk, [&] {
-      if (stop_ || !pending_.empty() || !flights.empty()) return true;
+      if (stop_ || !pending_.empty() || !flights.empty() || !embed_q_.empty()) return true;
       for (int s = first_slot_; s < n_slots_; ++s)
         if (slot_req_[s]) return true;
       return false;
@@ -189,6 +251,7 @@ void BatchScheduler::loop() {
           finish(*r, "cancelled");
           continue;
         }
+        if (!embed_q_.empty() && embed_q_.front()->id < r->id) break;  // an older embedding job goes first
         int lcp = 0;
         const int slot = pick_slot(r->prompt, &lcp);
         if (slot < 0) break;
@@ -250,6 +313,63 @@ void BatchScheduler::loop() {
         }
         if (adm.size() > 1) ++st_.joint_admissions;
         cv_out_.notify_all();  // the first tokens reach their waiters now, not after the next step
+      }
+    }
+    // 2a. one pass of the oldest embedding job, unless an older request still waits for a slot: as
+    //     many whole inputs as there are free slots (no request, in no queued step), at most
+    //     prefill_part_tokens() rows while a row decodes - the bound a chunked admission's part
+    //     puts on a decode stall - and always at least one input
+    while (!embed_q_.empty() && embed_q_.front()->cancel) finish_embed(*embed_q_.front(), "cancelled");
+    if (!embed_q_.empty() && (pending_.empty() || embed_q_.front()->id < pending_.front()->id)) {
+      std::shared_ptr<EmbedJob> j = embed_q_.front();
+      bool decoding = false;
+      for (int s = first_slot_; s < n_slots_; ++s) decoding = decoding || (slot_req_[s] && slot_req_[s]->n_done < 0);
+      const int cap = decoding ? eng_.prefill_part_tokens() : 0;
+      std::vector<int> e_slots;
+      std::vector<std::vector<int>> e_in;
+      long long rows_in = 0;
+      for (int s = first_slot_; s < n_slots_ && j->next + e_in.size() < j->inputs.size(); ++s) {
+        bool busy = slot_req_[s] != nullptr;
+        for (const Flight& f : flights) busy = busy || std::find(f.rows.begin(), f.rows.end(), s) != f.rows.end();
+        if (busy) continue;
+        const std::vector<int>& in = j->inputs[j->next + e_in.size()];
+        if (cap > 0 && !e_in.empty() && rows_in + (long long)in.size() > cap) break;
+        rows_in += (long long)in.size();
+        e_slots.push_back(s);
+        e_in.push_back(in);
+      }
+      if (!e_in.empty()) {
+        const int pooling = j->pooling;
+        const bool normalize = j->normalize;
+        std::string err;
+        std::vector<std::vector<float>> vecs;
+        lk.unlock();
+        try {
+          vecs = eng_.embed_begin(e_slots, e_in, pooling, normalize);
+          if (vecs.size() != e_in.size()) throw std::runtime_error("embed_begin: one vector per input");
+        } catch (const std::exception& e) {
+          err = e.what();
+        }
+        lk.lock();
+        for (int s : e_slots) {  // the pass overwrote the slot's KV: its resident prefix is gone
+          slot_hist_[s].clear();
+          slot_used_[s] = ++tick_;
+        }
+        if (!err.empty()) {
+          j->error = err;
+          finish_embed(*j, "error");
+        } else {
+          st_.embed_inputs += (long long)e_in.size();
+          st_.embed_tokens += rows_in;
+          for (auto& v : vecs) j->vectors.push_back(std::move(v));
+          j->next += e_in.size();
+          if (j->cancel && j->next < j->inputs.size()) {
+            finish_embed(*j, "cancelled");
+          } else if (j->next == j->inputs.size()) {
+            ++st_.embed_jobs;
+            finish_embed(*j, "done");
+          }
+        }
       }
     }
     // 2b. one part of the oldest chunked admission (a part is one prefill pass; the rows
@@ -336,7 +456,7 @@ void BatchScheduler::loop() {
           std::lock_guard<std::mutex> g(mu_);
           bool free_slot = false;
           for (int s = first_slot_; s < n_slots_ && !free_slot; ++s) free_slot = !slot_req_[s];
-          more = (pending_.empty() || !free_slot) && !stop_;
+          more = ((pending_.empty() && embed_q_.empty()) || !free_slot) && !stop_;
           for (size_t b = 0; more && b < row_req.size(); ++b) {
             const Req& r = *row_req[b];
             more = !r.done && !r.cancel && (int)(r.prompt.size() + r.tokens.size()) < eng_.n_ctx();
@@ -398,6 +518,7 @@ void BatchScheduler::loop() {
   // shutdown: nothing runs any more
   for (auto& r : pending_) finish(*r, "cancelled");
   pending_.clear();
+  while (!embed_q_.empty()) finish_embed(*embed_q_.front(), "cancelled");
   for (int s = first_slot_; s < n_slots_; ++s)
     if (slot_req_[s]) finish(*slot_req_[s], "cancelled");
   cv_out_.notify_all();

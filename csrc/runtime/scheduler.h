@@ -53,7 +53,17 @@ struct SchedStats {
   long long reused_tokens = 0;  // prompt tokens served from a slot's resident KV prefix
   long long joint_admissions = 0;  // admissions that prefilled several prompts in one pass
   long long chunked_admissions = 0;  // prompts prefilled in parts between decode steps
+  long long embed_jobs = 0;      // embedding jobs completed
+  long long embed_inputs = 0;    // their inputs, as embed_begin passes took them
+  long long embed_tokens = 0;    // ... and those inputs' tokens
   int active = 0, pending = 0, slots = 0;
+};
+
+struct SchedEmbedPoll {
+  bool done = false;
+  std::vector<std::vector<float>> vectors;  // one per input once done without error
+  std::string finish;                       // "done" | "cancelled" | "error"
+  std::string error;
 };
 
 class BatchScheduler {
@@ -70,6 +80,14 @@ class BatchScheduler {
   // Tokens of request `id` past the first `have`; blocks up to timeout_ms until there is at
   // least one new token or the request is done.
   SchedPoll wait(int64_t id, size_t have, int timeout_ms);
+  // Text embeddings: queue a job of several inputs (SlotBackend::embed_begin's pooling / normalize).
+  // Jobs and generation requests keep their arrival order: a free slot goes to whichever waiting
+  // item is older. A job borrows free slots for one embed_begin pass per loop iteration - as many
+  // whole inputs as there are free slots, capped at prefill_part_tokens() rows while any row decodes
+  // (always at least one input) - and continues in later iterations; the slots are free again right
+  // after a pass, their resident prefix gone. Ids share the requests' id space (cancel / release).
+  int64_t submit_embed(const std::vector<std::vector<int>>& inputs, int pooling, bool normalize);
+  SchedEmbedPoll wait_embed(int64_t id, int timeout_ms);
   void cancel(int64_t id);    // cooperative: the row leaves the batch before the next step
   void release(int64_t id);   // forget a finished (or abandoned: cancels it) request
   SchedStats stats();
@@ -92,6 +110,17 @@ class BatchScheduler {
     std::string finish, error;
     double t_submit = 0, t_start = 0, t_first = 0, t_done = 0;
   };
+  struct EmbedJob {
+    int64_t id = 0;
+    std::vector<std::vector<int>> inputs;
+    int pooling = 0;
+    bool normalize = false;
+    size_t next = 0;  // inputs [0, next) are done
+    std::vector<std::vector<float>> vectors;
+    bool cancel = false, done = false;
+    std::string finish, error;
+  };
+  void finish_embed(EmbedJob& j, const char* reason);
   void loop();
   void finish(Req& r, const char* reason);
   // append one sampled token (and, for a request that asked, its entry of the engine's
@@ -106,6 +135,8 @@ class BatchScheduler {
   std::condition_variable cv_work_, cv_out_;
   std::deque<std::shared_ptr<Req>> pending_;
   std::map<int64_t, std::shared_ptr<Req>> reqs_;
+  std::deque<std::shared_ptr<EmbedJob>> embed_q_;       // unfinished embedding jobs, oldest first
+  std::map<int64_t, std::shared_ptr<EmbedJob>> embeds_;
   std::vector<std::shared_ptr<Req>> slot_req_;   // active request per slot (null = free)
   std::vector<std::vector<int>> slot_hist_;      // tokens resident in each slot's KV
   std::vector<long long> slot_used_;             // last admission tick (LRU among equal prefixes)

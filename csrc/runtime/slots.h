@@ -3,6 +3,7 @@
 // scheduler through a deterministic CPU stand-in (bindings_cpu.cpp) so its admission,
 // prefix-reuse and retirement logic is checked without a GPU.
 #pragma once
+#include <stdexcept>
 #include <utility>
 #include <vector>
 
@@ -69,6 +70,15 @@ class SlotBackend {
   // entry with an empty `top` for a slot that did not ask). None at all: no slot asked, or the
   // backend computes none.
   virtual std::vector<LogprobEntry> step_logprobs() { return {}; }
+  // Text embeddings (optional): prefill input i into slots[i] from position 0 and return its pooled
+  // vector (pooling 0 none: its rows, flattened; 1 mean, 2 cls, 3 last), L2-normalised if asked.
+  // No sampling state is touched; the slots' KV is overwritten. An input may be n_ctx tokens long.
+  virtual std::vector<std::vector<float>> embed_begin(const std::vector<int>& slots,
+                                                      const std::vector<std::vector<int>>& inputs, int pooling,
+                                                      bool normalize) {
+    (void)slots; (void)inputs; (void)pooling; (void)normalize;
+    throw std::runtime_error("embeddings are not supported by this backend");
+  }
 };
 
 }  // namespace lfk

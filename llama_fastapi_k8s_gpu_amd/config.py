@@ -72,6 +72,8 @@ class Settings:
     # continuous batching (MI355X engine, one rank): up to max_batch generations decode
     # together as rows of one batched step. 1 = the reference's one-at-a-time serving.
     max_batch: int = 1
+    # POST /v1/embeddings: auto (the model's own pooling_type; mean where it has none) | mean | last | cls
+    embedding_pooling: str = "auto"
     # tensor parallelism (split_mode=row over torchrun ranks): the engine's collectives -
     # "auto" (one-shot P2P kernel for decode, RCCL for prefill), "rccl", or "ipc" (the P2P
     # kernel only: ranks may share a GPU). tp_device puts EVERY rank on that GPU (the one-GPU
@@ -131,6 +133,9 @@ class Settings:
         s.engine = _env("ENGINE", s.engine).lower()
         s.verbose = _env("VERBOSE", s.verbose, bool)
         s.max_batch = max(1, _env("MAX_BATCH", s.max_batch, int))
+        s.embedding_pooling = _env("EMBEDDING_POOLING", s.embedding_pooling).lower()
+        if s.embedding_pooling not in ("auto", "mean", "last", "cls"):
+            raise ValueError(f"EMBEDDING_POOLING={s.embedding_pooling!r}: auto, mean, last or cls")
         s.tp_comm = _env("TP_COMM", s.tp_comm).lower()
         tpd = _env("TP_DEVICE", None)
         s.tp_device = int(tpd) if tpd is not None else None

@@ -104,6 +104,15 @@ class ReferenceBackend:
         self.model.k_cache[:, :n] = kv[0]
         self.model.v_cache[:, :n] = kv[1]
 
+    def embed(self, inputs, pooling: int, normalize: bool, cancel=None):
+        """One vector per input (pooling none: its rows): the exact fp32 model's normed final
+        rows, pooled in float64. Overwrites the KV cache from position 0."""
+        import numpy as np
+
+        from .pooling import pool_host
+        return [pool_host(self.model.hidden(list(toks)).numpy().astype(np.float64), pooling, normalize, np.float64)
+                for toks in inputs]
+
     def generate(self, prompt: Sequence[int], n_keep: int, max_new: int, params: SamplingParams,
                  stop_ids: Sequence[int], poll: Optional[Callable[[], bool]] = None,
                  on_token: Optional[Callable[[int], None]] = None) -> GenerationResult:

@@ -71,3 +71,38 @@ class FakeEngine:
         return {"id": "chatcmpl-fake", "object": "chat.completion", "created": int(time.time()),
                 "model": "fake", "choices": choices,
                 "usage": {"prompt_tokens": 0, "completion_tokens": 0, "total_tokens": 0}}
+
+    N_EMBD = 16
+
+    def create_embedding(self, input, model: Optional[str] = None, normalize: bool = True,
+                         pooling_type: Optional[int] = None,
+                         cancel_event: Optional[threading.Event] = None, **kw):
+        """Deterministic unit vectors derived from each input's text (or token ids): the same
+        input always gets the same vector, different inputs different ones."""
+        import hashlib
+        import struct
+        items = [input] if isinstance(input, str) else list(input)
+        if items and all(isinstance(t, int) for t in items):
+            items = [items]
+        with self._lock:
+            self.calls.append({"embedding_input": items, "pooling_type": pooling_type, **kw})
+        if self.mode.startswith("raise:"):
+            raise RuntimeError(self.mode.split(":", 1)[1])
+        if self.mode.startswith("sleep:"):
+            t_end = time.monotonic() + float(self.mode.split(":", 1)[1])
+            while time.monotonic() < t_end and not (cancel_event is not None and cancel_event.is_set()):
+                time.sleep(min(0.01, max(0.0, t_end - time.monotonic())))
+        data, n_tok = [], 0
+        for i, it in enumerate(items):
+            if not it:
+                raise ValueError("embed: an input has no tokens")
+            key = it.encode("utf-8") if isinstance(it, str) else repr([int(t) for t in it]).encode()
+            n_tok += len(it.split()) if isinstance(it, str) else len(it)
+            raw = b"".join(hashlib.sha256(key + bytes([k])).digest() for k in range(self.N_EMBD * 4 // 32 + 1))
+            v = [struct.unpack_from("<i", raw, 4 * k)[0] / 2.0 ** 31 for k in range(self.N_EMBD)]
+            norm = sum(x * x for x in v) ** 0.5 or 1.0
+            data.append({"object": "embedding", "embedding": [x / norm for x in v], "index": i})
+        with self._lock:
+            self.completed += 1
+        return {"object": "list", "data": data, "model": model or "fake",
+                "usage": {"prompt_tokens": n_tok, "total_tokens": n_tok}}

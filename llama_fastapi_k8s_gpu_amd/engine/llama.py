@@ -31,6 +31,7 @@ from ..models.llama import LlamaHParams
 from .backends import GenerationResult, ReferenceBackend
 from .cache import BaseLlamaCache, LlamaState, longest_token_prefix
 from .chat_format import get_formatter
+from .pooling import check_pooling, resolve_pooling
 from .sampling import SamplingParams
 from .tokenizer import tokenizer_from_metadata
 
@@ -73,7 +74,8 @@ class Llama:
                  tensor_split: Optional[Sequence[float]] = None, split_mode: str = "layer",
                  main_gpu: int = 0, seed: Optional[int] = None, chat_format: Optional[str] = None,
                  last_n_tokens_size: int = 64, use_graphs: bool = True, verbose: bool = True,
-                 backend: Optional[str] = None, n_threads: Optional[int] = None, **kwargs):
+                 backend: Optional[str] = None, n_threads: Optional[int] = None, embedding: bool = False,
+                 pooling_type: int = -1, **kwargs):
         t0 = time.perf_counter()
         if not os.path.exists(model_path):
             raise ValueError(f"Model path does not exist: {model_path}")
@@ -87,6 +89,8 @@ class Llama:
         self._n_ctx = int(n_ctx) if n_ctx else self.hparams.n_ctx_train
         self.n_batch = n_batch
         self.last_n_tokens_size = last_n_tokens_size
+        self.embedding = bool(embedding)   # accepted for upstream compatibility: embed() needs no mode switch
+        self.pooling_type = resolve_pooling(pooling_type, self.hparams.pooling_type)
         self.verbose = verbose
         self._seed = seed if seed is not None else int.from_bytes(os.urandom(4), "little")
         self._request_ids = itertools.count(1)   # per-request seed derivation (thread-safe)
@@ -447,6 +451,82 @@ class Llama:
                             "n_prefilled": res.n_prefilled}}
 
     __call__ = create_completion
+
+    # ------------------------------------------------------------ embeddings
+    def _embed_tokens(self, item, truncate: bool) -> List[int]:
+        if isinstance(item, str):
+            toks = self.tokenize(item, add_bos=True, special=True)
+            if self.tokenizer.add_eos_token and self.tokenizer.eos_id >= 0:
+                toks.append(self.tokenizer.eos_id)
+        else:
+            toks = [int(t) for t in item]
+        if not toks:
+            raise ValueError("embed: an input has no tokens")
+        bad = next((t for t in toks if not 0 <= t < self.hparams.n_vocab), None)
+        if bad is not None:
+            raise ValueError(f"embed: token id {bad} outside the vocabulary [0, {self.hparams.n_vocab})")
+        if len(toks) > self._n_ctx:
+            if not truncate:
+                raise ValueError(f"Requested tokens ({len(toks)}) exceed context window of {self._n_ctx}")
+            toks = toks[:self._n_ctx]
+        return toks
+
+    def embed(self, input: Union[str, List[str], List[int], List[List[int]]], normalize: bool = False,
+              truncate: bool = True, return_count: bool = False, pooling_type: Optional[int] = None,
+              cancel_event: Optional[threading.Event] = None):
+        """Text embeddings (``llama_cpp.Llama.embed``): every token's residual row after the last
+        layer through the output RMSNorm, pooled per input by ``pooling_type`` (mean, cls = first
+        row, last; none returns every row). Attention stays causal. ``input``: a string, a list of
+        strings, a list of token ids (one input) or a list of such lists; strings are tokenised with
+        BOS (and EOS when ``tokenizer.ggml.add_eos_token`` says so). An input may fill the whole
+        context (nothing is generated after it); ``truncate`` cuts longer ones to ``n_ctx`` tokens,
+        otherwise they raise ``ValueError``. Returns one list of ``n_embd`` floats per input (none: a
+        list of rows per input), a single result for a single string; ``normalize`` divides each
+        returned vector by its L2 norm; ``return_count`` adds the total token count.
+
+        Deliberately unlike upstream, this works whether or not ``embedding=True`` was passed: the
+        engine needs no mode switch. ``pooling_type`` (an extension) overrides the pooling the
+        constructor resolved, for this call. The backend's KV cache is overwritten."""
+        pooling = check_pooling(self.pooling_type if pooling_type is None else pooling_type)
+        single = isinstance(input, str)
+        if single:
+            items = [input]
+        else:
+            items = list(input)
+            if not items:
+                raise ValueError("embed: no input")
+            if all(isinstance(t, (int, np.integer)) for t in items):
+                items = [items]   # a list of token ids is one input
+        inputs = [self._embed_tokens(it, truncate) for it in items]
+        emb = getattr(self._backend, "embed", None)
+        if emb is None:
+            raise NotImplementedError(f"embeddings are not supported on the {self.backend_name} backend")
+        if getattr(self._backend, "sched", None) is not None:
+            vecs = emb(inputs, pooling, bool(normalize), cancel=cancel_event)   # borrows free slots of the batch
+        else:
+            with self._lock:
+                try:
+                    vecs = emb(inputs, pooling, bool(normalize), cancel=cancel_event)
+                finally:
+                    self._kv_tokens = []   # the pass overwrote the KV cache: no prefix to reuse
+        out = [np.asarray(v, np.float32).tolist() for v in vecs]
+        result = out[0] if single else out
+        return (result, sum(len(t) for t in inputs)) if return_count else result
+
+    def create_embedding(self, input: Union[str, List[str], List[int], List[List[int]]], model: Optional[str] = None,
+                         normalize: bool = False, pooling_type: Optional[int] = None,
+                         cancel_event: Optional[threading.Event] = None) -> Dict[str, Any]:
+        """The OpenAI embeddings response (``llama_cpp.Llama.create_embedding``) of ``embed``.
+        Upstream's signature is ``(input, model)``; ``normalize``, ``pooling_type`` and
+        ``cancel_event`` are extensions handed on to ``embed`` (``POST /v1/embeddings`` uses them)."""
+        result, n = self.embed(input, normalize=normalize, return_count=True, pooling_type=pooling_type,
+                               cancel_event=cancel_event)
+        if isinstance(input, str):
+            result = [result]
+        return {"object": "list",
+                "data": [{"object": "embedding", "embedding": e, "index": i} for i, e in enumerate(result)],
+                "model": model or self.model_path,
+                "usage": {"prompt_tokens": n, "total_tokens": n}}
 
     def _stream(self, cid, tokens, max_tokens, params, stops, cancel_event, mname=None, echo_text=None,
                 stopping_criteria=None):

@@ -50,6 +50,7 @@ class _Base:
     bos_id: int
     eos_id: int
     add_bos_token: bool = True   # tokenizer.ggml.add_bos_token: False = encode(add_bos=True) adds none
+    add_eos_token: bool = False  # tokenizer.ggml.add_eos_token: embedding inputs end in EOS (Llama.embed)
 
     def _init_specials(self):
         self.token_to_id: Dict[str, int] = {t: i for i, t in enumerate(self.tokens)}
@@ -250,6 +251,12 @@ class SPMTokenizer(_Base):
 
 
 def tokenizer_from_metadata(md: dict):
+    tok = _tokenizer_from_metadata(md)
+    tok.add_eos_token = bool(md.get("tokenizer.ggml.add_eos_token", False))
+    return tok
+
+
+def _tokenizer_from_metadata(md: dict):
     model = md.get("tokenizer.ggml.model", "gpt2")
     tokens = md["tokenizer.ggml.tokens"]
     types = md.get("tokenizer.ggml.token_type") or [TOKEN_TYPE_NORMAL] * len(tokens)

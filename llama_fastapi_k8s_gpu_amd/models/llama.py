@@ -53,6 +53,7 @@ class LlamaHParams:
     rope_neox: bool = False      # RoPE pairs (i, i + head_dim/2) instead of (2i, 2i+1)
     qkv_bias: bool = False       # blk.N.attn_{q,k,v}.bias present (set by the loaders from the tensors)
     qk_norm: bool = False        # blk.N.attn_{q,k}_norm.weight present (qwen3; set by the loaders likewise)
+    pooling_type: int = -1       # {arch}.pooling_type (0 none, 1 mean, 2 cls, 3 last, 4 rank); -1: key absent
 
     @property
     def n_embd_kv(self) -> int:
@@ -91,7 +92,8 @@ class LlamaHParams:
                    rope_base=float(g("rope.freq_base", 10000.0)),
                    rms_eps=float(g("attention.layer_norm_rms_epsilon", 1e-5)),
                    n_ctx_train=int(g("context_length", 2048)), arch=arch,
-                   rope_neox=arch in ("qwen2", ARCH_QWEN3))
+                   rope_neox=arch in ("qwen2", ARCH_QWEN3),
+                   pooling_type=int(g("pooling_type", -1)))
 
 
 def rope_tables(hp: LlamaHParams, n_pos: int):
@@ -350,8 +352,9 @@ class ReferenceLlama:
         return torch.einsum("htl,lhd->thd", torch.softmax(s, -1), V).reshape(T, -1)
 
     def forward(self, tokens, n_past: int, all_logits: bool = False, trace: Optional[List[Dict]] = None,
-                path: Optional[str] = None, router_trace: Optional[List] = None):
-        """Evaluate ``tokens`` at positions n_past.. ; returns logits [T,V] or [V].
+                path: Optional[str] = None, router_trace: Optional[List] = None, hidden: bool = False):
+        """Evaluate ``tokens`` at positions n_past.. ; returns logits [T,V] or [V] (``hidden``: the
+        rows [T, n_embd] after the output RMSNorm instead, exact fp32 - what the lm_head reads).
         ``trace`` (a list) receives per layer the last token's q / k / v (roped), the attention
         output, x after the attention residual, the SwiGLU output and x after the FFN residual.
         ``path``: None (exact fp32) or the engine path whose rounding to reproduce (class doc).
@@ -393,6 +396,8 @@ class ReferenceLlama:
             x = x + self._ffn(L, x, path)
             if trace is not None and not self.hp.n_expert:
                 trace[-1]["x_ffn"] = x[-1].clone()
+        if hidden:
+            return self._rms(x, self.out_norm)
         # the logits: prefill and decode both end on the GEMV head (q8); the batched head
         # stages f16(x / rms * w) for the tile16 f16 output weights
         hpath = {"prefill": "decode", "prefill16": "decode"}.get(path, path)
@@ -405,3 +410,8 @@ class ReferenceLlama:
         if all_logits:
             return xo @ W.T
         return xo[-1] @ W.T
+
+    def hidden(self, tokens, path: Optional[str] = None):
+        """The normed final rows [T, n_embd] of ``tokens`` from position 0 (text embeddings pool
+        these); overwrites the KV cache from position 0."""
+        return self.forward(list(tokens), 0, path=path, hidden=True)

@@ -57,6 +57,19 @@ class CpuBackend:
         self.tp_rank, self.tp_size = rank, size
         self.n_ctx = n_ctx
 
+    def embed(self, inputs, pooling: int, normalize: bool, cancel=None):
+        """One vector per input (pooling none: its rows): eval_hidden over all layers (n_batch
+        chunks inside the engine), then the output RMSNorm and the pooling in fp32 on the host.
+        Overwrites the KV cache from position 0."""
+        if self.tp_size > 1:
+            raise NotImplementedError("embeddings are not supported on the tensor-parallel cpu backend")
+        import numpy as np
+
+        from ..engine.pooling import pool_host, rms_norm_rows
+        w, eps = np.asarray(self.engine.out_norm, np.float32), float(self.engine.hparams["rms_eps"])
+        return [pool_host(rms_norm_rows(self.engine.eval_hidden(list(toks), 0), w, eps), pooling,
+                          normalize) for toks in inputs]
+
     def health(self):
         return {"ok": True, "backend": self.name, "tp": self.tp_size}
 

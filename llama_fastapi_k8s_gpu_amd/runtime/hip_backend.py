@@ -225,6 +225,39 @@ class HipBackend:
         return GenerationResult(list(r["tokens"]), r["finish"], int(r["n_evaluated"]), r["prefill_s"],
                                 r["decode_s"], int(r["n_prefilled"]), lps)
 
+    def embed(self, inputs, pooling: int, normalize: bool, cancel=None):
+        """One float32 vector per input (pooling none: its rows [n_tokens, n_embd]), pooled on the
+        device (Engine.embed). With a scheduler the job borrows free KV slots between decode steps
+        (``cancel``: an event polled while waiting); without one the caller holds the facade's lock
+        and the inputs go through slot 0 one at a time, overwriting its KV."""
+        import numpy as np
+        if self.tp_size > 1:
+            raise NotImplementedError("embeddings are not supported on the tensor-parallel hip backend")
+        inputs = [[int(t) for t in toks] for toks in inputs]
+        d = int(self.engine.hparams["n_embd"])
+        if self.sched is None:
+            out = []
+            for toks in inputs:
+                r = self.engine.embed([0], [toks], int(pooling), bool(normalize))
+                out.append(np.asarray(r[0], np.float32))
+            return out
+        jid = self.sched.submit_embed(inputs, int(pooling), bool(normalize))
+        try:
+            while True:
+                r = self.sched.wait_embed(jid, 20)
+                if r["done"]:
+                    break
+                if cancel is not None and cancel.is_set():
+                    self.sched.cancel(jid)
+        finally:
+            self.sched.release(jid)
+        if r["finish"] == "error":
+            raise RuntimeError(r["error"] or "embedding failed")
+        if r["finish"] != "done":
+            raise RuntimeError(f"embedding {r['finish']}")
+        return [np.asarray(v, np.float32).reshape(-1, d) if pooling == 0 else np.asarray(v, np.float32)
+                for v in r["vectors"]]
+
     def save_kv(self, n: int, on_device: bool = False):
         """KV snapshot of positions [0, n): host bytes, or (``on_device``) an HBM buffer
         filled by a device-to-device strided copy - 288 GB of HBM holds thousands of

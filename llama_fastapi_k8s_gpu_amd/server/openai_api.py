@@ -1,4 +1,4 @@
-"""OpenAI-compatible routes (``/v1/models``, ``/v1/completions``, ``/v1/chat/completions``,
+"""OpenAI-compatible routes (``/v1/models``, ``/v1/completions``, ``/v1/chat/completions``, ``/v1/embeddings``,
 with server-sent-event streaming) over the same engine and the same admission queue as
 ``POST /response``.
 
@@ -60,6 +60,27 @@ class ChatCompletionRequest(_Base):
     logprobs: bool = False
     top_logprobs: Optional[int] = None
     response_format: Optional[Dict[str, Any]] = None
+
+
+class EmbeddingRequest(BaseModel):
+    model_config = ConfigDict(extra="allow")
+    input: Union[str, List[str], List[int], List[List[int]]]
+    model: Optional[str] = None
+    encoding_format: str = "float"       # float | base64 (little-endian float32 bytes)
+    dimensions: Optional[int] = None     # accepted only when it equals the model's n_embd
+    user: Optional[str] = None
+
+
+_POOLING = {"mean": 1, "cls": 2, "last": 3}
+
+
+def _embedding_pooling(setting: str, eng) -> int:
+    """EMBEDDING_POOLING -> pooling type: auto = the model's own pooling_type, mean where the model
+    has none (or says none): OpenAI clients expect one vector per input."""
+    if setting in _POOLING:
+        return _POOLING[setting]
+    own = int(getattr(getattr(eng, "hparams", None), "pooling_type", -1))
+    return own if own > 0 else _POOLING["mean"]
 
 
 def _error(status: int, message: str, typ: str = "invalid_request_error"):
@@ -174,6 +195,49 @@ def add_openai_routes(app, settings, metrics, submit: Callable[[Callable, thread
             finally:
                 cancel.set()      # client gone (or finished): stop the generation if still running
         return StreamingResponse(sse(), media_type="text/event-stream")
+
+    @app.post("/v1/embeddings")
+    async def embeddings(req: EmbeddingRequest):
+        if req.encoding_format not in ("float", "base64"):
+            return _error(400, "encoding_format must be 'float' or 'base64'")
+        cancel = threading.Event()
+        t0 = time.monotonic()
+
+        def job(eng, cancel_event):
+            create = getattr(eng, "create_embedding", None)
+            if create is None:
+                raise NotImplementedError("this engine serves no embeddings")
+            kw = {"cancel_event": cancel_event} if getattr(eng, "supports_cancel", False) else {}
+            out = create(req.input, req.model or model_name(), normalize=True,
+                         pooling_type=_embedding_pooling(settings.embedding_pooling, eng), **kw)
+            for item in out["data"]:
+                if req.dimensions is not None and req.dimensions != len(item["embedding"]):
+                    raise ValueError(f"dimensions={req.dimensions} differs from the model's {len(item['embedding'])}: "
+                                     "truncated embeddings are not supported")
+                if req.encoding_format == "base64":
+                    import base64
+                    import struct
+                    item["embedding"] = base64.b64encode(
+                        struct.pack(f"<{len(item['embedding'])}f", *item["embedding"])).decode("ascii")
+            return out
+        fut = submit(job, cancel)     # the same FIFO as the generation routes (503 when it is full)
+        try:
+            out = await asyncio.wait_for(fut, timeout=settings.timeout_seconds)
+        except asyncio.TimeoutError:
+            fut.cancel()
+            cancel.set()
+            metrics.requests.labels("timeout_408").inc()
+            return _error(408, "Embedding timed out", "timeout")
+        except (ValueError, NotImplementedError) as e:
+            metrics.requests.labels("error_400").inc()
+            return _error(400, str(e))
+        except Exception as e:
+            metrics.requests.labels("error_500").inc()
+            return _error(500, f"Internal server error: {e}", "server_error")
+        metrics.requests.labels("ok").inc()
+        metrics.latency.observe(time.monotonic() - t0)
+        metrics.observe_engine(out)
+        return out
 
     @app.post("/v1/completions")
     async def completions(req: CompletionRequest):
