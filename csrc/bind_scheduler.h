@@ -84,6 +84,13 @@ void bind_scheduler(pybind11::module_& m) {
              return b.submit_embed(inputs, pooling, normalize);
            },
            py::arg("inputs"), py::arg("pooling"), py::arg("normalize") = false)
+      // scoring job (wait_embed serves it: vectors = per input its rows' records, 4 floats each, flattened)
+      .def("submit_score",
+           [](BatchScheduler& b, const std::vector<std::vector<int>>& inputs) {
+             py::gil_scoped_release nogil;
+             return b.submit_score(inputs);
+           },
+           py::arg("inputs"))
       // vectors: one list of floats per input (pooling none: the input's rows, flattened)
       .def("wait_embed",
            [](BatchScheduler& b, int64_t id, int timeout_ms) {
@@ -117,6 +124,8 @@ void bind_scheduler(pybind11::module_& m) {
              d["embed_jobs"] = s.embed_jobs;
              d["embed_inputs"] = s.embed_inputs;
              d["embed_tokens"] = s.embed_tokens;
+             d["score_jobs"] = s.score_jobs;
+             d["score_tokens"] = s.score_tokens;
              d["active"] = s.active;
              d["pending"] = s.pending;
              d["slots"] = s.slots;

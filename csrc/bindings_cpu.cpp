@@ -286,6 +286,17 @@ PYBIND11_MODULE(_cpu, m) {
              std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(float));
              return a;
            })
+      .def("score",
+           [](CpuEngine& e, const std::vector<int>& tokens) {
+             std::vector<float> v;
+             {
+               py::gil_scoped_release nogil;
+               v = e.score(tokens);
+             }
+             py::array_t<float> a({(py::ssize_t)tokens.size(), (py::ssize_t)4});
+             std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(float));
+             return a;
+           })
       .def("kv_state_bytes", &CpuEngine::kv_state_bytes)
       .def("kv_save",
            [](CpuEngine& e, int n) {

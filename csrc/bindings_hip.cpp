@@ -44,8 +44,10 @@ PYBIND11_MODULE(_hip, m) {
   py::class_<Engine>(m, "Engine")
       .def(py::init([](const std::string& path, int n_ctx, int n_batch, int device, bool use_graph, int tp_rank,
                        int tp_size, py::bytes nccl_id, int layer_begin, const std::vector<float>& tensor_split,
-                       int n_slots, const std::string& comm, int layer_end, const std::string& test_fault) {
+                       int n_slots, const std::string& comm, int layer_end, const std::string& test_fault,
+                       bool scoring) {
              EngineOptions o;
+             o.scoring = scoring;
              o.test_fault = test_fault;
              o.layer_begin = layer_begin;
              o.layer_end = layer_end;
@@ -66,7 +68,7 @@ PYBIND11_MODULE(_hip, m) {
            py::arg("use_graph") = true, py::arg("tp_rank") = 0, py::arg("tp_size") = 1,
            py::arg("nccl_id") = py::bytes(""), py::arg("layer_begin") = 0,
            py::arg("tensor_split") = std::vector<float>{}, py::arg("n_slots") = 1, py::arg("comm") = "auto",
-           py::arg("layer_end") = -1, py::arg("test_fault") = "")
+           py::arg("layer_end") = -1, py::arg("test_fault") = "", py::arg("scoring") = false)
       .def(
           "generate",
           [](Engine& e, const std::vector<int>& prompt, int n_keep, int max_new, py::dict sp,
@@ -211,6 +213,26 @@ PYBIND11_MODULE(_hip, m) {
              return a;
            },
            py::arg("slots"), py::arg("inputs"), py::arg("pooling"), py::arg("normalize") = false)
+      // prompt log-probabilities (Engine::score): per input a float32 [n_tokens_i][4] array of
+      // [lp(next token) (NaN in the last row), log-sum-exp, most probable next token, its lp]
+      .def("score",
+           [](Engine& e, const std::vector<std::vector<int>>& inputs, const std::vector<int>& slots) {
+             std::vector<std::vector<float>> v;
+             {
+               py::gil_scoped_release nogil;
+               v = e.score(inputs, slots);
+             }
+             py::list out;
+             for (const auto& r : v) {
+               py::array_t<float> a({(py::ssize_t)r.size() / SlotBackend::kScoreRowFloats,
+                                     (py::ssize_t)SlotBackend::kScoreRowFloats});
+               std::memcpy(a.mutable_data(), r.data(), sizeof(float) * r.size());
+               out.append(a);
+             }
+             return out;
+           },
+           py::arg("inputs"), py::arg("slots"))
+      .def_property_readonly("scoring", &Engine::scoring)
       .def("batch_step",
            [](Engine& e, const std::vector<int>& slots) {
              py::gil_scoped_release nogil;
@@ -766,6 +788,21 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("ldo"), py::arg("out_h"), py::arg("ldh"), py::arg("epi"), py::arg("stream"), py::arg("resid") = 0,
      py::arg("cfg") = 0, py::arg("wseg") = std::vector<std::pair<uintptr_t, int>>{}, py::arg("seg_dev") = 0,
      py::arg("rows_hint") = 0, py::arg("out_zeroed") = false, py::arg("tile_stride") = 0, py::arg("step0") = 0);
+
+  // the scoring head over raw buffers (kernels.h ScoreHeadArgs): `w` is the tile16 copy of a
+  // [rows][K] head, `targets` the host copy of `target`; records [T][SCORE_REC_WORDS]
+  m.attr("SCORE_REC_WORDS") = kScoreRecWords;
+  m.def("score_head_workspace_words", &score_head_workspace_words, py::arg("T"), py::arg("V"), py::arg("gpr") = 0);
+  m.def("score_head", [](uintptr_t w, int type, int rows, int K, int V, uintptr_t x, int T, uintptr_t target,
+                         const std::vector<int>& targets, uintptr_t part, size_t part_words, uintptr_t rec,
+                         uintptr_t stream, int gpr) {
+    if ((int)targets.size() != T) throw std::runtime_error("score_head: one target per row");
+    score_head(score_head_args(make_qmat(P<void>(w), type, rows, K), V, P<__half>(x), T, P<int>(target),
+                               targets.data(), P<float>(part), part_words, P<float>(rec), gpr), S(stream));
+    hip_ok("score_head");
+  }, py::arg("w"), py::arg("type"), py::arg("rows"), py::arg("K"), py::arg("V"), py::arg("x"), py::arg("T"),
+     py::arg("target"), py::arg("targets"), py::arg("part"), py::arg("part_words"), py::arg("rec"), py::arg("stream"),
+     py::arg("gpr") = 0);
 
   m.def("attn_decode", [](uintptr_t q, uintptr_t kc, uintptr_t vc, uintptr_t pos, int n_ctx, int n_head, int n_kv,
                           int hd, float scale, uintptr_t part, uintptr_t out, uintptr_t stream, uintptr_t counters,

@@ -918,6 +918,31 @@ std::vector<float> CpuEngine::eval_hidden(const std::vector<int>& tokens, int po
   return out;
 }
 
+std::vector<float> CpuEngine::score(const std::vector<int>& tokens) {
+  if (sp_.tp > 1) throw std::runtime_error("score: tensor-parallel CPU engines score no text");
+  if (layer_end_ != n_layer_) throw std::runtime_error("score: this engine holds only a part of the layers");
+  const int T = (int)tokens.size();
+  for (int t : tokens)
+    if (t < 0 || t >= n_vocab_) throw std::runtime_error("score: token id outside the vocabulary");
+  const std::vector<float> x = eval_hidden(tokens, 0);
+  std::vector<float> out((size_t)T * 4), logits(n_vocab_);
+  for (int r = 0; r < T; ++r) {
+    head(x.data() + (size_t)r * n_embd_, logits.data());
+    int best = 0;
+    for (int i = 1; i < n_vocab_; ++i)
+      if (logits[i] > logits[best]) best = i;  // lowest id on ties
+    double s = 0;
+    for (int i = 0; i < n_vocab_; ++i) s += std::exp((double)logits[i] - (double)logits[best]);
+    const double lse = (double)logits[best] + std::log(s);
+    float* o = out.data() + (size_t)r * 4;
+    o[0] = r + 1 < T ? (float)((double)logits[tokens[r + 1]] - lse) : std::nanf("");
+    o[1] = (float)lse;
+    o[2] = (float)best;
+    o[3] = (float)((double)logits[best] - lse);
+  }
+  return out;
+}
+
 CpuGenOut CpuEngine::generate(const std::vector<int>& prompt, int n_keep, int max_new, const CpuSampling& sp,
                               const std::vector<int>& stop, const std::function<bool()>& poll,
                               const std::function<void(int)>& on_token) {

@@ -75,6 +75,9 @@ class CpuEngine {
   void head(const float* xrow, float* logits);
   // hybrid: hidden states after layers [0, layer_end) for tokens at pos0.. ([T][n_embd])
   std::vector<float> eval_hidden(const std::vector<int>& tokens, int pos0);
+  // prompt log-probabilities on the host: every row's logits through head(), log-softmax in fp64.
+  // Per row [lp(tokens[r + 1]) (NaN in the last row), log-sum-exp, argmax (lowest id on ties), its lp]
+  std::vector<float> score(const std::vector<int>& tokens);
   // the output RMSNorm's weight [n_embd] (text embeddings norm the rows of eval_hidden with it)
   const std::vector<float>& out_norm() const { return out_norm_; }
   // KV state of positions [0, n): [K|V][n_layer][local kv heads][n][hd] f16 (save/load_state)

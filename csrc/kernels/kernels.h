@@ -229,6 +229,8 @@ struct BmmArgs {
 // split-K Q|K|V (BmmArgs::qkv_sk): false = unsupported shape / type mix (caller: one-part path)
 bool bmm_qkv_sk_supported(int tq, int tk, int tv, int K, int B);
 bool bmm_supported(int type, int K);
+// compute units of the device (queried once, at the first call): the tile16 launchers size their grids by it
+int bmm_cus();
 bool bmm_qkv_fits(int K, int B);   // the Q|K|V epilogue needs one K part (x slice in LDS)
 bool bmm_norm_fits(int K, int B);  // one K part + the folded RMSNorm's staging shape
 void bmm(const BmmArgs& a, hipStream_t s);
@@ -547,6 +549,40 @@ struct GemmT16Args {
   int wseg_tiles[3] = {0, 0, 0};
 };
 void gemm_t16(const GemmT16Args& a, int epi, hipStream_t s);
+
+// Scoring head (score.hip): the lm_head over T rows WITHOUT storing the [T][V] logits - per row the
+// natural-log probability of a given target token, the log-sum-exp, and the most probable token
+// with its log-probability (lowest id on ties). gemm_t16's main loop over the head's tile16 copy;
+// a block owns TM tokens x a contiguous range of 256-row vocabulary groups and carries an online
+// log-sum-exp per token in registers over its range (stage 1: one kScorePartWords partial per
+// token at part[range][t]); stage 2 (one wave per token) merges the ranges in a fixed order. No
+// split-K, no atomics: two runs are bit-equal. Weight rows >= V (tile padding) are masked.
+static constexpr int kScorePartWords = 5;  // {max, sum exp(l - max), target logit, best logit, best id}
+static constexpr int kScoreRecWords = 4;   // {lp(target) (NaN: no target), lse, best id (int), lp(best)}
+struct ScoreHeadArgs {
+  QMat w;                          // base = tile16 copy; rows = the copy's rows (a multiple of 16, >= V)
+  int V = 0;                       // real vocabulary
+  const __half* x = nullptr;       // [T][K] f16, bmm k order (rmsnorm_bf16(..., f16sw = true))
+  int T = 0;
+  const int* target = nullptr;     // [T] device: the token to score per row, -1 for none
+  const int* h_target = nullptr;   // host copy: checked (0 <= target < V or -1) before any launch
+  float* part = nullptr;           // stage-1 partials, score_head_workspace_words(T, V, gpr) words
+  size_t part_words = 0;           // capacity of `part`
+  float* rec = nullptr;            // [T][kScoreRecWords], 16-byte aligned
+  int gpr = 0;                     // vocabulary groups per range pin (tests, tuning); 0: the rule
+};
+// the args over a head's tile16 copy `t16` (rows = the planar matrix's, V or V padded to 16)
+inline ScoreHeadArgs score_head_args(const QMat& t16, int V, const __half* x, int T, const int* target,
+                                     const int* h_target, float* part, size_t part_words, float* rec, int gpr = 0) {
+  ScoreHeadArgs a;
+  a.w = t16; a.w.rows = (t16.rows + 15) / 16 * 16; a.V = V;
+  a.x = x; a.T = T; a.target = target; a.h_target = h_target;
+  a.part = part; a.part_words = part_words; a.rec = rec; a.gpr = gpr;
+  return a;
+}
+size_t score_head_workspace_words(int T, int V, int gpr = 0);
+// validates every bound on the host and throws before anything is queued
+void score_head(const ScoreHeadArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- MoE prefill (grouped experts)
 // Device-side routing: per-expert row lists in ascending token order (moe.hip).

@@ -148,6 +148,7 @@ Engine::Engine(const std::string& path, const EngineOptions& opts) : opt_(opts) 
   alloc_buffers();
   build_rope();
   setup_batch_mfma();
+  setup_scoring();
   HIPCHK(hipStreamSynchronize(stream_));
 }
 
@@ -186,6 +187,8 @@ Engine::~Engine() {
   }
   if (h_rmeta_) hipHostFree(h_rmeta_);
   if (h_lp_) hipHostFree(h_lp_);
+  if (h_score_tgt_) hipHostFree(h_score_tgt_);
+  if (h_score_rec_) hipHostFree(h_score_rec_);
   if (wo_err_h_) hipHostFree(wo_err_h_);
   if (chain_err_h_) hipHostFree(chain_err_h_);
   for (auto& e : step_ev_) if (e) hipEventDestroy(e);
@@ -580,6 +583,27 @@ void Engine::setup_batch_mfma() {
     if (hp_.n_expert > 0) t16 = t16 && L.down_exps.K % 256 == 0 && L.gu_exps.rows % 16 == 0;
   }
   prefill_t16_ = t16;
+}
+
+void Engine::setup_scoring() {
+  if (!opt_.scoring || tp_on_ || !has_head() || opt_.layer_begin > 0) return;  // (score() refuses those engines)
+  if (!output_.base || !bmm_supported(output_.type, output_.K))
+    throw std::runtime_error("scoring: the output head (type " + std::to_string(output_.type) + ", K " +
+                             std::to_string(output_.K) + ") has no tile16 form (a tile16 type, K a multiple of 256)");
+  if (hp_.n_vocab >= (1 << 24)) throw std::runtime_error("scoring: vocabulary ids must stay below 2^24");
+  if (!t_output_.base || t_output_.base == output_.base) {  // one KV slot, or a model the batched path does not serve
+    t_output_ = output_;
+    uint8_t* dst = (uint8_t*)dalloc(t16_bytes(output_.type, output_.rows, output_.K));
+    t16_repack(output_, dst, stream_);
+    t_output_.base = dst;
+  }
+  const int B = nb_cap_;
+  for (int T = 1; T <= B; ++T) score_part_words_ = std::max(score_part_words_, score_head_workspace_words(T, hp_.n_vocab));
+  score_part_ = (float*)dalloc(sizeof(float) * score_part_words_);
+  score_tgt_ = (int*)dalloc(sizeof(int) * B);
+  score_rec_ = (float*)dalloc(sizeof(float) * B * kScoreRecWords);
+  HIPCHK(hipHostMalloc((void**)&h_score_tgt_, sizeof(int) * B, hipHostMallocDefault));
+  HIPCHK(hipHostMalloc((void**)&h_score_rec_, sizeof(float) * B * kScoreRecWords, hipHostMallocDefault));
 }
 
 std::vector<long long> Engine::step_clk() {
@@ -2002,6 +2026,80 @@ std::vector<std::vector<float>> Engine::embed(const std::vector<int>& slots,
     HIPCHK(hipMemcpy(host.data(), pool_out_, sizeof(float) * host.size(), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) std::copy(host.begin() + i * d, host.begin() + (i + 1) * d, out[i].begin());
   }
+  check_device_err();
+  return out;
+}
+
+std::vector<std::vector<float>> Engine::score(const std::vector<std::vector<int>>& inputs,
+                                              const std::vector<int>& slots) {
+  if (tp_on_) throw std::runtime_error("score: tensor-parallel engines score no text");
+  if (!has_head() || opt_.layer_begin > 0) throw std::runtime_error("score: this engine holds only a part of the layers");
+  if (!score_rec_) throw std::runtime_error("score: the engine was built without scoring (EngineOptions::scoring)");
+  ExecGuard guard(this);
+  const size_t n = slots.size();
+  if (n < 1 || (int)n > opt_.n_slots || inputs.size() != n) throw std::runtime_error("score: 1 <= inputs <= n_slots");
+  if (!bmax_ && n != 1) throw std::runtime_error("score: an engine with one KV slot takes one input");
+  std::vector<int> input_of(opt_.n_slots, -1);
+  for (size_t i = 0; i < n; ++i) {
+    if (slots[i] < 0 || slots[i] >= opt_.n_slots) throw std::runtime_error("score: slot out of range");
+    if (input_of[slots[i]] >= 0) throw std::runtime_error("score: duplicate slot");
+    input_of[slots[i]] = (int)i;
+    if (inputs[i].empty()) throw std::runtime_error("score: empty input");
+    if ((int)inputs[i].size() > opt_.n_ctx) throw std::runtime_error("score: input exceeds context window");
+    for (int tok : inputs[i])
+      if (tok < 0 || tok >= hp_.n_vocab) throw std::runtime_error("score: token id outside the vocabulary");
+  }
+  const int d = hp_.n_embd;
+  constexpr int W = kScoreRecWords;
+  static_assert(W == SlotBackend::kScoreRowFloats, "a record is one row of the result");
+  std::vector<std::vector<float>> out(n);
+  for (size_t i = 0; i < n; ++i) out[i].resize(inputs[i].size() * (size_t)W);
+  // the records of the chunk queued last reach the pinned mirror behind its launches: they are
+  // read once the stream has been synchronised (packed_prefill does after every chunk)
+  std::vector<PrefillSeg> queued;
+  auto harvest = [&]() {
+    for (const PrefillSeg& g : queued) {
+      float* o = out[input_of[g.slot]].data() + (size_t)g.pos * W;
+      const float* h = h_score_rec_ + (size_t)g.row * W;
+      for (int r = 0; r < g.n; ++r, o += W, h += W) {
+        int best;
+        std::memcpy(&best, h + 2, sizeof(int));
+        o[0] = h[0]; o[1] = h[1]; o[2] = (float)best; o[3] = h[3];
+      }
+    }
+    queued.clear();
+  };
+  // the epilogue of one chunk, on its residual rows: output norm as f16 rows, then the scoring head
+  auto score_chunk = [&](const std::vector<PrefillSeg>& segs) {
+    harvest();
+    int rows = 0;
+    for (const PrefillSeg& g : segs) {
+      const std::vector<int>& in = inputs[input_of[g.slot]];
+      for (int r = 0; r < g.n; ++r) h_score_tgt_[g.row + r] = g.pos + r + 1 < (int)in.size() ? in[g.pos + r + 1] : -1;
+      rows = std::max(rows, g.row + g.n);
+    }
+    __half* const xh16 = reinterpret_cast<__half*>(xb_);
+    HIPCHK(hipMemcpyAsync(score_tgt_, h_score_tgt_, sizeof(int) * rows, hipMemcpyHostToDevice, stream_));
+    rmsnorm_bf16(x_, out_norm_, hp_.rms_eps, rows, d, xb_, stream_, nullptr, 0, /*f16sw=*/true);
+    score_head(score_head_args(t_output_, hp_.n_vocab, xh16, rows, score_tgt_, h_score_tgt_, score_part_,
+                               score_part_words_, score_rec_), stream_);
+    HIPCHK(hipMemcpyAsync(h_score_rec_, score_rec_, sizeof(float) * W * rows, hipMemcpyDeviceToHost, stream_));
+    queued = segs;
+  };
+  if (bmax_) {
+    packed_prefill(slots, inputs, std::vector<int>(n, 0), score_chunk);
+  } else {
+    const std::vector<int>& in = inputs[0];
+    const int np = (int)in.size();
+    for (int pos = 0; pos < np;) {
+      const int T = std::min(opt_.n_batch, np - pos);
+      prefill_chunk(slots[0], in.data() + pos, T, pos, /*head=*/false);
+      score_chunk({PrefillSeg{0, T, slots[0], pos, pos + T == np}});
+      HIPCHK(hipStreamSynchronize(stream_));  // the pinned targets and records are rewritten next
+      pos += T;
+    }
+  }
+  harvest();
   check_device_err();
   return out;
 }

@@ -47,6 +47,9 @@ struct EngineOptions {
   // KV slots (continuous batching): slot 0 serves generate() / the graph decode path, slots
   // [0, n_slots) can decode together through batch_step() (also under tensor parallelism)
   int n_slots = 1;
+  // prompt scoring (Engine::score): builds the head's tile16 copy (also with one KV slot) and the
+  // scoring buffers; a head whose type or K has no tile16 form is refused at construction
+  bool scoring = false;
   bool verbose = false;
   // fault-injection test hook, "<rank>:<n>[:dev|:shard]" (empty in production; set only by the tests
   // through the Python backend's explicit opt-in, runtime/hip_backend.py): follower <rank> fails its
@@ -260,6 +263,19 @@ class Engine : public SlotBackend {
                                               bool normalize) override {
     return embed(slots, inputs, pooling, normalize);
   }
+  // Prompt log-probabilities (EngineOptions::scoring): embed's route - inputs[i] prefilled into KV
+  // slot slots[i] from position 0, packed as slots_begin packs them (one KV slot: one input, chunk
+  // by chunk) - with another epilogue: each chunk's residual rows go through the output RMSNorm as
+  // f16 rows and the scoring head (kernels.h ScoreHeadArgs), which never stores the logits. Row r's
+  // target is the input's own token r + 1 (carried across chunk borders; none for the last row).
+  // Returns per input its rows' records, SlotBackend::kScoreRowFloats floats each. No lm_head
+  // GEMV, no sampler, no sampling state; the slots' KV is overwritten. One rank, all layers.
+  std::vector<std::vector<float>> score(const std::vector<std::vector<int>>& inputs, const std::vector<int>& slots);
+  std::vector<std::vector<float>> score_begin(const std::vector<int>& slots,
+                                              const std::vector<std::vector<int>>& inputs) override {
+    return score(inputs, slots);
+  }
+  bool scoring() const { return score_rec_ != nullptr; }
   long long logprob_launches() const { return lp_launches_.load(); }
   // inspection hook (tests): single-row decode layers enqueued as the one attention + Wo launch
   // (attn_wo1) so far - per step when eager, per capture under a graph; 0 with LFK_WO_FUSE=0
@@ -346,6 +362,14 @@ class Engine : public SlotBackend {
   int* pool_segs_ = nullptr;     // [max(n_slots, 1)][kPoolSegInts] the chunk's segment table
   int* h_pool_segs_ = nullptr;   // pinned copy
   int pool_part_rows_ = 0;
+  // scoring epilogue (setup_scoring; null unless EngineOptions::scoring)
+  void setup_scoring();
+  int* score_tgt_ = nullptr;      // [nb_cap_] the chunk's target per row
+  int* h_score_tgt_ = nullptr;    // pinned copy
+  float* score_part_ = nullptr;   // the head's partial workspace (the largest a chunk can need)
+  size_t score_part_words_ = 0;
+  float* score_rec_ = nullptr;    // [nb_cap_][kScoreRecWords]
+  float* h_score_rec_ = nullptr;  // pinned mirror
   int* rpos_ = nullptr;     // [n_batch] per-row position of a packed chunk
   int* rslots_ = nullptr;   // [n_batch] per-row KV slot
   int* h_rmeta_ = nullptr;  // pinned [3][n_batch]: tokens | positions | slots

@@ -83,16 +83,27 @@ SchedPoll BatchScheduler::wait(int64_t id, size_t have, int timeout_ms) {
 }
 
 int64_t BatchScheduler::submit_embed(const std::vector<std::vector<int>>& inputs, int pooling, bool normalize) {
-  if (inputs.empty()) throw std::runtime_error("embed: no inputs");
   if (pooling < 0 || pooling > 3) throw std::runtime_error("embed: unknown pooling type");
+  return submit_job(inputs, pooling, normalize, /*score=*/false);
+}
+
+int64_t BatchScheduler::submit_score(const std::vector<std::vector<int>>& inputs) {
+  return submit_job(inputs, 0, false, /*score=*/true);
+}
+
+int64_t BatchScheduler::submit_job(const std::vector<std::vector<int>>& inputs, int pooling, bool normalize,
+                                   bool score) {
+  const std::string what = score ? "score" : "embed";
+  if (inputs.empty()) throw std::runtime_error(what + ": no inputs");
   for (const auto& in : inputs) {
-    if (in.empty()) throw std::runtime_error("embed: empty input");
-    if ((int)in.size() > eng_.n_ctx()) throw std::runtime_error("embed: input exceeds context window");
+    if (in.empty()) throw std::runtime_error(what + ": empty input");
+    if ((int)in.size() > eng_.n_ctx()) throw std::runtime_error(what + ": input exceeds context window");
   }
   auto j = std::make_shared<EmbedJob>();
   j->inputs = inputs;
   j->pooling = pooling;
   j->normalize = normalize;
+  j->score = score;
   {
     std::lock_guard<std::mutex> g(mu_);
     if (stop_) throw std::runtime_error("BatchScheduler: shut down");
@@ -340,13 +351,13 @@ void BatchScheduler::loop() {
       }
       if (!e_in.empty()) {
         const int pooling = j->pooling;
-        const bool normalize = j->normalize;
+        const bool normalize = j->normalize, score = j->score;
         std::string err;
         std::vector<std::vector<float>> vecs;
         lk.unlock();
         try {
-          vecs = eng_.embed_begin(e_slots, e_in, pooling, normalize);
-          if (vecs.size() != e_in.size()) throw std::runtime_error("embed_begin: one vector per input");
+          vecs = score ? eng_.score_begin(e_slots, e_in) : eng_.embed_begin(e_slots, e_in, pooling, normalize);
+          if (vecs.size() != e_in.size()) throw std::runtime_error("embed_begin / score_begin: one vector per input");
         } catch (const std::exception& e) {
           err = e.what();
         }
@@ -359,14 +370,18 @@ void BatchScheduler::loop() {
           j->error = err;
           finish_embed(*j, "error");
         } else {
-          st_.embed_inputs += (long long)e_in.size();
-          st_.embed_tokens += rows_in;
+          if (score) {
+            st_.score_tokens += rows_in;
+          } else {
+            st_.embed_inputs += (long long)e_in.size();
+            st_.embed_tokens += rows_in;
+          }
           for (auto& v : vecs) j->vectors.push_back(std::move(v));
           j->next += e_in.size();
           if (j->cancel && j->next < j->inputs.size()) {
             finish_embed(*j, "cancelled");
           } else if (j->next == j->inputs.size()) {
-            ++st_.embed_jobs;
+            ++(score ? st_.score_jobs : st_.embed_jobs);
             finish_embed(*j, "done");
           }
         }

@@ -56,6 +56,8 @@ struct SchedStats {
   long long embed_jobs = 0;      // embedding jobs completed
   long long embed_inputs = 0;    // their inputs, as embed_begin passes took them
   long long embed_tokens = 0;    // ... and those inputs' tokens
+  long long score_jobs = 0;      // scoring jobs completed
+  long long score_tokens = 0;    // tokens of the inputs their score_begin passes took
   int active = 0, pending = 0, slots = 0;
 };
 
@@ -88,6 +90,10 @@ class BatchScheduler {
   // after a pass, their resident prefix gone. Ids share the requests' id space (cancel / release).
   int64_t submit_embed(const std::vector<std::vector<int>>& inputs, int pooling, bool normalize);
   SchedEmbedPoll wait_embed(int64_t id, int timeout_ms);
+  // Scoring: a second kind of the same job - same ordering, free-slot rule, row cap and loss of the
+  // borrowed slots' resident prefix - whose passes call SlotBackend::score_begin. wait_embed serves
+  // it: `vectors` holds per input its rows' records (SlotBackend::kScoreRowFloats floats each).
+  int64_t submit_score(const std::vector<std::vector<int>>& inputs);
   void cancel(int64_t id);    // cooperative: the row leaves the batch before the next step
   void release(int64_t id);   // forget a finished (or abandoned: cancels it) request
   SchedStats stats();
@@ -115,12 +121,14 @@ class BatchScheduler {
     std::vector<std::vector<int>> inputs;
     int pooling = 0;
     bool normalize = false;
+    bool score = false;  // a scoring job (score_begin passes; pooling / normalize unused)
     size_t next = 0;  // inputs [0, next) are done
     std::vector<std::vector<float>> vectors;
     bool cancel = false, done = false;
     std::string finish, error;
   };
   void finish_embed(EmbedJob& j, const char* reason);
+  int64_t submit_job(const std::vector<std::vector<int>>& inputs, int pooling, bool normalize, bool score);
   void loop();
   void finish(Req& r, const char* reason);
   // append one sampled token (and, for a request that asked, its entry of the engine's

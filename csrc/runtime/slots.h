@@ -79,6 +79,16 @@ class SlotBackend {
     (void)slots; (void)inputs; (void)pooling; (void)normalize;
     throw std::runtime_error("embeddings are not supported by this backend");
   }
+  // Scoring (optional): prefill input i into slots[i] from position 0 and return, per row r of the
+  // input, kScoreRowFloats floats: the log-probability of token r + 1 given tokens [0, r] (NaN for
+  // the last row), the row's log-sum-exp, the most probable next token (its id as a float: exact,
+  // vocabularies stay below 2^24) and that token's log-probability. Slots as embed_begin.
+  static constexpr int kScoreRowFloats = 4;
+  virtual std::vector<std::vector<float>> score_begin(const std::vector<int>& slots,
+                                                      const std::vector<std::vector<int>>& inputs) {
+    (void)slots; (void)inputs;
+    throw std::runtime_error("scoring is not supported by this backend");
+  }
 };
 
 }  // namespace lfk

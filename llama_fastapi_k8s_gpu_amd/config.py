@@ -74,6 +74,9 @@ class Settings:
     max_batch: int = 1
     # POST /v1/embeddings: auto (the model's own pooling_type; mean where it has none) | mean | last | cls
     embedding_pooling: str = "auto"
+    # Llama(logits_all=True): /v1/completions with echo and logprobs fills the prompt tokens'
+    # log-probabilities (the MI355X engine builds its scoring head)
+    logits_all: bool = False
     # tensor parallelism (split_mode=row over torchrun ranks): the engine's collectives -
     # "auto" (one-shot P2P kernel for decode, RCCL for prefill), "rccl", or "ipc" (the P2P
     # kernel only: ranks may share a GPU). tp_device puts EVERY rank on that GPU (the one-GPU
@@ -136,6 +139,7 @@ class Settings:
         s.embedding_pooling = _env("EMBEDDING_POOLING", s.embedding_pooling).lower()
         if s.embedding_pooling not in ("auto", "mean", "last", "cls"):
             raise ValueError(f"EMBEDDING_POOLING={s.embedding_pooling!r}: auto, mean, last or cls")
+        s.logits_all = _env("LOGITS_ALL", s.logits_all, bool)
         s.tp_comm = _env("TP_COMM", s.tp_comm).lower()
         tpd = _env("TP_DEVICE", None)
         s.tp_device = int(tpd) if tpd is not None else None

@@ -113,6 +113,21 @@ class ReferenceBackend:
         return [pool_host(self.model.hidden(list(toks)).numpy().astype(np.float64), pooling, normalize, np.float64)
                 for toks in inputs]
 
+    def score(self, inputs, cancel=None):
+        """Per input [n_tokens, 4] rows [lp(next token) (NaN in the last row), log-sum-exp, argmax
+        (lowest id on ties), its lp]: the exact fp32 model's logits of every row, log-softmax in
+        float64. Overwrites the KV cache from position 0."""
+        import numpy as np
+        out = []
+        for toks in inputs:
+            toks = [int(t) for t in toks]
+            l = self.model.forward(toks, 0, all_logits=True).numpy().astype(np.float64)
+            lse = l.max(1) + np.log(np.exp(l - l.max(1, keepdims=True)).sum(1))
+            best = l.argmax(1)
+            lp = np.append(l[np.arange(len(toks) - 1), toks[1:]] - lse[:-1], np.nan)
+            out.append(np.stack([lp, lse, best, l.max(1) - lse], 1).astype(np.float32))
+        return out
+
     def generate(self, prompt: Sequence[int], n_keep: int, max_new: int, params: SamplingParams,
                  stop_ids: Sequence[int], poll: Optional[Callable[[], bool]] = None,
                  on_token: Optional[Callable[[int], None]] = None) -> GenerationResult:

@@ -19,4 +19,5 @@ def build_engine(settings: Settings):
                  tensor_split=settings.tensor_split, split_mode=settings.split_mode,
                  main_gpu=settings.main_gpu, seed=settings.seed, chat_format=settings.chat_format,
                  use_graphs=settings.use_graphs, verbose=settings.verbose,
-                 **({"max_batch": settings.max_batch} if settings.max_batch > 1 else {}), **tp)
+                 **({"max_batch": settings.max_batch} if settings.max_batch > 1 else {}),
+                 **({"logits_all": True} if settings.logits_all else {}), **tp)

@@ -75,7 +75,7 @@ class Llama:
                  main_gpu: int = 0, seed: Optional[int] = None, chat_format: Optional[str] = None,
                  last_n_tokens_size: int = 64, use_graphs: bool = True, verbose: bool = True,
                  backend: Optional[str] = None, n_threads: Optional[int] = None, embedding: bool = False,
-                 pooling_type: int = -1, **kwargs):
+                 pooling_type: int = -1, logits_all: bool = False, **kwargs):
         t0 = time.perf_counter()
         if not os.path.exists(model_path):
             raise ValueError(f"Model path does not exist: {model_path}")
@@ -91,6 +91,9 @@ class Llama:
         self.last_n_tokens_size = last_n_tokens_size
         self.embedding = bool(embedding)   # accepted for upstream compatibility: embed() needs no mode switch
         self.pooling_type = resolve_pooling(pooling_type, self.hparams.pooling_type)
+        # upstream's parameter: with it, echoed prompt tokens carry log-probabilities (score()); the
+        # MI355X engine then builds its scoring head's buffers (it never keeps [T][V] logits)
+        self.logits_all = bool(logits_all)
         self.verbose = verbose
         self._seed = seed if seed is not None else int.from_bytes(os.urandom(4), "little")
         self._request_ids = itertools.count(1)   # per-request seed derivation (thread-safe)
@@ -125,7 +128,7 @@ class Llama:
             from ..runtime.hip_backend import HipBackend
             self._backend = HipBackend(model_path, self.hparams, n_ctx=self._n_ctx, n_gpu_layers=n_gpu_layers,
                                        tensor_split=tensor_split, split_mode=split_mode, main_gpu=main_gpu,
-                                       n_batch=n_batch, use_graphs=use_graphs, **kwargs)
+                                       n_batch=n_batch, use_graphs=use_graphs, logits_all=self.logits_all, **kwargs)
         else:
             raise ValueError(f"unknown backend {kind!r}")
         del reader
@@ -379,11 +382,15 @@ class Llama:
         return self.detokenize([t]).decode("utf-8", errors="ignore")
 
     def _completion_logprobs(self, prompt_tokens: List[int], toks: List[int], res: GenerationResult, echo: bool,
-                             prompt_text: str):
+                             prompt_text: str, prompt_rows=None, n_top: int = 0):
         """The OpenAI / llama-cpp-python ``logprobs`` block. Generated tokens carry the
         log-probabilities of the raw model logits; echoed prompt tokens carry None (the
         engine keeps only the last prompt position's logits - upstream needs
-        ``logits_all=True`` for those)."""
+        ``logits_all=True`` for those). With ``logits_all=True`` the caller passes ``prompt_rows``
+        (``_score_rows`` of the prompt): every echoed token but the first then carries its
+        log-probability, and its ``top_logprobs`` holds the token itself and, for ``n_top >= 1``, the
+        most probable token at that position - prompt positions carry at most that ONE alternative
+        (the scoring head keeps no logits to rank more from)."""
         entries = list(res.logprobs or [])[:len(toks)]
         all_toks = (list(prompt_tokens) if echo else []) + list(toks)
         strs = [self._piece(t) for t in all_toks]
@@ -397,11 +404,20 @@ class Llama:
             out["tokens"].append(ts)
             out["text_offset"].append(offset + run)
             run += len(ts)
-            if i < n_echo:
+            if i < n_echo and (prompt_rows is None or i == 0):
                 out["token_logprobs"].append(None)
                 out["top_logprobs"].append(None)
                 continue
+            if i < n_echo:   # row i - 1 predicts token i
+                lp, _, best, best_lp = (float(v) for v in prompt_rows[i - 1])
+                out["token_logprobs"].append(lp)
+                d = {self._piece(int(best)): best_lp} if n_top >= 1 else {}
+                d[ts] = lp
+                out["top_logprobs"].append(d)
+                continue
             lp, top = entries[i - n_echo] if i - n_echo < len(entries) else (None, [])
+            if prompt_rows is not None:
+                top = top[:n_top]   # (logprobs=0 under logits_all asked the sampler for one entry)
             out["token_logprobs"].append(lp)
             d = {self._piece(j): v for j, v in top}
             if lp is not None:
@@ -430,17 +446,29 @@ class Llama:
             tokens = list(prompt)
             prompt_text = self.detokenize(tokens).decode("utf-8", errors="replace")
         stops = [stop] if isinstance(stop, str) else list(stop or [])
+        # logits_all: echoed prompt tokens carry log-probabilities. logprobs=0 then asks the sampler for
+        # the chosen token's own value too (one entry, trimmed from top_logprobs below), so that prompt
+        # and generated positions of one response are filled alike
+        score_prompt = (self.logits_all and echo and not stream and logprobs is not None and logprobs >= 0
+                        and len(tokens) > 1)
         params = self._params(temperature, top_p, top_k, min_p, typical_p, tfs_z, repeat_penalty,
                               frequency_penalty, presence_penalty, seed, logit_bias, mirostat_mode,
-                              mirostat_tau, mirostat_eta, logprobs, logits_processor, grammar)
+                              mirostat_tau, mirostat_eta, 1 if score_prompt and logprobs == 0 else logprobs,
+                              logits_processor, grammar)
         cid = f"cmpl-{uuid.uuid4()}"
         mname = model or self.model_path
         if stream:
             return self._stream(cid, tokens, max_tokens, params, stops, cancel_event, mname,
                                 echo_text=prompt_text if echo else None, stopping_criteria=stopping_criteria)
+        # the prompt's own log-probabilities first (the generation then refills the KV)
+        rows = None
+        if score_prompt:
+            rows = self._score_rows([self._embed_tokens(tokens, truncate=False)], cancel_event)[0]
         text, toks, reason, res = self._generate(tokens, max_tokens, params, stops, cancel_event,
                                                  stopping_criteria=stopping_criteria)
-        lp = self._completion_logprobs(tokens, toks, res, echo, prompt_text) if params.n_probs > 0 else None
+        lp = None
+        if params.n_probs > 0 or rows is not None:
+            lp = self._completion_logprobs(tokens, toks, res, echo, prompt_text, rows, int(logprobs or 0))
         return {"id": cid, "object": "text_completion", "created": int(time.time()),
                 "model": mname,
                 "choices": [{"text": (prompt_text + text) if echo else text, "index": 0, "logprobs": lp,
@@ -512,6 +540,50 @@ class Llama:
         out = [np.asarray(v, np.float32).tolist() for v in vecs]
         result = out[0] if single else out
         return (result, sum(len(t) for t in inputs)) if return_count else result
+
+    # ------------------------------------------------------------ scoring
+    def _score_rows(self, inputs: List[List[int]], cancel_event=None):
+        """Per input the backend's [n_tokens, 4] rows: [lp(next token), log-sum-exp, most probable
+        next token, its lp] (the last row's lp is NaN)."""
+        score = getattr(self._backend, "score", None)
+        if score is None:
+            raise NotImplementedError(f"scoring is not supported on the {self.backend_name} backend")
+        if not self.logits_all:
+            raise RuntimeError("score() and echoed prompt log-probabilities need Llama(..., logits_all=True)")
+        if getattr(self._backend, "sched", None) is not None:
+            return score(inputs, cancel=cancel_event)   # borrows free slots of the batch
+        with self._lock:
+            try:
+                return score(inputs, cancel=cancel_event)
+            finally:
+                self._kv_tokens = []   # the pass overwrote the KV cache: no prefix to reuse
+
+    def score(self, input: Union[str, List[str], List[int], List[List[int]]],
+              cancel_event: Optional[threading.Event] = None):
+        """How likely is this text under the model: per input a dict of ``token_logprobs`` (the
+        natural-log probability of every token given the ones before it; ``None`` for the first),
+        ``greedy`` (per position: is the token the model's most probable one; ``None`` for the
+        first) and ``logprob``, their sum. ``input`` follows ``embed``'s conventions: a string, a list
+        of strings, a list of token ids (one input) or a list of such lists; strings are tokenised
+        with BOS; an input longer than ``n_ctx`` raises ``ValueError``. A single string or id list
+        returns one dict, a list of inputs a list of dicts. Needs ``logits_all=True`` at
+        construction. On the MI355X engine the prompt is prefilled once and a fused lm_head +
+        log-softmax kernel reduces each row on the fly - no [T][V] logits exist. The backend's KV
+        cache is overwritten."""
+        single = isinstance(input, str)
+        items = [input] if single else list(input)
+        if not items:
+            raise ValueError("score: no input")
+        if not single and all(isinstance(t, (int, np.integer)) for t in items):
+            items, single = [items], True   # a list of token ids is one input
+        inputs = [self._embed_tokens(it, truncate=False) for it in items]
+        out = []
+        for toks, rows in zip(inputs, self._score_rows(inputs, cancel_event)):
+            lps = [float(v) for v in np.asarray(rows)[:-1, 0]]
+            greedy = [int(b) == t for b, t in zip(np.asarray(rows)[:-1, 2], toks[1:])]
+            out.append({"tokens": toks, "token_logprobs": [None] + lps, "greedy": [None] + greedy,
+                        "logprob": float(np.sum(lps, dtype=np.float64))})
+        return out[0] if single else out
 
     def create_embedding(self, input: Union[str, List[str], List[int], List[List[int]]], model: Optional[str] = None,
                          normalize: bool = False, pooling_type: Optional[int] = None,

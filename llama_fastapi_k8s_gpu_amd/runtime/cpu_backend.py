@@ -70,6 +70,14 @@ class CpuBackend:
         return [pool_host(rms_norm_rows(self.engine.eval_hidden(list(toks), 0), w, eps), pooling,
                           normalize) for toks in inputs]
 
+    def score(self, inputs, cancel=None):
+        """Per input [n_tokens, 4] rows [lp(next token) (NaN in the last row), log-sum-exp, argmax, its
+        lp]: every row's logits through the C++ head, log-softmax in fp64 (CpuEngine::score).
+        Overwrites the KV cache from position 0."""
+        if self.tp_size > 1:
+            raise NotImplementedError("scoring is not supported on the tensor-parallel cpu backend")
+        return [self.engine.score([int(t) for t in toks]) for toks in inputs]
+
     def health(self):
         return {"ok": True, "backend": self.name, "tp": self.tp_size}
 

@@ -89,7 +89,7 @@ class HipBackend:
     def __init__(self, model_path: str, hparams, n_ctx: int = 1024, n_gpu_layers: int = -1,
                  tensor_split: Optional[Sequence[float]] = None, split_mode: str = "layer", main_gpu: int = 0,
                  n_batch: int = 512, use_graphs: bool = True, max_batch: int = 1, tp_comm: Optional[str] = None,
-                 device: Optional[int] = None, **_):
+                 device: Optional[int] = None, logits_all: bool = False, **_):
         hip = load_hip()
         if 0 <= n_gpu_layers < hparams.n_layer:
             raise ValueError(f"n_gpu_layers={n_gpu_layers} < n_layer={hparams.n_layer}: partial offload runs on "
@@ -112,7 +112,8 @@ class HipBackend:
         self.engine = hip.Engine(model_path, n_ctx=n_ctx, n_batch=min(n_batch, n_ctx), device=device,
                                  use_graph=use_graphs, tp_rank=rank, tp_size=size, nccl_id=nccl_id,
                                  tensor_split=ts, n_slots=max_batch + 1 if max_batch > 1 else 1, comm=comm,
-                                 test_fault=_test_fault() if size > 1 else "")
+                                 test_fault=_test_fault() if size > 1 else "",
+                                 scoring=bool(logits_all) and size == 1)
         self.n_ctx = n_ctx
         self.n_vocab = int(hparams.n_vocab)
         self.n_batch = min(n_batch, n_ctx)  # the engine's prefill chunk bound (eval_logits rejects T > n_batch)
@@ -257,6 +258,35 @@ class HipBackend:
             raise RuntimeError(f"embedding {r['finish']}")
         return [np.asarray(v, np.float32).reshape(-1, d) if pooling == 0 else np.asarray(v, np.float32)
                 for v in r["vectors"]]
+
+    def score(self, inputs, cancel=None):
+        """Per input a float32 [n_tokens, 4] array of [log-probability of the next token (NaN in
+        the last row), log-sum-exp, most probable next token, its log-probability], computed by the
+        device's scoring head (Engine.score: no logits are stored). Needs ``logits_all=True`` at
+        construction. Slots and cancellation as ``embed``."""
+        import numpy as np
+        if self.tp_size > 1:
+            raise NotImplementedError("scoring is not supported on the tensor-parallel hip backend")
+        if not self.engine.scoring:
+            raise RuntimeError("scoring needs logits_all=True when the model is loaded")
+        inputs = [[int(t) for t in toks] for toks in inputs]
+        if self.sched is None:
+            return [np.asarray(self.engine.score([toks], [0])[0], np.float32) for toks in inputs]
+        jid = self.sched.submit_score(inputs)
+        try:
+            while True:
+                r = self.sched.wait_embed(jid, 20)
+                if r["done"]:
+                    break
+                if cancel is not None and cancel.is_set():
+                    self.sched.cancel(jid)
+        finally:
+            self.sched.release(jid)
+        if r["finish"] == "error":
+            raise RuntimeError(r["error"] or "scoring failed")
+        if r["finish"] != "done":
+            raise RuntimeError(f"scoring {r['finish']}")
+        return [np.asarray(v, np.float32).reshape(-1, 4) for v in r["vectors"]]
 
     def save_kv(self, n: int, on_device: bool = False):
         """KV snapshot of positions [0, n): host bytes, or (``on_device``) an HBM buffer
