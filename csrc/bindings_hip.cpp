@@ -721,6 +721,41 @@ PYBIND11_MODULE(_hip, m) {
     hip_ok("moe_scatter_add");
   });
 
+  // wide MoE (moe_wide.hip; tests/test_moe_wide_gpu.py): the engine's own argument builders
+  m.def("moe_router_wide", [](uintptr_t x, int ldx, int rows, uintptr_t nw, float eps, uintptr_t W, int d, int E, int k,
+                              uintptr_t ws, uintptr_t logits, uintptr_t ids, uintptr_t w, uintptr_t stream) {
+    moe_router_wide(P<float>(x), ldx, rows, P<float>(nw), eps, P<float>(W), d, E, k, P<void>(ws), P<float>(logits),
+                    P<int>(ids), P<float>(w), S(stream));
+    hip_ok("moe_router_wide");
+  }, py::arg("x"), py::arg("ldx"), py::arg("rows"), py::arg("nw"), py::arg("eps"), py::arg("W"), py::arg("d"),
+     py::arg("E"), py::arg("k"), py::arg("ws"), py::arg("logits"), py::arg("ids"), py::arg("w"), py::arg("stream"));
+  m.def("moe_router_wide_ok", &moe_router_wide_ok);
+  m.def("moe_gemm_grouped_ok", &moe_gemm_grouped_ok);
+  m.def("moe_router_wide_workspace", &moe_router_wide_workspace);
+  m.def("moe_group_wide_workspace", &moe_group_wide_workspace);
+  m.def("moe_group_wide_items", &moe_group_wide_items);
+  m.attr("MOE_ITEM_ROWS") = kMoeItemRows;
+  m.def("moe_route_group_wide", [](uintptr_t logits, int T, int E, int k, uintptr_t sel, uintptr_t selw,
+                                   uintptr_t cnt_off, uintptr_t tok, uintptr_t gw, uintptr_t pos, uintptr_t items,
+                                   uintptr_t n_items, uintptr_t ws, uintptr_t stream) {
+    moe_route_group_wide(P<float>(logits), T, E, k, P<int>(sel), P<float>(selw), P<int>(cnt_off), P<int>(tok),
+                         P<float>(gw), P<int>(pos), P<int>(items), P<int>(n_items), P<void>(ws), S(stream));
+    hip_ok("moe_route_group_wide");
+  });
+  // one projection of all routed experts: swiglu - gate/up (w: the SwiGLU copies back to back, x [T k][d]
+  // -> out f16 [T k][F]); else down (w: the experts concatenated along K, x [T k][F] -> out f32 [T k][d])
+  m.def("moe_gemm_grouped", [](uintptr_t w, int type, int d, int F, int E, uintptr_t x, uintptr_t out, bool swiglu,
+                               uintptr_t items, uintptr_t n_items, int max_items, uintptr_t stream) {
+    const MoeGroupedArgs a =
+        swiglu ? moe_grouped_gate_up_args(P<uint8_t>(w), type, F, d, E, P<__half>(x), P<__half>(out), P<int>(items),
+                                          P<int>(n_items), max_items)
+               : moe_grouped_down_args(P<uint8_t>(w), type, d, F, E, P<__half>(x), P<float>(out), P<int>(items),
+                                       P<int>(n_items), max_items);
+    moe_gemm_grouped(a, S(stream));
+    hip_ok("moe_gemm_grouped");
+  }, py::arg("w"), py::arg("type"), py::arg("d"), py::arg("F"), py::arg("E"), py::arg("x"), py::arg("out"),
+     py::arg("swiglu"), py::arg("items"), py::arg("n_items"), py::arg("max_items"), py::arg("stream"));
+
   m.def("moe_router_rows", [](uintptr_t x, int ldx, int B, uintptr_t nw, float eps, uintptr_t W, int d, int E, int k,
                               uintptr_t wd, int ld, uintptr_t stream) {
     moe_router_rows(P<float>(x), ldx, B, P<float>(nw), eps, P<float>(W), d, E, k, P<float>(wd), ld, S(stream));

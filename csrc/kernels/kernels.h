@@ -592,6 +592,53 @@ void gather_rows_bf16(const __hip_bfloat16* src, const int* tok, int n_rows, int
                       hipStream_t s);
 void moe_scatter_add(float* acc, const float* y, const int* pos, const float* gw, int T, int k, int d, hipStream_t s);
 
+// ---------------------------------------------------------------- wide MoE: 17 .. 256 experts (moe_wide.hip)
+// Router over `rows` f32 rows (row stride ldx): RMSNorm * nw -> F32 router W [E][d] -> softmax, top-k
+// (lowest id on a tie), renormalise. The experts of a row are split over blocks; the row's last block
+// finishes. ids / w [rows][k] (the sel / selw form of moe_route_group_wide), logits [rows][E] optional.
+// ws: moe_router_wide_workspace bytes for the most rows of any launch on it (<= 4096), zero before the
+// first launch; the kernel re-arms it, and launches of different row counts may share it.
+bool moe_router_wide_ok(int router_type, int E, int k, int d);
+size_t moe_router_wide_workspace(int rows, int E);
+void moe_router_wide(const float* x, int ldx, int rows, const float* nw, float eps, const float* W, int d, int E, int k,
+                     void* ws, float* logits, int* ids, float* w, hipStream_t s);
+// moe_route_group's outputs for E <= 256, k <= 16 over blocks of 16 tokens, plus the work list of
+// moe_gemm_grouped: items [n][3] = (expert, first gathered row, rows <= kMoeItemRows), none for an
+// expert without rows, and their count n_items [1] <= moe_group_wide_items(T, E, k). logits null:
+// sel / selw hold the picks already (moe_router_wide). ws as above.
+static constexpr int kMoeItemRows = 32;
+static constexpr int kMoeRouterRows = 16;  // up to this many rows the engine routes with moe_router_wide
+void zero_f32(float* p, size_t n, hipStream_t s);  // p[0, n) = 0 by a kernel (n % 4 == 0): no memset node
+int moe_group_wide_items(int T, int E, int k);
+size_t moe_group_wide_workspace(int T, int E);
+void moe_route_group_wide(const float* logits, int T, int E, int k, int* sel, float* selw, int* cnt_off, int* tok,
+                          float* gw, int* pos, int* items, int* n_items, void* ws, hipStream_t s);
+// One projection of every routed expert in one launch over the work list, on the experts' tile16
+// copies; block (x, y) multiplies item y's rows with weight rows [128 x, 128 x + 128) of its expert
+// and exits at once when y >= *n_items. Expert e's tile t starts at
+// w + e * expert_bytes + t * tile_stride + e * expert_step0 steps.
+struct MoeGroupedArgs {
+  const uint8_t* w = nullptr;
+  int type = 0, rows = 0, K = 0, n_expert = 0;  // one expert's matrix
+  size_t tile_stride = 0, expert_bytes = 0;
+  int expert_step0 = 0;
+  const __half* x = nullptr;   // gathered rows [T k][K] f16, bmm k order
+  __half* out_h = nullptr;     // swiglu: silu(gate) * up [T k][ld] f16, bmm k order
+  float* out = nullptr;        // else: [T k][ld] f32, stored plainly (nothing to pre-zero)
+  int ld = 0;
+  bool swiglu = false;
+  const int* items = nullptr;
+  const int* n_items = nullptr;
+  int max_items = 0;           // grid.y: moe_group_wide_items
+};
+bool moe_gemm_grouped_ok(int type, int rows, int K);
+void moe_gemm_grouped(const MoeGroupedArgs& a, hipStream_t s);
+// the engine's layouts: the experts' SwiGLU copies back to back; the down experts concatenated along K
+MoeGroupedArgs moe_grouped_gate_up_args(const uint8_t* t_gu, int type, int F, int d, int n_expert, const __half* xg,
+                                        __half* h, const int* items, const int* n_items, int max_items);
+MoeGroupedArgs moe_grouped_down_args(const uint8_t* t_down, int type, int d, int F, int n_expert, const __half* h,
+                                     float* y, const int* items, const int* n_items, int max_items);
+
 // ---------------------------------------------------------------- elementwise / misc
 // x[t][:] = dequant(token_embd[tokens[t]][:])
 // (side job: zero [zero, zero + zero_n) ints)

@@ -91,6 +91,9 @@ Engine::Engine(const std::string& path, const EngineOptions& opts) : opt_(opts) 
   GGUFFile f(path);
   hp_ = read_hparams(f);
   const int tp = opt_.tp_size, r = opt_.tp_rank;
+  // (an expert FFN of three 256-blocks does not split evenly over ranks)
+  if (hp_.arch == "qwen3moe" && (tp > 1 || opt_.comm == "rccl"))
+    throw std::runtime_error("qwen3moe: tensor parallelism is not supported");
   const ShardPlan sp =
       make_shard_plan(hp_.n_head, hp_.n_head_kv, hp_.head_dim, hp_.n_ff, hp_.n_vocab, tp, r, opt_.tensor_split);
   q0_ = sp.q_row0();
@@ -148,6 +151,7 @@ Engine::Engine(const std::string& path, const EngineOptions& opts) : opt_(opts) 
   alloc_buffers();
   build_rope();
   setup_batch_mfma();
+  setup_moe_wide();
   setup_scoring();
   HIPCHK(hipStreamSynchronize(stream_));
 }
@@ -407,6 +411,30 @@ void Engine::alloc_buffers() {
     moe_xg_ = (__hip_bfloat16*)dalloc(2 * R * d);
     moe_hg_ = (__hip_bfloat16*)dalloc(2 * R * F_l_);
     moe_yg_ = (float*)dalloc(sizeof(float) * R * d);
+    // Wide MoE: more than 16 experts on one rank, where the wide kernels take every layer. Under tensor
+    // parallelism, or for a file they decline (a router that is not F32, widths that are no multiples of
+    // 256), the few-expert paths stay as they were; qwen3moe has no such path to go back to
+    bool wide = hp_.n_expert > 16 && !tp_on_;
+    for (int l = opt_.layer_begin; wide && l < layer_end_; ++l) {
+      const Layer& L = layers_[l];
+      wide = moe_router_wide_ok(L.router.type, hp_.n_expert, hp_.n_expert_used, d) &&
+             moe_gemm_grouped_ok(L.gu_exps.type, 2 * F_l_, d) && moe_gemm_grouped_ok(L.down_exps.type, d, F_l_);
+    }
+    if (!wide && hp_.arch == "qwen3moe")
+      throw std::runtime_error("qwen3moe: " + std::to_string(hp_.n_expert) + " experts need an F32 router (17 .. 256 "
+                               "experts, top-k <= 16) and tile16 expert types with n_embd and the expert FFN width "
+                               "multiples of 256");
+    moe_wide_ = wide;
+    if (moe_wide_) {  // workspaces sized from E and k; the counters start at zero and re-arm themselves
+      moe_items_ = (int*)dalloc(sizeof(int) * 3 * moe_group_wide_items(B, E, KU));
+      moe_n_items_ = (int*)dalloc(sizeof(int));
+      const size_t rws = moe_router_wide_workspace(kMoeRouterRows, E), gws = moe_group_wide_workspace(B, E);
+      moe_router_ws_ = dalloc(rws);
+      moe_group_ws_ = dalloc(gws);
+      HIPCHK(hipMemset(moe_router_ws_, 0, rws));
+      HIPCHK(hipMemset(moe_group_ws_, 0, gws));
+      HIPCHK(hipMemset(moe_n_items_, 0, sizeof(int)));
+    }
   }
   HIPCHK(hipMemset(state_, 0, sizeof(int) * S_NSTATE * NS));
   HIPCHK(hipMemset(ring_, 0, sizeof(int) * 64 * NS));
@@ -477,6 +505,41 @@ void Engine::alloc_buffers() {
   }
 }
 
+// The experts' tile16 copies (the stacked batched decode and every grouped path read them):
+void Engine::tile_experts(Layer& L) {
+  const int E = hp_.n_expert;
+  // gate/up: the experts' SwiGLU tile16 copies back to back (expert e = tiles [e T, (e+1) T))
+  const size_t gu1 = t16_bytes(L.gu_exps.type, L.gu_exps.rows, L.gu_exps.K);
+  uint8_t* gdst = (uint8_t*)dalloc(gu1 * E);
+  // down: every 16-row tile's 256-k steps run expert 0's F_l, then expert 1's, ... (K = E F_l):
+  // each expert's copy goes through `tmp` and is strided into its step range of every tile
+  const int dsteps = L.down_exps.K / 256, dtiles = (L.down_exps.rows + 15) / 16;
+  const size_t dn1 = t16_bytes(L.down_exps.type, L.down_exps.rows, L.down_exps.K);
+  const size_t run = dn1 / dtiles;  // one tile's steps of one expert
+  uint8_t* ddst = (uint8_t*)dalloc(dn1 * E);
+  // one expert's copy, strided into place, then freed (the P2P receive region checks that it
+  // is a whole allocation of its own, runtime/p2p.cpp, so a reuse of this block cannot alias it)
+  uint8_t* tmp = nullptr;
+  HIPCHK(hipMalloc((void**)&tmp, dn1));
+  for (int e = 0; e < E; ++e) {
+    QMat g = L.gu_exps;
+    g.base += L.gu_exps.expert_stride * e;
+    g.expert_stride = 0;
+    t16_repack(g, gdst + gu1 * e, stream_, /*swiglu=*/true);
+    QMat dm = L.down_exps;
+    dm.base += L.down_exps.expert_stride * e;
+    dm.expert_stride = 0;
+    t16_repack(dm, tmp, stream_);
+    HIPCHK(hipMemcpy2DAsync(ddst + run * e, run * E, tmp, run, run, dtiles, hipMemcpyDeviceToDevice, stream_));
+  }
+  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipFree(tmp));
+  L.t_gu = L.gu_exps;
+  L.t_gu.base = gdst; L.t_gu.rows = L.gu_exps.rows * E; L.t_gu.expert_stride = 0;
+  L.t_down = L.down_exps;
+  L.t_down.base = ddst; L.t_down.K = dsteps * 256 * E; L.t_down.expert_stride = 0;
+}
+
 void Engine::setup_batch_mfma() {
   bg_ = bg_ffn_ = false;
   if (!bmax_ || opt_.layer_begin > 0 || !has_head()) return;
@@ -538,38 +601,7 @@ void Engine::setup_batch_mfma() {
     Layer& L = layers_[l];
     L.t_wq = tile(L.wq); L.t_wk = tile(L.wk); L.t_wv = tile(L.wv); L.t_wo = tile(L.wo);
     if (bg_ffn_) { L.t_gu = tile(L.w_gu, /*swiglu=*/true); L.t_down = tile(L.w_down); }
-    if (moe_b_) {
-      // gate/up: the experts' SwiGLU tile16 copies back to back (expert e = tiles [e T, (e+1) T))
-      const size_t gu1 = t16_bytes(L.gu_exps.type, L.gu_exps.rows, L.gu_exps.K);
-      uint8_t* gdst = (uint8_t*)dalloc(gu1 * E);
-      // down: every 16-row tile's 256-k steps run expert 0's F_l, then expert 1's, ... (K = E F_l):
-      // each expert's copy goes through `tmp` and is strided into its step range of every tile
-      const int dsteps = L.down_exps.K / 256, dtiles = (L.down_exps.rows + 15) / 16;
-      const size_t dn1 = t16_bytes(L.down_exps.type, L.down_exps.rows, L.down_exps.K);
-      const size_t run = dn1 / dtiles;  // one tile's steps of one expert
-      uint8_t* ddst = (uint8_t*)dalloc(dn1 * E);
-      // one expert's copy, strided into place, then freed (the P2P receive region checks that it
-      // is a whole allocation of its own, runtime/p2p.cpp, so a reuse of this block cannot alias it)
-      uint8_t* tmp = nullptr;
-      HIPCHK(hipMalloc((void**)&tmp, dn1));
-      for (int e = 0; e < E; ++e) {
-        QMat g = L.gu_exps;
-        g.base += L.gu_exps.expert_stride * e;
-        g.expert_stride = 0;
-        t16_repack(g, gdst + gu1 * e, stream_, /*swiglu=*/true);
-        QMat dm = L.down_exps;
-        dm.base += L.down_exps.expert_stride * e;
-        dm.expert_stride = 0;
-        t16_repack(dm, tmp, stream_);
-        HIPCHK(hipMemcpy2DAsync(ddst + run * e, run * E, tmp, run, run, dtiles, hipMemcpyDeviceToDevice, stream_));
-      }
-      HIPCHK(hipStreamSynchronize(stream_));
-      HIPCHK(hipFree(tmp));
-      L.t_gu = L.gu_exps;
-      L.t_gu.base = gdst; L.t_gu.rows = L.gu_exps.rows * E; L.t_gu.expert_stride = 0;
-      L.t_down = L.down_exps;
-      L.t_down.base = ddst; L.t_down.K = dsteps * 256 * E; L.t_down.expert_stride = 0;
-    }
+    if (moe_b_) tile_experts(L);
   }
   HIPCHK(hipStreamSynchronize(stream_));
   // dense models: prompt chunks on the same tile16 copies (gemm_t16: the dequantisation spread
@@ -583,6 +615,14 @@ void Engine::setup_batch_mfma() {
     if (hp_.n_expert > 0) t16 = t16 && L.down_exps.K % 256 == 0 && L.gu_exps.rows % 16 == 0;
   }
   prefill_t16_ = t16;
+}
+
+// Wide MoE (n_expert > 16: the stacked plan, which streams every expert, is declined): prompt chunks
+// and batched rows run the experts as two one-launch grouped GEMMs over the tile16 copies, with or
+// without a batched step - about twice the expert bytes of HBM (moe_wide_: alloc_buffers).
+void Engine::setup_moe_wide() {
+  if (!moe_wide_) return;
+  for (int l = opt_.layer_begin; l < layer_end_; ++l) tile_experts(layers_[l]);
 }
 
 void Engine::setup_scoring() {
@@ -924,6 +964,9 @@ void Engine::enqueue_layer_decode(int l, hipStream_t s) {
                              gemv_route_fits(L.gu_exps.type, F_l_, hp_.n_expert_used);
     if (route_in_gu) {
       // (routing happens in the gate/up launch below)
+    } else if (moe_wide_) {  // more than 16 experts: the router's rows split over blocks
+      moe_router_wide(x_, d, 1, L.ffn_norm, hp_.rms_eps, reinterpret_cast<const float*>(L.router.base), d, hp_.n_expert,
+                      hp_.n_expert_used, moe_router_ws_, router_logits_, moe_ids_, moe_w_, s);
     } else if (moe_router_fused_ok(L.router.type, hp_.n_expert, d)) {  // one launch: norm + f32 router + top-k
       moe_router_fused(x_, L.ffn_norm, hp_.rms_eps, reinterpret_cast<const float*>(L.router.base), d, hp_.n_expert,
                        hp_.n_expert_used, router_logits_, moe_ids_, moe_w_, s);
@@ -1155,6 +1198,35 @@ void Engine::enqueue_rows_ffn(int l, int T, hipStream_t s, bool t16) {
   const Layer& L = layers_[l];
   const int d = hp_.n_embd;
   const bool tp = tp_on_;
+  if (moe_wide_) {  // (never under tensor parallelism: alloc_buffers)
+    // n_expert > 16, prompt chunks and batched rows alike (no host sync: a captured step replays it):
+    // route -> row lists + work list -> gather -> gate/up and down as ONE launch each -> scatter-add
+    const int E = hp_.n_expert, KU = hp_.n_expert_used;
+    const float* logits = nullptr;
+    if (T <= kMoeRouterRows) {  // decode rows: the f32 router on x_, its experts split over blocks
+      moe_router_wide(x_, d, T, L.ffn_norm, hp_.rms_eps, reinterpret_cast<const float*>(L.router.base), d, E, KU,
+                      moe_router_ws_, nullptr, moe_sel_, moe_selw_, s);
+    } else {                    // a chunk: one router GEMM over the bf16 norm, the top-k in the row-list kernel
+      rmsnorm_bf16(x_, L.ffn_norm, hp_.rms_eps, T, d, xb_, s);
+      GemmArgs ra;
+      ra.w = L.router; ra.x = xb_; ra.T = T; ra.out = router_logits_; ra.ldo = E;
+      gemm_dq(ra, GEMM_STORE, s);
+      logits = router_logits_;
+    }
+    moe_route_group_wide(logits, T, E, KU, moe_sel_, moe_selw_, moe_off_, moe_tok_, moe_gw_, moe_pos_, moe_items_,
+                         moe_n_items_, moe_group_ws_, s);
+    rmsnorm_bf16(x_, L.ffn_norm, hp_.rms_eps, T, d, xb_, s, nullptr, 0, true);  // f16 rows (after the router read xb_)
+    gather_rows_bf16(xb_, moe_tok_, T * KU, d, moe_xg_, s);
+    const int mi = moe_group_wide_items(T, E, KU);
+    moe_gemm_grouped(moe_grouped_gate_up_args(L.t_gu.base, L.gu_exps.type, F_l_, d, E,
+                                              reinterpret_cast<const __half*>(moe_xg_),
+                                              reinterpret_cast<__half*>(moe_hg_), moe_items_, moe_n_items_, mi), s);
+    moe_gemm_grouped(moe_grouped_down_args(L.t_down.base, L.down_exps.type, d, F_l_, E,
+                                           reinterpret_cast<const __half*>(moe_hg_), moe_yg_, moe_items_,
+                                           moe_n_items_, mi), s);
+    moe_scatter_add(x_, moe_yg_, moe_pos_, moe_gw_, T, KU, d, s);
+    return;
+  }
   // MoE: the router GEMM reads the bf16 norm; the experts' f16 norm is written after it
   rmsnorm_bf16(x_, L.ffn_norm, hp_.rms_eps, T, d, xb_, s, nullptr, 0, t16 && hp_.n_expert == 0);
   if (t16 && hp_.n_expert == 0) {
@@ -1405,7 +1477,8 @@ BatchLayerPlan Engine::plan_batch_layer(int l, int B) const {
     p.ffn_norm_folded = fnorm;
   } else {
     // MoE without the stacked copies (or unsupported FFN types): the grouped-GEMM FFN of the prompt path
-    p.ffn = bg_ffn_ ? P::Ffn::prep : P::Ffn::grouped;
+    // (more than 16 experts: the same FFN function takes its one-launch grouped experts)
+    p.ffn = bg_ffn_ ? P::Ffn::prep : moe_wide_ ? P::Ffn::moe_grouped : P::Ffn::grouped;
   }
   return p;
 }
@@ -1452,7 +1525,7 @@ Engine::BatchFfnArgs Engine::batch_ffn_args(int l, int B, const BatchLayerPlan& 
     a.dn = bmm_moe_down_args(L.t_down, hh_b_, E * F_l_, acc, d, B, zero, zero_n, ew_b_, E, F_l_ / 256);
   } else if (p.ffn == P::Ffn::prep) {
     a.dn = bmm_down_args(L.t_down, xh_b_, F_l_, acc, d, B, zero, zero_n);
-  } else if (p.ffn != P::Ffn::grouped) {
+  } else if (p.ffn != P::Ffn::grouped && p.ffn != P::Ffn::moe_grouped) {
     // SwiGLU in the gate/up epilogue: one K part, silu(gate) * up straight to the down
     // projection's f16 input (hh_b_; xh_b_ is still being read by other blocks)
     a.gu = bmm_gate_up_args(L.t_gu, xh_b_, d, norm, B, hh_b_, F_l_);
@@ -1590,6 +1663,10 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     case P::Ffn::grouped:
       enqueue_rows_ffn(l, B, s);
       if (p.zero_qkv == P::ZeroQkv::memset) HIPCHK(hipMemsetAsync(qkv_b_, 0, sizeof(float) * qkv_b_zero_n(), s));
+      break;
+    case P::Ffn::moe_grouped:
+      enqueue_rows_ffn(l, B, s);
+      if (p.zero_qkv == P::ZeroQkv::memset) zero_f32(qkv_b_, qkv_b_zero_n(), s);  // (a kernel, not a memset node)
       break;
   }
 }

@@ -96,6 +96,7 @@ struct BatchLayerPlan {
     moe_stacked,   // Wo; router; the experts' stacked gate/up; their K-concatenated down
     prep,          // Wo; bprep, gate/up, SwiGLU prep, down
     grouped,       // Wo; the prompt path's grouped-GEMM FFN (enqueue_rows_ffn)
+    moe_grouped,   // Wo; wide MoE (n_expert > 16): router, row lists, two one-launch grouped expert GEMMs
   };
   enum class Tp { none, p2p_accumulate, rccl };
   enum class ZeroQkv { nobody, down, memset };  // who re-zeroes the split-K Q|K|V sums for the next layer
@@ -120,7 +121,8 @@ inline const char* to_string(BatchLayerPlan::Finish v) {
   return n[(int)v];
 }
 inline const char* to_string(BatchLayerPlan::Ffn v) {
-  static constexpr const char* n[] = {"wo_ffn_chain", "ffn_chain", "swiglu", "moe_stacked", "prep", "grouped"};
+  static constexpr const char* n[] = {"wo_ffn_chain", "ffn_chain", "swiglu", "moe_stacked", "prep", "grouped",
+                                      "moe_grouped"};
   return n[(int)v];
 }
 inline const char* to_string(BatchLayerPlan::Tp v) {
@@ -478,6 +480,12 @@ class Engine : public SlotBackend {
   __hip_bfloat16* moe_xg_ = nullptr; __hip_bfloat16* moe_hg_ = nullptr; float* moe_yg_ = nullptr;
   int* moe_ids_ = nullptr;
   float* moe_w_ = nullptr;
+  // wide MoE (moe_wide.hip, n_expert > 16): the work list, its count and the routing workspaces
+  bool moe_wide_ = false;
+  int* moe_items_ = nullptr; int* moe_n_items_ = nullptr;
+  void* moe_router_ws_ = nullptr; void* moe_group_ws_ = nullptr;
+  void setup_moe_wide();
+  void tile_experts(Layer& L);
   int* h_ring_ = nullptr;     // pinned [64]
   int* h_tokens_ = nullptr;   // pinned [n_batch]
 

@@ -216,10 +216,13 @@ void GGUFFile::prefetch(const GGUFTensor& t) const {
 HParams read_hparams(const GGUFFile& f) {
   HParams h;
   const std::string arch = f.get_str("general.architecture", "llama");
-  if (arch == "qwen3moe")
-    throw std::runtime_error("unsupported architecture qwen3moe (general.architecture): the Qwen3 MoE models are not served");
-  if (arch != "llama" && arch != "mistral" && arch != "mixtral" && arch != "qwen2" && arch != "qwen3")
+  if (arch != "llama" && arch != "mistral" && arch != "mixtral" && arch != "qwen2" && arch != "qwen3" && arch != "qwen3moe")
     throw std::runtime_error("unsupported architecture " + arch);
+  // qwen3moe: Qwen3's attention (QK-norm, key_length, NeoX pairs) over the Mixtral expert tensor set
+  const bool qwen3 = arch == "qwen3" || arch == "qwen3moe";
+  if (arch == "qwen3moe" && f.get_int(arch + ".expert_count", 0) <= 0)
+    throw std::runtime_error("unsupported architecture qwen3moe (general.architecture) without qwen3moe.expert_count: "
+                             "the dense models are qwen3");
   h.arch = arch;
   auto gi = [&](const char* k, int64_t d) { return (int)f.get_int(arch + "." + k, d); };
   h.n_embd = gi("embedding_length", 0);
@@ -227,7 +230,7 @@ HParams read_hparams(const GGUFFile& f) {
   h.n_head = gi("attention.head_count", 0);
   h.n_head_kv = gi("attention.head_count_kv", h.n_head);
   h.head_dim = gi("rope.dimension_count", h.n_head ? h.n_embd / h.n_head : 0);
-  if (arch == "qwen3") {  // the head width is a key of its own (Qwen3-0.6B: 16 heads of 128 at n_embd 1024)
+  if (qwen3) {  // the head width is a key of its own (Qwen3-0.6B: 16 heads of 128 at n_embd 1024)
     const std::string kl = arch + ".attention.key_length", vl = arch + ".attention.value_length";
     if (f.has(kl)) h.head_dim = (int)f.get_int(kl, 0);
     if (f.has(vl) && (int)f.get_int(vl, 0) != h.head_dim)
@@ -239,6 +242,14 @@ HParams read_hparams(const GGUFFile& f) {
   h.n_ff = gi("feed_forward_length", 0);
   h.n_expert = gi("expert_count", 0);
   h.n_expert_used = gi("expert_used_count", 0);
+  if (arch == "qwen3moe") {
+    // the experts' width is a key of its own (feed_forward_length is the dense size), else the tensor's shape
+    const GGUFTensor* g = f.find("blk.0.ffn_gate_exps.weight");
+    h.n_ff = gi("expert_feed_forward_length", g && g->ne.size() > 1 ? (int64_t)g->ne[1] : 0);
+    if (h.n_ff <= 0) throw std::runtime_error("qwen3moe.expert_feed_forward_length: missing, and no blk.0.ffn_gate_exps.weight");
+    if (h.n_expert > 256 || h.n_expert_used < 1 || h.n_expert_used > 16 || h.n_expert_used > h.n_expert)
+      throw std::runtime_error("qwen3moe.expert_count / expert_used_count: up to 256 experts, top-k up to 16");
+  }
   h.n_ctx_train = gi("context_length", 2048);
   h.rope_base = (float)f.get_float(arch + ".rope.freq_base", 10000.0);
   h.rms_eps = (float)f.get_float(arch + ".attention.layer_norm_rms_epsilon", 1e-5);
@@ -246,7 +257,7 @@ HParams read_hparams(const GGUFFile& f) {
   const GGUFTensor* emb = f.find("token_embd.weight");
   if (!emb) throw std::runtime_error("missing token_embd.weight");
   h.n_vocab = (int)emb->ne[1];
-  if (arch == "qwen2" || arch == "qwen3") {
+  if (arch == "qwen2" || qwen3) {
     h.rope_neox = true;
     const std::string key = arch + ".rope.scaling.type";
     if (f.has(key) && f.get_str(key, "") != "none")
@@ -271,7 +282,7 @@ HParams read_hparams(const GGUFFile& f) {
                                std::to_string(h.n_layer) + " layers");
     h.qkv_bias = with > 0;
   }
-  if (arch == "qwen3") {
+  if (qwen3) {
     // QK-norm weights: both of every layer, F32 [head_dim], or none anywhere
     int with = 0;
     for (int l = 0; l < h.n_layer; ++l) {

@@ -123,7 +123,7 @@ def guess_chat_format(metadata: dict) -> Optional[str]:
         return None
     known = KNOWN_TEMPLATES.get(tmpl)
     # a Qwen2 / Qwen2.5 / Qwen3 template (ChatML behind a long tool-calling preamble) matches none exactly
-    if known is None and metadata.get("general.architecture") in ("qwen2", "qwen3"):
+    if known is None and metadata.get("general.architecture") in ("qwen2", "qwen3", "qwen3moe"):
         return "chatml"
     return known
 

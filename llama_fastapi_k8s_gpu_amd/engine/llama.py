@@ -26,6 +26,7 @@ from typing import Any, Dict, Iterator, List, Optional, Sequence, Union
 
 import numpy as np
 
+from ..gguf.constants import ARCH_QWEN3MOE
 from ..gguf.reader import GGUFReader
 from ..models.llama import LlamaHParams
 from .backends import GenerationResult, ReferenceBackend
@@ -86,6 +87,8 @@ class Llama:
         self.tokenizer = tokenizer_from_metadata(self.metadata)
         if not self.hparams.n_vocab:
             self.hparams.n_vocab = self.tokenizer.n_vocab
+        if not self.hparams.n_ff and self.hparams.n_expert:   # qwen3moe without expert_feed_forward_length
+            self.hparams.n_ff = int(reader.tensors["blk.0.ffn_gate_exps.weight"].shape[1])
         self._n_ctx = int(n_ctx) if n_ctx else self.hparams.n_ctx_train
         self.n_batch = n_batch
         self.last_n_tokens_size = last_n_tokens_size
@@ -104,6 +107,10 @@ class Llama:
         self.chat_format, self._formatter = get_formatter(self.metadata, chat_format, bos, eos)
         kind = _select_backend(reader, self.hparams, n_gpu_layers, backend, split_mode, tensor_split)
         self.backend_name = kind
+        if self.hparams.arch == ARCH_QWEN3MOE and kind != "reference" and (
+                kind == "layer" or (split_mode == "row" and sum(1 for v in (tensor_split or []) if v > 0) > 1)):
+            raise NotImplementedError("qwen3moe: tensor parallelism and the layer split across GPUs are not supported "
+                                      "(an expert FFN of three 256-blocks does not split evenly)")
         if kind == "reference":
             self._backend = ReferenceBackend(reader, self._n_ctx)
         elif kind == "cpu":

@@ -87,9 +87,10 @@ FTYPE_MOSTLY_IQ4_NL = 25
 FTYPE_MOSTLY_IQ4_XS = 30
 
 # general.architecture values the engines serve, and the ones refused by name
-ARCHITECTURES = ("llama", "mistral", "mixtral", "qwen2", "qwen3")
+ARCHITECTURES = ("llama", "mistral", "mixtral", "qwen2", "qwen3", "qwen3moe")
 ARCH_QWEN3 = "qwen3"
-ARCH_QWEN3MOE = "qwen3moe"   # refused: 128 experts, a different router
+ARCH_QWEN3MOE = "qwen3moe"   # qwen3's attention over the mixtral expert tensors (128 experts, top-8)
+KEY_EXPERT_FF_LENGTH = "expert_feed_forward_length"   # the experts' width (feed_forward_length: the dense size)
 
 # qwen3 metadata keys ("{arch}." in front)
 KEY_ATTN_KEY_LENGTH = "attention.key_length"      # head_dim (need not be n_embd / n_head)

@@ -30,7 +30,7 @@ import numpy as np
 from .constants import (FTYPE_MOSTLY_IQ4_NL, FTYPE_MOSTLY_IQ4_XS, FTYPE_MOSTLY_Q2_K, FTYPE_MOSTLY_Q3_K_M, FTYPE_MOSTLY_Q3_K_S, FTYPE_MOSTLY_Q4_0,
                         FTYPE_MOSTLY_Q4_1, FTYPE_MOSTLY_Q4_K_M, FTYPE_MOSTLY_Q5_0, FTYPE_MOSTLY_Q5_1, FTYPE_MOSTLY_Q8_0, GGMLType, GGUFValueType,
                         TOKEN_TYPE_BYTE, TOKEN_TYPE_CONTROL, TOKEN_TYPE_NORMAL)
-from .constants import ARCH_QWEN3, KEY_ATTN_KEY_LENGTH, KEY_ATTN_VALUE_LENGTH, TENSOR_ATTN_K_NORM, TENSOR_ATTN_Q_NORM
+from .constants import ARCH_QWEN3, ARCH_QWEN3MOE, KEY_EXPERT_FF_LENGTH, KEY_ATTN_KEY_LENGTH, KEY_ATTN_VALUE_LENGTH, TENSOR_ATTN_K_NORM, TENSOR_ATTN_Q_NORM
 from .quants import random_blocks
 from .writer import GGUFWriter
 
@@ -91,6 +91,10 @@ class ModelSpec:
     tied_output: bool = False  # no output.weight: the head is token_embd.weight
     qk_norm: bool = False     # F32 blk.N.attn_{q,k}_norm.weight [head_dim] (Qwen3)
     hd: int = 0               # head width where it is not n_embd / n_head (Qwen3: attention.key_length)
+    # > 1: every router reads ONE coordinate of the normed input, its rows +-4 ratio^-rank along it (ranks
+    # drawn per layer): every logit is a multiple of that coordinate, so the gap between a token's 8th and
+    # 9th logit is a fixed fraction of them whatever the input - far above a bf16 rounding of that input
+    router_levels: float = 0.0
 
     @property
     def head_dim(self) -> int:
@@ -223,6 +227,16 @@ SPECS.update({
     # Qwen3-8B's shape (for measuring, not for tests)
     "qwen3-8b-q4_k_m": replace(_qwen3("Qwen3-8B", 4096, 36, 32, 8, 128, 12288, "q4_k_m", n_vocab=151936),
                                n_ctx_train=40960),
+})
+
+# Qwen3-MoE: Qwen3's attention over the Mixtral expert tensors, 128 experts, top-8, no shared expert; n_ff is
+# the experts' width (expert_feed_forward_length)
+SPECS.update({
+    "tiny-qwen3moe": replace(_qwen3("tiny-qwen3moe", 256, 2, 4, 2, 64, 256, "q4_k_m"), arch="qwen3moe", n_expert=128,
+                             n_expert_used=8, router_levels=1.5),
+    # Qwen3-30B-A3B's shape (for measuring, not for tests)
+    "qwen3-30b-a3b-q4_k_m": replace(_qwen3("Qwen3-30B-A3B", 2048, 48, 32, 4, 128, 768, "q4_k_m", n_vocab=151936),
+                                    arch="qwen3moe", n_expert=128, n_expert_used=8, n_ctx_train=40960),
 })
 
 # the legacy 32-weight block formats (Q4_0 / Q4_1 / Q5_0 / Q5_1) over existing shapes
@@ -383,7 +397,7 @@ def build_vocab(spec: ModelSpec) -> Tuple[Dict, int]:
                 tokens.append(cand)
         base = len(tokens)
         types = [TOKEN_TYPE_NORMAL] * base
-        qwen2 = spec.arch in ("qwen2", "qwen3")
+        qwen2 = spec.arch in ("qwen2", "qwen3", ARCH_QWEN3MOE)
         for k in range(256):
             name = (QWEN2_SPECIALS if qwen2 else LLAMA3_SPECIALS).get(k, f"<|reserved_special_token_{k}|>")
             tokens.append(name)
@@ -499,7 +513,10 @@ def hparams_metadata(spec: ModelSpec, n_vocab: int) -> Dict:
         md[f"{a}.expert_used_count"] = spec.n_expert_used
     if a == "qwen2":  # (Qwen2 files carry no rope.dimension_count: head_dim = n_embd / n_head)
         del md[f"{a}.rope.dimension_count"]
-    if a == ARCH_QWEN3:  # the head width is a key of its own, for keys and for values
+    if a == ARCH_QWEN3MOE:  # the experts' width under its own key; feed_forward_length is the dense size
+        md[f"{a}.{KEY_EXPERT_FF_LENGTH}"] = spec.n_ff
+        md[f"{a}.feed_forward_length"] = 8 * spec.n_ff
+    if a in (ARCH_QWEN3, ARCH_QWEN3MOE):  # the head width is a key of its own, for keys and for values
         del md[f"{a}.rope.dimension_count"]
         md[f"{a}.{KEY_ATTN_KEY_LENGTH}"] = spec.head_dim
         md[f"{a}.{KEY_ATTN_VALUE_LENGTH}"] = spec.head_dim
@@ -554,6 +571,11 @@ def write_synthetic_gguf(spec, path: str, seed: int = 0, log=None, extra_metadat
             data = (1.0 + 0.5 * rng.standard_normal(n)).astype(np.float32)
         elif name.endswith("norm.weight"):
             data = (1.0 + 0.1 * rng.standard_normal(n)).astype(np.float32)
+        elif name.endswith("ffn_gate_inp.weight") and spec.router_levels > 1:
+            W = np.zeros((spec.n_expert, spec.n_embd), np.float32)   # (ModelSpec.router_levels)
+            rank = rng.permutation(spec.n_expert)
+            W[:, rng.integers(spec.n_embd)] = 4.0 * np.where(rank % 2, -1.0, 1.0) * spec.router_levels ** -(rank // 2)
+            data = W.reshape(-1)
         elif name.endswith(".bias"):
             # four times the standard deviation of the projection's own output on a normed input
             # (weight_std * sqrt(d)): real Qwen2 biases are large, and a dropped one must show

@@ -32,7 +32,7 @@ from typing import Dict, List, Optional
 import numpy as np
 
 from ..gguf.constants import (ARCH_QWEN3, ARCH_QWEN3MOE, ARCHITECTURES, KEY_ATTN_KEY_LENGTH, KEY_ATTN_VALUE_LENGTH,
-                              KEY_ROPE_SCALING_TYPE, TENSOR_ATTN_K_NORM, TENSOR_ATTN_Q_NORM)
+                              KEY_EXPERT_FF_LENGTH, KEY_ROPE_SCALING_TYPE, TENSOR_ATTN_K_NORM, TENSOR_ATTN_Q_NORM)
 
 
 @dataclass
@@ -66,19 +66,21 @@ class LlamaHParams:
     @classmethod
     def from_metadata(cls, md: Dict) -> "LlamaHParams":
         arch = md.get("general.architecture", "llama")
-        if arch == ARCH_QWEN3MOE:
-            raise NotImplementedError(f"architecture {arch!r} is not supported (the Qwen3 MoE models are not served)")
         if arch not in ARCHITECTURES:
             raise NotImplementedError(f"architecture {arch!r} is not supported")
         g = lambda k, d=None: md.get(f"{arch}.{k}", d)
-        if arch in ("qwen2", ARCH_QWEN3) and g(KEY_ROPE_SCALING_TYPE, "none") not in (None, "none"):
+        if arch == ARCH_QWEN3MOE and not int(g("expert_count", 0) or 0):
+            raise NotImplementedError(f"architecture {arch!r} without {arch}.expert_count is not supported "
+                                      "(the dense models are qwen3)")
+        qwen3 = arch in (ARCH_QWEN3, ARCH_QWEN3MOE)   # qwen3moe: Qwen3's attention over the Mixtral expert tensors
+        if (arch == "qwen2" or qwen3) and g(KEY_ROPE_SCALING_TYPE, "none") not in (None, "none"):
             raise NotImplementedError(f"{arch}.{KEY_ROPE_SCALING_TYPE} = {g(KEY_ROPE_SCALING_TYPE)!r}: RoPE scaling "
                                       "is not supported")
         n_embd = int(g("embedding_length"))
         n_head = int(g("attention.head_count"))
         n_vocab = int(g("vocab_size", 0) or len(md.get("tokenizer.ggml.tokens", [])))
         head_dim = int(g("rope.dimension_count", n_embd // n_head))
-        if arch == ARCH_QWEN3:
+        if qwen3:
             head_dim = int(g(KEY_ATTN_KEY_LENGTH, head_dim))
             if int(g(KEY_ATTN_VALUE_LENGTH, head_dim)) != head_dim:
                 raise NotImplementedError(f"{arch}.{KEY_ATTN_VALUE_LENGTH} differs from {arch}.{KEY_ATTN_KEY_LENGTH}")
@@ -87,12 +89,14 @@ class LlamaHParams:
         return cls(n_vocab=n_vocab, n_embd=n_embd, n_layer=int(g("block_count")), n_head=n_head,
                    n_head_kv=int(g("attention.head_count_kv", n_head)),
                    head_dim=head_dim,
-                   n_ff=int(g("feed_forward_length")), n_expert=int(g("expert_count", 0) or 0),
+                   # (qwen3moe: the experts' width has its own key; 0: the loaders take the tensor's shape)
+                   n_ff=int(g(KEY_EXPERT_FF_LENGTH, 0) or 0) if arch == ARCH_QWEN3MOE else int(g("feed_forward_length")),
+                   n_expert=int(g("expert_count", 0) or 0),
                    n_expert_used=int(g("expert_used_count", 0) or 0),
                    rope_base=float(g("rope.freq_base", 10000.0)),
                    rms_eps=float(g("attention.layer_norm_rms_epsilon", 1e-5)),
                    n_ctx_train=int(g("context_length", 2048)), arch=arch,
-                   rope_neox=arch in ("qwen2", ARCH_QWEN3),
+                   rope_neox=arch == "qwen2" or qwen3,
                    pooling_type=int(g("pooling_type", -1)))
 
 
@@ -143,6 +147,8 @@ class ReferenceLlama:
         hp = self.hp
         if not hp.n_vocab:
             hp.n_vocab = reader.tensors["token_embd.weight"].shape[1]
+        if not hp.n_ff and hp.n_expert:   # (qwen3moe without expert_feed_forward_length)
+            hp.n_ff = int(reader.tensors["blk.0.ffn_gate_exps.weight"].shape[1])
         if rope_neox is not None:
             hp.rope_neox = bool(rope_neox)
         self.n_ctx = n_ctx

@@ -191,5 +191,79 @@ def attention_prefill(q, k_cache, v_cache, pos0: int, scale: Optional[float] = N
     return out
 
 
+def _ws(nbytes, device):
+    import torch
+    return torch.zeros((nbytes + 3) // 4, device=device, dtype=torch.int32)
+
+
+def moe_router_wide(x, norm, W, k: int, eps: float = 1e-5):
+    """Rows x [B, d] -> RMSNorm * norm -> F32 router W [E, d] (17 <= E <= 256) -> softmax, top-k (lowest
+    id on a tie), renormalised. Returns (ids [B, k] int32, weights [B, k], logits [B, E])."""
+    import torch
+    B, d = map(int, x.shape)
+    E = int(W.shape[0])
+    hip = _hip()
+    if not hip.moe_router_wide_ok(0, E, k, d):
+        raise ValueError("moe_router_wide: 17 <= E <= 256, k <= 16, d a multiple of 4 up to 15360")
+    xp, npp, wp = _check(x, torch.float32, (B, d), "x"), _check(norm, torch.float32, (d,), "norm"), \
+        _check(W, torch.float32, (E, d), "W")
+    ids = torch.empty(B, k, device=x.device, dtype=torch.int32)
+    w = torch.empty(B, k, device=x.device, dtype=torch.float32)
+    logits = torch.empty(B, E, device=x.device, dtype=torch.float32)
+    ws = _ws(hip.moe_router_wide_workspace(B, E), x.device)
+    hip.moe_router_wide(xp, d, B, npp, eps, wp, d, E, k, ws.data_ptr(), logits.data_ptr(), ids.data_ptr(), w.data_ptr(),
+                        _stream())
+    return ids, w, logits
+
+
+def moe_route_group_wide(E: int, k: int, logits=None, sel=None, selw=None):
+    """Per-expert row lists (ascending token order) and the grouped GEMM's work list, from router
+    logits [T, E] or from picks sel / selw [T, k]. Returns a dict of sel, selw, cnt_off [E + 1], tok,
+    gw, pos [T k], items [bound, 3] = (expert, first row, rows), n_items [1]."""
+    import torch
+    hip = _hip()
+    if (logits is None) == (sel is None) or not 1 <= k <= min(16, E) or E > 256:
+        raise ValueError("moe_route_group_wide: logits or sel / selw; E <= 256, k <= 16")
+    if logits is not None:
+        T, dev = int(logits.shape[0]), logits.device
+        lp = _check(logits, torch.float32, (T, E), "logits")
+        sel = torch.empty(T, k, device=dev, dtype=torch.int32)
+        selw = torch.empty(T, k, device=dev, dtype=torch.float32)
+    else:
+        T, dev, lp = int(sel.shape[0]), sel.device, 0
+        if int(sel.min()) < 0 or int(sel.max()) >= E:
+            raise ValueError("expert id out of range")
+    sp, swp = _check(sel, torch.int32, (T, k), "sel"), _check(selw, torch.float32, (T, k), "selw")
+    i32 = lambda n: torch.empty(n, device=dev, dtype=torch.int32)
+    o = dict(sel=sel, selw=selw, cnt_off=i32(E + 1), tok=i32(T * k), gw=torch.empty(T * k, device=dev), pos=i32(T * k),
+             items=torch.empty(hip.moe_group_wide_items(T, E, k), 3, device=dev, dtype=torch.int32), n_items=i32(1))
+    ws = _ws(hip.moe_group_wide_workspace(T, E), dev)
+    hip.moe_route_group_wide(lp, T, E, k, sp, swp, o["cnt_off"].data_ptr(), o["tok"].data_ptr(), o["gw"].data_ptr(),
+                             o["pos"].data_ptr(), o["items"].data_ptr(), o["n_items"].data_ptr(), ws.data_ptr(), _stream())
+    return o
+
+
+def moe_gemm_grouped(w_t16, qtype: int, d: int, F: int, E: int, x, routing, swiglu: bool):
+    """One projection of every routed expert in one launch over ``routing`` (moe_route_group_wide's dict).
+    swiglu: w_t16 = the experts' SwiGLU tile16 copies back to back, x f16 [T k, d] -> f16 [T k, F];
+    else: w_t16 = the down experts concatenated along K, x f16 [T k, F] -> f32 [T k, d]. Rows in gathered
+    order, f16 in the batched kernels' 4-group k order."""
+    import torch
+    hip = _hip()
+    R, Kin, n_out = int(routing["tok"].numel()), (d if swiglu else F), (F if swiglu else d)
+    xp = _check(x, torch.float16, (R, Kin), "x")
+    rows = 2 * F if swiglu else d
+    if not hip.moe_gemm_grouped_ok(int(qtype), rows, Kin):
+        raise ValueError("moe_gemm_grouped: a tile16 weight type, K a multiple of 256, rows a multiple of 16")
+    need = E * hip.t16_bytes(int(qtype), rows, Kin)
+    if _check(w_t16, torch.uint8, None, "w_t16") == 0 or w_t16.numel() != need:
+        raise ValueError(f"w_t16 must hold {need} bytes")
+    out = torch.empty(R, n_out, device=x.device, dtype=torch.float16 if swiglu else torch.float32)
+    hip.moe_gemm_grouped(w_t16.data_ptr(), int(qtype), d, F, E, xp, out.data_ptr(), bool(swiglu),
+                         routing["items"].data_ptr(), routing["n_items"].data_ptr(), int(routing["items"].shape[0]),
+                         _stream())
+    return out
+
+
 __all__ = ["QuantMatrix", "gemv", "gemv_swiglu", "gemm", "rmsnorm_bf16", "embed", "attention_decode",
-           "attention_prefill"]
+           "attention_prefill", "moe_router_wide", "moe_route_group_wide", "moe_gemm_grouped"]
