@@ -371,6 +371,8 @@ PYBIND11_MODULE(_cpu, m) {
     return cpu_sample(l, window, parse_sampling(sp), step);
   });
   m.def("uniform", &splitmix_uniform);
+  // the loaders' refusal of MoE expert tensors of a type without expert kernels (common.h)
+  m.def("check_expert_type", &check_expert_type);
 
   // the load-time planar repack (runtime/repack.cpp), as the HIP module exposes it (tests)
   m.def("repack", [](int type, py::array_t<uint8_t, py::array::c_style> src, size_t K_src, size_t r0, size_t R,

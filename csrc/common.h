@@ -34,7 +34,7 @@
 //           fields as they stand: f16 d | u16 scales_h | u8 scales_l[4], one aligned 8-byte load
 //           per superblock; sub-block ib has the 6-bit scale ls = low nibble ib of scales_l |
 //           bit pair ib of scales_h << 4 and the weight is d * (ls - 32) * codebook[nibble].)
-//   F16 / F32 : [R][K] unchanged
+//   F16 / BF16 / F32 : [R][K] unchanged
 //
 // Total bytes are identical to the GGUF tensor (no padding), so 4.6 GB of
 // Llama-3-8B Q4_K_M weights stay 4.6 GB on HBM.
@@ -111,7 +111,7 @@ constexpr TypeLayout type_layout(int t) {
   X(T_Q4_K, __VA_ARGS__) X(T_Q5_K, __VA_ARGS__) X(T_Q6_K, __VA_ARGS__) X(T_Q8_0, __VA_ARGS__)                \
   X(T_Q4_0, __VA_ARGS__) X(T_Q4_1, __VA_ARGS__) X(T_Q5_0, __VA_ARGS__) X(T_Q5_1, __VA_ARGS__)                \
   X(T_Q2_K, __VA_ARGS__) X(T_Q3_K, __VA_ARGS__) X(T_IQ4_NL, __VA_ARGS__) X(T_IQ4_XS, __VA_ARGS__)            \
-  X(T_F16, __VA_ARGS__) X(T_F32, __VA_ARGS__)
+  X(T_F16, __VA_ARGS__) X(T_BF16, __VA_ARGS__) X(T_F32, __VA_ARGS__)
 // the GEMV instantiations of kernels/gemv.hip itself ...
 #define LFK_TYPES_GEMV_MAIN(X, ...)                                                                           \
   X(T_Q4_K, __VA_ARGS__) X(T_Q5_K, __VA_ARGS__) X(T_Q6_K, __VA_ARGS__) X(T_Q8_0, __VA_ARGS__)                \
@@ -120,6 +120,8 @@ constexpr TypeLayout type_layout(int t) {
 #define LFK_TYPES_GEMV_LEGACY(X, ...)                                                                         \
   X(T_Q4_0, __VA_ARGS__) X(T_Q4_1, __VA_ARGS__) X(T_Q5_0, __VA_ARGS__) X(T_Q5_1, __VA_ARGS__)                \
   X(T_Q2_K, __VA_ARGS__) X(T_Q3_K, __VA_ARGS__) X(T_IQ4_NL, __VA_ARGS__) X(T_IQ4_XS, __VA_ARGS__)
+// ... and the unquantised BF16 of kernels/gemv_bf16.hip (a third one: fp32 activations, its own flags)
+#define LFK_TYPES_GEMV_BF16(X, ...) X(T_BF16, __VA_ARGS__)
 // MoE expert tensors (the down GEMV's types)
 #define LFK_TYPES_MOE(X, ...)                                                                                 \
   X(T_Q4_K, __VA_ARGS__) X(T_Q5_K, __VA_ARGS__) X(T_Q6_K, __VA_ARGS__) X(T_Q8_0, __VA_ARGS__)                \
@@ -167,7 +169,7 @@ constexpr int8_t kIQ4Values[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 
 
 // MoE expert tensors of the kernel types outside LFK_TYPES_MOE are not supported (attention, router
 // and embeddings of such a file are): refuse the model at load, naming the tensor. These are the
-// legacy 32-weight block types, the 2- and 3-bit K-quants Q2_K and Q3_K, and IQ4_NL and IQ4_XS.
+// legacy 32-weight block types, the 2- and 3-bit K-quants Q2_K and Q3_K, IQ4_NL and IQ4_XS, and BF16.
 inline void check_expert_type(const std::string& tensor, int t) {
   if (!LFK_TYPE_IN(LFK_TYPES_KERNEL, t) || LFK_TYPE_IN(LFK_TYPES_MOE, t)) return;
   throw std::runtime_error("unsupported expert tensor " + tensor + ": type " + type_layout(t).name +

@@ -251,12 +251,19 @@ static void launch_gemm(const GemmArgs& a, int epi, hipStream_t s) {
   } else launch_gemm_t<QT, 64, 128>(a, epi, s);
 }
 
+// BF16 weights are MFMA operands as they stand: gemm_w16.hip's kernel, no decode
+template <int QT>
+static void launch_gemm_any(const GemmArgs& a, int epi, hipStream_t s) {
+  if constexpr (QT == T_BF16) gemm_bf16w(a, epi, s);
+  else launch_gemm<QT>(a, epi, s);
+}
+
 void gemm_dq(const GemmArgs& a, int epi, hipStream_t s) {
   if (a.T <= 0) return;
   if (a.w.K % BK) throw std::runtime_error("gemm_dq: K must be a multiple of 64");
   if (epi == GEMM_SWIGLU && (a.w.rows % 64)) throw std::runtime_error("gemm_dq: swiglu needs 64-row groups");
   LFK_DISPATCH(LFK_TYPES_KERNEL, a.w.type, throw std::runtime_error("gemm_dq: unsupported weight type"),
-               launch_gemm<QT>(a, epi, s));
+               launch_gemm_any<QT>(a, epi, s));
 }
 
 }  // namespace lfk

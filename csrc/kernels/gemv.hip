@@ -121,7 +121,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const int bid, cons
   int n_done = 0;
   const int K = a.w.K;
   int8_t* xq = reinterpret_cast<int8_t*>(smem);
-  float* xd = reinterpret_cast<float*>(smem + K);
+  float* xd = reinterpret_cast<float*>(smem + gemv_xd_off(QT, K));
   float* red = xd + (K >> 5);
   const int wave = wave_id(), lane = threadIdx.x & 63;
   const int nchunks = K >> 5;
@@ -148,7 +148,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const int bid, cons
   RowPtr R[NR];
   int slot = 0, f0 = 0;
   WStream<QT, NR, U> ws;
-  XPrologue<NORM, BLOCK, WAIT> xp;
+  XPrologue<NORM, BLOCK, WAIT, gemv_xf(QT)> xp;
   int kp = 0;
   if constexpr (WAIT) {
     // the weights stream while the producer (the attention planes of this launch) finishes
@@ -398,25 +398,29 @@ static int pow2_floor(int v) {
   while (p * 2 <= v) p *= 2;
   return p;
 }
+// rows x passes a lane may hold of the unquantised types (the quantised ones: up to 8, pick_cfg)
+constexpr int gemv_raw_budget(int qt) { return qt == T_BF16 ? 2 : (qt == T_F32 || qt == T_F16) ? 4 : 8; }
 static GemvCfg pick_cfg(int qt, int rows, int nchunks, int min_nr) {
-  const int LB = (qt == T_F32) ? 2 : ((qt == T_F16 || nchunks > 128) ? 4 : 8);
+  const int LB = (qt == T_F32) ? 2 : ((qt == T_F16 || qt == T_BF16 || nchunks > 128) ? 4 : 8);
   // measured on MI355X with weights streamed from HBM (tools/gemv_sweep.sh):
   //   K > 4096 (FFN down)         : one row per wave, 4 passes (Q6_K: 2) in flight
   //   >= 16384 rows (gate/up, head): 4 rows per wave, 1 pass
-  if (qt == T_Q3_K) {
+  if (qt == T_Q3_K || qt == T_BF16) {
     // a Q3_K chunk holds 12 raw dwords (quants, hmask, packed scales): only NR * U <= 2 stays
-    // under 128 VGPRs (88-109; (4, 1) and (2, 2) spill to scratch in the 1024-thread blocks)
+    // under 128 VGPRs (88-109; (4, 1) and (2, 2) spill to scratch in the 1024-thread blocks).
+    // BF16 likewise: 16 raw dwords per chunk and row beside f32 x; NR * U = 4 spilled 34-168 VGPRs
+    // there, and two 64-byte rows per lane already keep 128 KiB per CU in flight.
     const int nr = (min_nr >= 2 || rows / 2 >= 2048) ? 2 : 1;
     return {nr, nr == 2 ? 1 : std::min(2, std::max(1, (nchunks + 63) / 64))};
   }
-  if (qt != T_F32 && qt != T_F16) {
+  if (qt != T_F32 && qt != T_F16 && qt != T_BF16) {
     if (nchunks > 128) {  // long rows run on 1024-thread blocks: NR * U <= 4 (128 VGPRs)
       const int nr = std::max(1, min_nr);
       return {nr, std::max(1, (qt == T_Q6_K ? 2 : 4) / nr)};
     }
     if (rows >= 16384) return {4, 1};
   }
-  int nr = (qt == T_F32 || qt == T_F16) ? 2 : 4;
+  int nr = (qt == T_F32 || qt == T_F16 || qt == T_BF16) ? 2 : 4;
   while (nr > min_nr && rows / nr < 2048) nr /= 2;
   const int passes = (nchunks + 63) / 64;
   int u = pow2_floor(std::max(1, std::min(LB / nr, passes)));
@@ -459,11 +463,11 @@ template <int QT, int EPI, int NR, int U>
 static void launch_gemv_cfg(const GemvArgs& a, hipStream_t s) {
   if constexpr (EPI == EPI_SWIGLU && NR < 2) {
     throw std::runtime_error("gemv: swiglu needs >= 2 rows per item");
-  } else if constexpr ((QT == T_F32 || QT == T_F16) && NR * U > 4) {
-    throw std::runtime_error("gemv: config exceeds the F16/F32 register budget");
+  } else if constexpr (NR * U > gemv_raw_budget(QT)) {
+    throw std::runtime_error("gemv: config exceeds the F16/BF16/F32 register budget");
   } else {
     constexpr int NF = (EPI == EPI_SWIGLU) ? NR / 2 : NR;
-    const size_t lds = a.w.K + (a.w.K / 32) * 4 + 128;
+    const size_t lds = gemv_lds(QT, a.w.K);
     const int items = (a.n_out + NF - 1) / NF * a.n_slots;
     // K > 4096 (FFN down, 70B): 1024-thread blocks so the x prologue is one batch
     // of loads per thread (issued before the weights) and 16 waves share its LDS
@@ -586,11 +590,17 @@ static void gemv_t(const GemvArgs& a, int epi, hipStream_t s) {
   }
 }
 
-#ifdef LFK_GEMV_LEGACY_TU
-// gemv_legacy.hip: the legacy 32-block types' instantiations, compiled beside the rest
-void gemv_legacy(const GemvArgs& a, int epi, hipStream_t s) {
-  LFK_DISPATCH(LFK_TYPES_GEMV_LEGACY, a.w.type, throw std::runtime_error("gemv: unsupported weight type"),
+#if defined(LFK_GEMV_BF16_TU)
+// gemv_bf16.hip: the last unit of the chain gemv -> gemv_legacy -> gemv_bf16
+void gemv_bf16(const GemvArgs& a, int epi, hipStream_t s) {
+  LFK_DISPATCH(LFK_TYPES_GEMV_BF16, a.w.type, throw std::runtime_error("gemv: unsupported weight type"),
                gemv_t<QT>(a, epi, s));
+}
+#elif defined(LFK_GEMV_LEGACY_TU)
+// gemv_legacy.hip: the legacy 32-block types' instantiations, compiled beside the rest
+void gemv_bf16(const GemvArgs& a, int epi, hipStream_t s);
+void gemv_legacy(const GemvArgs& a, int epi, hipStream_t s) {
+  LFK_DISPATCH(LFK_TYPES_GEMV_LEGACY, a.w.type, gemv_bf16(a, epi, s), gemv_t<QT>(a, epi, s));
 }
 #else
 void gemv_legacy(const GemvArgs& a, int epi, hipStream_t s);
@@ -665,7 +675,8 @@ __device__ __forceinline__ void qkv_item(const QkvLaunch& a, int s_lo, int s_hi,
 // instantiation in the same way.
 template <int QT, int NR, int U, int BLOCK, bool BIAS, bool RAW = false>
 __device__ __forceinline__ void qkv_run(const QkvLaunch& a, int s_lo, int s_hi, int blk, int nblk, int pos,
-                                        XPrologue<true, BLOCK>& xp, int8_t* xq, float* xd, float* red) {
+                                        XPrologue<true, BLOCK, false, gemv_xf(QT)>& xp, int8_t* xq, float* xd,
+                                        float* red) {
   const int wave = wave_id(), lane = threadIdx.x & 63;
   int total = 0;
   for (int i = s_lo; i < s_hi; ++i) total += a.seg[i].rows / NR;
@@ -751,14 +762,15 @@ template <int QT0, int NR0, int U0, int QT1, int NR1, int U1, bool TWO, int BLOC
 __global__ __launch_bounds__(BLOCK) void gemv_qkv_kernel(QkvLaunch a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int8_t* xq = reinterpret_cast<int8_t*>(smem);
-  float* xd = reinterpret_cast<float*>(smem + a.K);
+  static_assert(!TWO || (!gemv_xf(QT0) && !gemv_xf(QT1)), "two type runs share one q8 x prologue");
+  float* xd = reinterpret_cast<float*>(smem + gemv_xd_off(QT0, a.K));
   float* red = xd + (a.K >> 5);
   // the prologue's kernarg fields in one scalar batch (as gemv_body's)
   asm volatile("" ::"s"(a.x), "s"(a.norm_w), "s"(a.K), "s"(a.pos), "s"(a.nseg), "s"(a.g1), "s"(a.blocks0),
                "s"(a.seg[0].base), "s"(a.seg[1].base), "s"(a.seg[2].base), "s"(a.seg[0].rows), "s"(a.seg[1].rows),
                "s"(a.seg[2].rows), "s"(a.seg[0].P.s0), "s"(a.seg[1].P.s0), "s"(a.seg[2].P.s0));
   const int pos = *a.pos;
-  XPrologue<true, BLOCK> xp;   // QKV always follows the attention RMSNorm
+  XPrologue<true, BLOCK, false, gemv_xf(QT0)> xp;   // QKV always follows the attention RMSNorm
   xp.load(a.x, a.norm_w, a.K);
   if (a.raw_out) {  // (launch-uniform: the raw-sum form of a QK-norm model; gemv_qkv refuses biases with it)
     if (!TWO || (int)blockIdx.x < a.blocks0) {
@@ -791,11 +803,11 @@ static size_t qkv_lds(int K) { return K + (K / 32) * 4 + 128; }
 template <int QT>
 static void launch_qkv1(QkvLaunch L, int rows, hipStream_t s) {
   const GemvCfg c = pick_cfg(QT, rows, L.K >> 5, 2);
-  const size_t lds = qkv_lds(L.K);
+  const size_t lds = gemv_lds(QT, L.K);
   L.g1 = L.nseg;
   L.blocks0 = 0;
   LFK_NRU_DISPATCH(c.nr, c.u, ({
-    if constexpr (NR >= 2 && NR * U <= 4) {
+    if constexpr (NR >= 2 && NR * U <= 4 && NR * U <= gemv_raw_budget(QT)) {
       if (gemv_early(L.K > 4096 ? EC_QKV_LONG : EC_QKV)) {
         auto k = gemv_qkv_kernel<QT, NR, U, QT, NR, U, false, 1024>;
         const size_t l = std::max(lds, kOnePerCuLds);
@@ -803,7 +815,7 @@ static void launch_qkv1(QkvLaunch L, int rows, hipStream_t s) {
         return;
       }
     }
-    if constexpr (NR >= 2 && !((QT == T_F32 || QT == T_F16) && NR * U > 4)) {
+    if constexpr (NR >= 2 && NR * U <= gemv_raw_budget(QT)) {
       auto k = gemv_qkv_kernel<QT, NR, U, QT, NR, U, false>;
       hipLaunchKernelGGL(k, gemv_grid(k, lds, rows / NR), dim3(256), lds, s, L);
     } else {
@@ -812,10 +824,15 @@ static void launch_qkv1(QkvLaunch L, int rows, hipStream_t s) {
   }));
 }
 
-#ifdef LFK_GEMV_LEGACY_TU
-void gemv_qkv1_legacy(const QkvLaunch& L, int type, int rows, hipStream_t s) {
-  LFK_DISPATCH(LFK_TYPES_GEMV_LEGACY, type, throw std::runtime_error("gemv_qkv: unsupported type"),
+#if defined(LFK_GEMV_BF16_TU)
+void gemv_qkv1_bf16(const QkvLaunch& L, int type, int rows, hipStream_t s) {
+  LFK_DISPATCH(LFK_TYPES_GEMV_BF16, type, throw std::runtime_error("gemv_qkv: unsupported type"),
                launch_qkv1<QT>(L, rows, s));
+}
+#elif defined(LFK_GEMV_LEGACY_TU)
+void gemv_qkv1_bf16(const QkvLaunch& L, int type, int rows, hipStream_t s);
+void gemv_qkv1_legacy(const QkvLaunch& L, int type, int rows, hipStream_t s) {
+  LFK_DISPATCH(LFK_TYPES_GEMV_LEGACY, type, gemv_qkv1_bf16(L, type, rows, s), launch_qkv1<QT>(L, rows, s));
 }
 #else
 void gemv_qkv1_legacy(const QkvLaunch& L, int type, int rows, hipStream_t s);

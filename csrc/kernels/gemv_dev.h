@@ -9,6 +9,12 @@ namespace lfk {
 
 static constexpr int kMaxBlocks = 1024;  // 256 CUs x 4
 
+// LDS of a GEMV block: x as q8 + one f32 scale per 32 (BF16 weights: x as f32), then the norm's
+// per-wave sums. xd_off: where the scales (and after them the sums) start.
+__host__ __device__ constexpr bool gemv_xf(int qt) { return qt == T_BF16; }
+__host__ __device__ inline size_t gemv_xd_off(int qt, int K) { return gemv_xf(qt) ? (size_t)4 * K : (size_t)K; }
+inline size_t gemv_lds(int qt, int K) { return gemv_xd_off(qt, K) + (K / 32) * 4 + 128; }
+
 // Block prologue: x (or x * w_norm) -> per-32 int8 + f32 scale in LDS.
 //
 // Split in two so its global loads are issued BEFORE the wave's first weight
@@ -27,7 +33,9 @@ __device__ __forceinline__ float4 ld16f_sc1(const float* base, int i) {
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
 
-template <bool NORM, int BLOCK = 256, bool SC1 = false>
+// XF (BF16 weights): x (times the norm weight) goes to LDS as f32 in qdot.h's xf_slot order instead
+// of q8 + scales; xq is then the f32 area (4 K bytes) and xd is unused.
+template <bool NORM, int BLOCK = 256, bool SC1 = false, bool XF = false>
 struct XPrologue {
   static constexpr int NB = 4;
   static constexpr int SHIFT = (BLOCK == 1024) ? 12 : (BLOCK == 512 ? 11 : 10);  // log2(BLOCK * 4 floats per slot)
@@ -56,6 +64,10 @@ struct XPrologue {
         if constexpr (NORM) {
           ss += t.x * t.x + t.y * t.y + t.z * t.z + t.w * t.w;
           t.x *= w[b].x; t.y *= w[b].y; t.z *= w[b].z; t.w *= w[b].w;
+        }
+        if constexpr (XF) {
+          reinterpret_cast<float4*>(xq)[xf_slot(i >> 5, (i >> 2) & 7)] = t;
+          continue;
         }
         const float amax = max8(fmaxf(fmaxf(fabsf(t.x), fabsf(t.y)), fmaxf(fabsf(t.z), fabsf(t.w))));
         const float d = amax * (1.f / 127.f);
@@ -128,10 +140,22 @@ struct WStream {
     for (int u = 0; u < U; ++u) {
       const int c = c0 + 64 * u + lane;
       if (c < nchunks) {
-        XChunk X;
-        load_x<QT>(X, xq, xd, c);
+        if constexpr (QT == T_BF16) {
+          float s0[NR] = {}, s1[NR] = {};
 #pragma unroll
-        for (int r = 0; r < NR; ++r) acc[r] += wdot<QT>(w[u][r], X, c);
+          for (int i = 0; i < 4; ++i) {
+            const XQuarterF X = load_xf(reinterpret_cast<const float4*>(xq), c, i);
+#pragma unroll
+            for (int r = 0; r < NR; ++r) wdot_bf16(w[u][r].w[i], X, s0[r], s1[r]);
+          }
+#pragma unroll
+          for (int r = 0; r < NR; ++r) acc[r] += s0[r] + s1[r];
+        } else {
+          XChunk X;
+          load_x<QT>(X, xq, xd, c);
+#pragma unroll
+          for (int r = 0; r < NR; ++r) acc[r] += wdot<QT>(w[u][r], X, c);
+        }
       }
     }
   }

@@ -515,6 +515,9 @@ struct GemmArgs {
   bool out_zeroed = false;         // STORE: the caller already zeroed `out` (no memset for split-K)
 };
 void gemm_dq(const GemmArgs& a, int epi, hipStream_t s);
+// gemm_dq's contract for T_BF16 weights (gemm_dq routes them here; gemm_w16.hip): the weight bytes
+// reach the MFMA unchanged. No grouped (seg_dev) form.
+void gemm_bf16w(const GemmArgs& a, int epi, hipStream_t s);
 
 // Prefill GEMM on the tile16 weight copy (bmm.hip): Y[T][N] = X[T][K] . W^T with X f16 in bmm's
 // 4-group k order (rmsnorm_bf16(..., f16sw), attention prefill out_h, this kernel's SwiGLU

@@ -45,6 +45,9 @@ __device__ __forceinline__ unsigned pk_bf16_pair(float a, float b) {
 __device__ __forceinline__ float h2f(unsigned short h) {
   return __half2float(__ushort_as_half(h));
 }
+// the two bf16 of a dword, widened exactly (one shift / one mask each)
+__device__ __forceinline__ float bf16_lo(unsigned d) { return __uint_as_float(d << 16); }
+__device__ __forceinline__ float bf16_hi(unsigned d) { return __uint_as_float(d & 0xFFFF0000u); }
 
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
@@ -598,6 +601,7 @@ template <> struct WRaw<T_Q3_K> : K23Raw {};
 template <> struct WRaw<T_IQ4_NL> : IQ4Raw {};
 template <> struct WRaw<T_IQ4_XS> : IQ4Raw {};
 template <> struct WRaw<T_F16> { uint4 w[4]; };
+template <> struct WRaw<T_BF16> { int4 w[4]; };  // 32 bf16 weights, two per dword
 template <> struct WRaw<T_F32> { float4 w[8]; };
 
 // per-row plane pointers (wave-uniform -> SGPRs)
@@ -648,6 +652,9 @@ __device__ __forceinline__ void wload(WRaw<T>& w, const RowPtr& R, int c) {
   } else if constexpr (T == T_F16) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) w.w[i] = reinterpret_cast<const uint4*>(R.p0 + 64 * c)[i];
+  } else if constexpr (T == T_BF16) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w.w[i] = ld_nt16(R.p0 + 64 * c + 16 * i);
   } else {
 #pragma unroll
     for (int i = 0; i < 8; ++i) w.w[i] = reinterpret_cast<const float4*>(R.p0 + 128 * c)[i];
@@ -729,6 +736,32 @@ __device__ __forceinline__ float wdot(const WRaw<T>& w, const XChunk& X, int c) 
     }
     return s * X.dlo;
   }
+}
+
+// ---------------------------------------------------------------------------
+// BF16 weights multiply the fp32 activations themselves (no q8 pass: the weights are unquantised,
+// so the int8 rounding of x would be the launch's whole error). The prologue leaves x (times the
+// norm weight) in LDS as f32, chunk c = 32 floats = 8 float4, float4 q of chunk c at slot
+// q ^ (c & 7): lane l reads chunk l, so 8 neighbouring lanes' ds_read_b128 of one q cover all
+// banks instead of meeting in four of them (the chunks are 128 B apart).
+__device__ __forceinline__ int xf_slot(int c, int q) { return 8 * c + (q ^ (c & 7)); }
+
+// A chunk is consumed in quarters - 8 activations (two float4) against one 16-byte weight load of
+// every row of the item - so x takes 8 VGPRs beside the rows' raw weights, not the chunk's 32: a
+// whole f32 chunk pushed the 1024-thread forms (128 VGPRs) into scratch.
+struct XQuarterF {
+  float4 a, b;
+};
+__device__ __forceinline__ XQuarterF load_xf(const float4* xf, int c, int i) {
+  return {xf[xf_slot(c, 2 * i)], xf[xf_slot(c, 2 * i + 1)]};
+}
+// 8 bf16 weights . 8 f32 activations, onto two partial sums (even / odd weights of a dword)
+__device__ __forceinline__ void wdot_bf16(const int4& w, const XQuarterF& X, float& s0, float& s1) {
+  const unsigned d[4] = {(unsigned)w.x, (unsigned)w.y, (unsigned)w.z, (unsigned)w.w};
+  s0 = fmaf(bf16_lo(d[0]), X.a.x, s0); s1 = fmaf(bf16_hi(d[0]), X.a.y, s1);
+  s0 = fmaf(bf16_lo(d[1]), X.a.z, s0); s1 = fmaf(bf16_hi(d[1]), X.a.w, s1);
+  s0 = fmaf(bf16_lo(d[2]), X.b.x, s0); s1 = fmaf(bf16_hi(d[2]), X.b.y, s1);
+  s0 = fmaf(bf16_lo(d[3]), X.b.z, s0); s1 = fmaf(bf16_hi(d[3]), X.b.w, s1);
 }
 
 // Dequantise 32 CONTIGUOUS weights [32*q, 32*q+32) of `row` into out[32] (used by
@@ -814,7 +847,20 @@ __device__ __forceinline__ void dequant32(const uint8_t* __restrict__ base, cons
       float4 w = wp[i];
       out[4 * i] = w.x; out[4 * i + 1] = w.y; out[4 * i + 2] = w.z; out[4 * i + 3] = w.w;
     }
+  } else if constexpr (T == T_BF16) {  // exact: a bf16 is the high half of its f32
+    const uint4* wp = reinterpret_cast<const uint4*>(base + row * P.s0 + 64 * q);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint4 w = wp[i];
+      const unsigned d[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        out[8 * i + 2 * j] = bf16_lo(d[j]);
+        out[8 * i + 2 * j + 1] = bf16_hi(d[j]);
+      }
+    }
   } else {  // F16
+    static_assert(T == T_F16, "dequant32: unsupported type");
     const uint2* wp = reinterpret_cast<const uint2*>(base + row * P.s0 + 64 * q);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {

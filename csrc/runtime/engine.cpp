@@ -628,8 +628,8 @@ void Engine::setup_moe_wide() {
 void Engine::setup_scoring() {
   if (!opt_.scoring || tp_on_ || !has_head() || opt_.layer_begin > 0) return;  // (score() refuses those engines)
   if (!output_.base || !bmm_supported(output_.type, output_.K))
-    throw std::runtime_error("scoring: the output head (type " + std::to_string(output_.type) + ", K " +
-                             std::to_string(output_.K) + ") has no tile16 form (a tile16 type, K a multiple of 256)");
+    throw std::runtime_error(std::string("scoring: the output head output.weight (type ") + type_layout(output_.type).name +
+                             ", K " + std::to_string(output_.K) + ") has no tile16 form (a tile16 type, K a multiple of 256)");
   if (hp_.n_vocab >= (1 << 24)) throw std::runtime_error("scoring: vocabulary ids must stay below 2^24");
   if (!t_output_.base || t_output_.base == output_.base) {  // one KV slot, or a model the batched path does not serve
     t_output_ = output_;

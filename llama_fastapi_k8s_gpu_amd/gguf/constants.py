@@ -85,6 +85,7 @@ FTYPE_MOSTLY_Q5_K_M = 17
 FTYPE_MOSTLY_Q6_K = 18
 FTYPE_MOSTLY_IQ4_NL = 25
 FTYPE_MOSTLY_IQ4_XS = 30
+FTYPE_MOSTLY_BF16 = 32
 
 # general.architecture values the engines serve, and the ones refused by name
 ARCHITECTURES = ("llama", "mistral", "mixtral", "qwen2", "qwen3", "qwen3moe")

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .constants import (FTYPE_MOSTLY_IQ4_NL, FTYPE_MOSTLY_IQ4_XS, FTYPE_MOSTLY_Q2_K, FTYPE_MOSTLY_Q3_K_M, FTYPE_MOSTLY_Q3_K_S, FTYPE_MOSTLY_Q4_0,
+from .constants import (FTYPE_MOSTLY_BF16, FTYPE_MOSTLY_F16, FTYPE_MOSTLY_IQ4_NL, FTYPE_MOSTLY_IQ4_XS, FTYPE_MOSTLY_Q2_K, FTYPE_MOSTLY_Q3_K_M, FTYPE_MOSTLY_Q3_K_S, FTYPE_MOSTLY_Q4_0,
                         FTYPE_MOSTLY_Q4_1, FTYPE_MOSTLY_Q4_K_M, FTYPE_MOSTLY_Q5_0, FTYPE_MOSTLY_Q5_1, FTYPE_MOSTLY_Q8_0, GGMLType, GGUFValueType,
                         TOKEN_TYPE_BYTE, TOKEN_TYPE_CONTROL, TOKEN_TYPE_NORMAL)
 from .constants import ARCH_QWEN3, ARCH_QWEN3MOE, KEY_EXPERT_FF_LENGTH, KEY_ATTN_KEY_LENGTH, KEY_ATTN_VALUE_LENGTH, TENSOR_ATTN_K_NORM, TENSOR_ATTN_Q_NORM
@@ -78,7 +78,7 @@ class ModelSpec:
     rope_base: float
     tokenizer: str            # "bpe" | "spm"
     quant: str                # "q4_k_m" | "q8_0" | "f32" | "mixed-test" | LEGACY_QUANTS | "legacy-mixed-test"
-    #                           | K23_QUANTS | "kmixed-test" | IQ4_QUANTS | "iq4-mixed-test"
+    #                           | K23_QUANTS | "kmixed-test" | IQ4_QUANTS | "iq4-mixed-test" | FLOAT16_QUANTS
     n_expert: int = 0
     n_expert_used: int = 0
     n_ctx_train: int = 8192
@@ -124,6 +124,12 @@ K23_QUANTS = {
 IQ4_QUANTS = {
     "iq4_nl": (GGMLType.IQ4_NL, FTYPE_MOSTLY_IQ4_NL),
     "iq4_xs": (GGMLType.IQ4_XS, FTYPE_MOSTLY_IQ4_XS),
+}
+
+# the unquantised 16-bit file types (every matrix, token_embd and output.weight included)
+FLOAT16_QUANTS = {
+    "f16": (GGMLType.F16, FTYPE_MOSTLY_F16),
+    "bf16": (GGMLType.BF16, FTYPE_MOSTLY_BF16),
 }
 
 SPECS: Dict[str, ModelSpec] = {
@@ -282,6 +288,15 @@ SPECS.update({
 })
 
 
+# unquantised BF16 (what convert_hf_to_gguf writes by default) and the F16 twin of the 8B shape it is timed against
+SPECS.update({
+    "tiny-llama-bf16": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama-bf16", quant="bf16"),
+    "tiny-qwen3-bf16": replace(SPECS["tiny-qwen3-g2-hd128"], name="tiny-qwen3-bf16", quant="bf16"),
+    "llama3-8b-bf16": replace(SPECS["llama3-8b-q4_k_m"], name="Llama-3-8B-BF16", quant="bf16"),
+    "llama3-8b-f16": replace(SPECS["llama3-8b-q4_k_m"], name="Llama-3-8B-F16", quant="f16"),
+})
+
+
 def use_more_bits(i: int, n: int) -> bool:
     return i < n // 8 or i >= 7 * n // 8 or (i - n // 8) % 3 == 2
 
@@ -347,8 +362,8 @@ def tensor_types(spec: ModelSpec, layer: int) -> Dict[str, GGMLType]:
     if q == "f32":
         t = GGMLType.F32
         return {k: t for k in ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")}
-    if q in LEGACY_QUANTS:
-        t = LEGACY_QUANTS[q][0]
+    if q in LEGACY_QUANTS or q in FLOAT16_QUANTS:
+        t = (LEGACY_QUANTS.get(q) or FLOAT16_QUANTS[q])[0]
         return {k: t for k in ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_up", "ffn_down")}
     if q == "legacy-mixed-test":  # the four legacy formats and Q8_0 in one model
         cyc = [GGMLType.Q4_0, GGMLType.Q4_1, GGMLType.Q5_0, GGMLType.Q5_1, GGMLType.Q8_0]
@@ -444,6 +459,8 @@ def tensor_plan(spec: ModelSpec, n_vocab: int) -> List[Tuple[str, GGMLType, Tupl
         emb_t, out_t = GGMLType.Q8_0, GGMLType.Q8_0
     elif spec.quant == "f32":
         emb_t, out_t = GGMLType.F32, GGMLType.F32
+    elif spec.quant in FLOAT16_QUANTS:
+        emb_t = out_t = FLOAT16_QUANTS[spec.quant][0]
     elif spec.quant in LEGACY_QUANTS:
         emb_t, out_t = LEGACY_QUANTS[spec.quant][0], GGMLType.Q6_K
     elif spec.quant == "legacy-mixed-test":
@@ -498,6 +515,8 @@ def hparams_metadata(spec: ModelSpec, n_vocab: int) -> Dict:
         ftype = K23_QUANTS[spec.quant][1]
     elif spec.quant in IQ4_QUANTS:
         ftype = IQ4_QUANTS[spec.quant][1]
+    elif spec.quant in FLOAT16_QUANTS:
+        ftype = FLOAT16_QUANTS[spec.quant][1]
     else:
         ftype = FTYPE_MOSTLY_Q8_0 if spec.quant == "q8_0" else FTYPE_MOSTLY_Q4_K_M
     md = {"general.architecture": a, "general.name": spec.name + " (synthetic random-init)",
