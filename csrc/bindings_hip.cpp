@@ -838,6 +838,22 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("w"), py::arg("type"), py::arg("rows"), py::arg("K"), py::arg("V"), py::arg("x"), py::arg("T"),
      py::arg("target"), py::arg("targets"), py::arg("part"), py::arg("part_words"), py::arg("rec"), py::arg("stream"),
      py::arg("gpr") = 0);
+  // the same over a row-major BF16 / F16 head (score_head_w16): `w` is the planar [rows][K] matrix as
+  // uploaded, rows = V; `x` rows of the head's element type in plain k order
+  m.def("score_head_w16_workspace_words", &score_head_w16_workspace_words, py::arg("T"), py::arg("V"), py::arg("gpr") = 0);
+  m.def("score_head_w16", [](uintptr_t w, int type, int rows, int K, int V, uintptr_t x, int T, uintptr_t target,
+                             const std::vector<int>& targets, uintptr_t part, size_t part_words, uintptr_t rec,
+                             uintptr_t stream, int gpr) {
+    if ((int)targets.size() != T) throw std::runtime_error("score_head_w16: one target per row");
+    if (rows != V) throw std::runtime_error("score_head_w16: rows = V");
+    QMat q;  // (make_qmat refuses nothing here: the type is checked by score_head_w16 itself)
+    q.base = P<uint8_t>(w); q.type = type; q.rows = rows; q.K = K;
+    score_head_w16(score_head_w16_args(q, P<void>(x), T, P<int>(target), targets.data(), P<float>(part), part_words,
+                                       P<float>(rec), gpr), S(stream));
+    hip_ok("score_head_w16");
+  }, py::arg("w"), py::arg("type"), py::arg("rows"), py::arg("K"), py::arg("V"), py::arg("x"), py::arg("T"),
+     py::arg("target"), py::arg("targets"), py::arg("part"), py::arg("part_words"), py::arg("rec"), py::arg("stream"),
+     py::arg("gpr") = 0);
 
   m.def("attn_decode", [](uintptr_t q, uintptr_t kc, uintptr_t vc, uintptr_t pos, int n_ctx, int n_head, int n_kv,
                           int hd, float scale, uintptr_t part, uintptr_t out, uintptr_t stream, uintptr_t counters,

@@ -586,6 +586,21 @@ inline ScoreHeadArgs score_head_args(const QMat& t16, int V, const __half* x, in
 size_t score_head_workspace_words(int T, int V, int gpr = 0);
 // validates every bound on the host and throws before anything is queued
 void score_head(const ScoreHeadArgs& a, hipStream_t s);
+// The same contract on a row-major BF16 / F16 head as uploaded (score_w16.hip): a.w = the planar
+// [V][K] matrix (rows = V exactly, K a multiple of 64, no copy), a.x = [T][K] rows of the head's own
+// element type in plain k order (rmsnorm_bf16 / rmsnorm_f16). The weight bytes reach
+// v_mfma_f32_32x32x16_{bf16,f16} unchanged; groups are 128 rows. Records, partials and stage 2 are
+// score_head's.
+inline ScoreHeadArgs score_head_w16_args(const QMat& w, const void* x, int T, const int* target, const int* h_target,
+                                         float* part, size_t part_words, float* rec, int gpr = 0) {
+  ScoreHeadArgs a;
+  a.w = w; a.V = w.rows;
+  a.x = static_cast<const __half*>(x); a.T = T; a.target = target; a.h_target = h_target;
+  a.part = part; a.part_words = part_words; a.rec = rec; a.gpr = gpr;
+  return a;
+}
+size_t score_head_w16_workspace_words(int T, int V, int gpr = 0);
+void score_head_w16(const ScoreHeadArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- MoE prefill (grouped experts)
 // Device-side routing: per-expert row lists in ascending token order (moe.hip).
@@ -652,6 +667,8 @@ void embed_rows(const QMat& emb, const int* tokens, int T, float* x, hipStream_t
 // f16sw: write y as f16 in bmm's 4-group k order instead (gemm_t16's input; same 2-byte rows)
 void rmsnorm_bf16(const float* x, const float* w, float eps, int T, int d, __hip_bfloat16* y, hipStream_t s,
                   float* zero = nullptr, int zero_ld = 0, bool f16sw = false);
+// the same norm as f16 rows in plain k order (score_head_w16 on an F16 head)
+void rmsnorm_f16(const float* x, const float* w, float eps, int T, int d, __half* y, hipStream_t s);
 // f32 activation [T][d] -> bf16 (for the next GEMM)
 void to_bf16(const float* x, int n, __hip_bfloat16* y, hipStream_t s);
 // prefill: rope q/k of QKV rows, write q (f32) and k/v to the caches at pos0+t.

@@ -42,7 +42,8 @@ void embed_rows(const QMat& emb, const int* tokens, int T, float* x, hipStream_t
   hipLaunchKernelGGL(embed_kernel, dim3(T), dim3(128), 0, s, emb, tokens, T, x, zero, zero ? zero_n : 0);
 }
 
-template <bool F16SW>
+// FORM 0: bf16 rows; 1: f16 rows in bmm's 4-group k order; 2: f16 rows in plain k order
+template <int FORM>
 __global__ __launch_bounds__(256) void rmsnorm_bf16_kernel(const float* x, const float* w, float eps, int d,
                                                           __hip_bfloat16* y, float* zero, int zero_ld) {
   const int t = blockIdx.x, tid = threadIdx.x;
@@ -64,7 +65,12 @@ __global__ __launch_bounds__(256) void rmsnorm_bf16_kernel(const float* x, const
   for (int i = tid * 4; i < d; i += 1024) {
     float4 v = *reinterpret_cast<const float4*>(xr + i);
     float4 g = *reinterpret_cast<const float4*>(w + i);
-    if constexpr (F16SW) {  // 4-group order (0, 2, 1, 3): the pairs (0, 2) and (1, 3)
+    if constexpr (FORM == 2) {
+      const __half2 p0 = __floats2half2_rn(v.x * sc * g.x, v.y * sc * g.y);
+      const __half2 p1 = __floats2half2_rn(v.z * sc * g.z, v.w * sc * g.w);
+      *reinterpret_cast<uint2*>(y + (size_t)t * d + i) =
+          make_uint2(__builtin_bit_cast(unsigned, p0), __builtin_bit_cast(unsigned, p1));
+    } else if constexpr (FORM == 1) {  // 4-group order (0, 2, 1, 3): the pairs (0, 2) and (1, 3)
       const __half2 p0 = __floats2half2_rn(v.x * sc * g.x, v.z * sc * g.z);
       const __half2 p1 = __floats2half2_rn(v.y * sc * g.y, v.w * sc * g.w);
       *reinterpret_cast<uint2*>(y + (size_t)t * d + i) =
@@ -81,8 +87,14 @@ void rmsnorm_bf16(const float* x, const float* w, float eps, int T, int d, __hip
   if (T <= 0) return;
   if (zero && (zero_ld % 4 || reinterpret_cast<uintptr_t>(zero) % 16))
     throw std::runtime_error("rmsnorm_bf16: zeroed rows must be float4 aligned");
-  if (f16sw) hipLaunchKernelGGL(rmsnorm_bf16_kernel<true>, dim3(T), dim3(256), 0, s, x, w, eps, d, y, zero, zero_ld);
-  else hipLaunchKernelGGL(rmsnorm_bf16_kernel<false>, dim3(T), dim3(256), 0, s, x, w, eps, d, y, zero, zero_ld);
+  if (f16sw) hipLaunchKernelGGL(rmsnorm_bf16_kernel<1>, dim3(T), dim3(256), 0, s, x, w, eps, d, y, zero, zero_ld);
+  else hipLaunchKernelGGL(rmsnorm_bf16_kernel<0>, dim3(T), dim3(256), 0, s, x, w, eps, d, y, zero, zero_ld);
+}
+
+void rmsnorm_f16(const float* x, const float* w, float eps, int T, int d, __half* y, hipStream_t s) {
+  if (T <= 0) return;
+  hipLaunchKernelGGL(rmsnorm_bf16_kernel<2>, dim3(T), dim3(256), 0, s, x, w, eps, d,
+                     reinterpret_cast<__hip_bfloat16*>(y), nullptr, 0);
 }
 
 __global__ void to_bf16_kernel(const float* x, int n, __hip_bfloat16* y) {

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <stdexcept>
 
+#include "score_dev.h"
 #include "t16_dev.h"
 
 namespace lfk {
@@ -18,29 +19,8 @@ namespace lfk {
 // (the X buffers are free then); thread t < TM carries token t's running (max, sum exp(l - max),
 // target logit, best logit, best id) in registers over the range and stores ONE partial at
 // part[range][t]. A finish launch (one wave per token) merges the ranges in a fixed order. Every
-// merge is (max, rescaled sum): no logit is ever exponentiated without its maximum subtracted.
-struct ScoreRun {
-  float m, s, tl, bv;  // max, sum exp(l - m), the target's logit (-inf: not seen), the best logit
-  int bi;              // ... and its id (lowest on ties)
-};
-__device__ __forceinline__ ScoreRun score_empty() {
-  return ScoreRun{-__builtin_inff(), 0.f, -__builtin_inff(), -__builtin_inff(), 0x7FFFFFFF};
-}
-__device__ __forceinline__ void score_merge(ScoreRun& a, const ScoreRun& b) {
-  const float M = fmaxf(a.m, b.m);
-  if (M > -__builtin_inff()) a.s = a.s * expf(a.m - M) + b.s * expf(b.m - M);  // (exp(-inf) = 0: an empty side)
-  a.m = M;
-  a.tl = fmaxf(a.tl, b.tl);  // one side at most holds the target's row
-  if (b.bv > a.bv || (b.bv == a.bv && b.bi < a.bi)) {
-    a.bv = b.bv;
-    a.bi = b.bi;
-  }
-}
-__device__ __forceinline__ ScoreRun score_shfl_xor(const ScoreRun& r, int off) {
-  return ScoreRun{__shfl_xor(r.m, off), __shfl_xor(r.s, off), __shfl_xor(r.tl, off), __shfl_xor(r.bv, off),
-                  __shfl_xor(r.bi, off)};
-}
-
+// merge is (max, rescaled sum): no logit is ever exponentiated without its maximum subtracted
+// (ScoreRun, score_dev.h).
 template <int QT, int TM>
 __global__ __launch_bounds__(512) void score_head_kernel(ScoreHeadArgs a, int gpr, int ngroups) {
   constexpr int NWV = 8, NG = TM / 16, NT = NWV * 64;
@@ -215,6 +195,10 @@ __global__ __launch_bounds__(256) void score_finish_kernel(ScoreHeadArgs a, int 
   }
 }
 
+void score_finish(const ScoreHeadArgs& a, int nranges, hipStream_t s) {
+  hipLaunchKernelGGL(score_finish_kernel, dim3((a.T + 3) / 4), dim3(256), 0, s, a, nranges);
+}
+
 // block shape and ranges: TM = 64 up to 64 rows, else 128 (each token block streams the whole head
 // once, so fewer blocks along T decode fewer weights); ranges sized for about two resident rounds
 // of 512-thread blocks over the CUs
@@ -239,7 +223,7 @@ static void launch_score_head(const ScoreHeadArgs& a, int tm, int ngroups, int g
   const dim3 grid(nranges, (a.T + tm - 1) / tm);
   if (tm == 128) hipLaunchKernelGGL((score_head_kernel<QT, 128>), grid, dim3(512), 0, s, a, gpr, ngroups);
   else hipLaunchKernelGGL((score_head_kernel<QT, 64>), grid, dim3(512), 0, s, a, gpr, ngroups);
-  hipLaunchKernelGGL(score_finish_kernel, dim3((a.T + 3) / 4), dim3(256), 0, s, a, nranges);
+  score_finish(a, nranges, s);
 }
 
 void score_head(const ScoreHeadArgs& a, hipStream_t s) {

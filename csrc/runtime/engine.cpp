@@ -627,18 +627,23 @@ void Engine::setup_moe_wide() {
 
 void Engine::setup_scoring() {
   if (!opt_.scoring || tp_on_ || !has_head() || opt_.layer_begin > 0) return;  // (score() refuses those engines)
-  if (!output_.base || !bmm_supported(output_.type, output_.K))
+  // a row-major 16-bit head is scored as uploaded (score_head_w16: no tile16 copy); K-quants on the tile16 copy
+  score_w16_ = output_.base && (output_.type == T_BF16 || output_.type == T_F16) && output_.K % 64 == 0;
+  if (!output_.base || !(score_w16_ || bmm_supported(output_.type, output_.K)))
     throw std::runtime_error(std::string("scoring: the output head output.weight (type ") + type_layout(output_.type).name +
-                             ", K " + std::to_string(output_.K) + ") has no tile16 form (a tile16 type, K a multiple of 256)");
+                             ", K " + std::to_string(output_.K) + ") has no tile16 form (a tile16 type, K a multiple of 256)" +
+                             " and is no BF16 / F16 matrix with K a multiple of 64");
   if (hp_.n_vocab >= (1 << 24)) throw std::runtime_error("scoring: vocabulary ids must stay below 2^24");
-  if (!t_output_.base || t_output_.base == output_.base) {  // one KV slot, or a model the batched path does not serve
+  if (!score_w16_ && (!t_output_.base || t_output_.base == output_.base)) {  // one KV slot, or a model the batched path does not serve
     t_output_ = output_;
     uint8_t* dst = (uint8_t*)dalloc(t16_bytes(output_.type, output_.rows, output_.K));
     t16_repack(output_, dst, stream_);
     t_output_.base = dst;
   }
   const int B = nb_cap_;
-  for (int T = 1; T <= B; ++T) score_part_words_ = std::max(score_part_words_, score_head_workspace_words(T, hp_.n_vocab));
+  for (int T = 1; T <= B; ++T)
+    score_part_words_ = std::max(score_part_words_, score_w16_ ? score_head_w16_workspace_words(T, hp_.n_vocab)
+                                                               : score_head_workspace_words(T, hp_.n_vocab));
   score_part_ = (float*)dalloc(sizeof(float) * score_part_words_);
   score_tgt_ = (int*)dalloc(sizeof(int) * B);
   score_rec_ = (float*)dalloc(sizeof(float) * B * kScoreRecWords);
@@ -2146,7 +2151,7 @@ std::vector<std::vector<float>> Engine::score(const std::vector<std::vector<int>
     }
     queued.clear();
   };
-  // the epilogue of one chunk, on its residual rows: output norm as f16 rows, then the scoring head
+  // the epilogue of one chunk, on its residual rows: output norm as 16-bit rows, then the scoring head
   auto score_chunk = [&](const std::vector<PrefillSeg>& segs) {
     harvest();
     int rows = 0;
@@ -2157,9 +2162,18 @@ std::vector<std::vector<float>> Engine::score(const std::vector<std::vector<int>
     }
     __half* const xh16 = reinterpret_cast<__half*>(xb_);
     HIPCHK(hipMemcpyAsync(score_tgt_, h_score_tgt_, sizeof(int) * rows, hipMemcpyHostToDevice, stream_));
-    rmsnorm_bf16(x_, out_norm_, hp_.rms_eps, rows, d, xb_, stream_, nullptr, 0, /*f16sw=*/true);
-    score_head(score_head_args(t_output_, hp_.n_vocab, xh16, rows, score_tgt_, h_score_tgt_, score_part_,
-                               score_part_words_, score_rec_), stream_);
+    if (score_w16_) {  // rows of the head's own element type in plain k order, the head as uploaded
+      QMat w = output_;
+      w.rows = hp_.n_vocab;
+      if (w.type == T_F16) rmsnorm_f16(x_, out_norm_, hp_.rms_eps, rows, d, xh16, stream_);
+      else rmsnorm_bf16(x_, out_norm_, hp_.rms_eps, rows, d, xb_, stream_);
+      score_head_w16(score_head_w16_args(w, xb_, rows, score_tgt_, h_score_tgt_, score_part_, score_part_words_,
+                                         score_rec_), stream_);
+    } else {
+      rmsnorm_bf16(x_, out_norm_, hp_.rms_eps, rows, d, xb_, stream_, nullptr, 0, /*f16sw=*/true);
+      score_head(score_head_args(t_output_, hp_.n_vocab, xh16, rows, score_tgt_, h_score_tgt_, score_part_,
+                                 score_part_words_, score_rec_), stream_);
+    }
     HIPCHK(hipMemcpyAsync(h_score_rec_, score_rec_, sizeof(float) * W * rows, hipMemcpyDeviceToHost, stream_));
     queued = segs;
   };

@@ -47,8 +47,9 @@ struct EngineOptions {
   // KV slots (continuous batching): slot 0 serves generate() / the graph decode path, slots
   // [0, n_slots) can decode together through batch_step() (also under tensor parallelism)
   int n_slots = 1;
-  // prompt scoring (Engine::score): builds the head's tile16 copy (also with one KV slot) and the
-  // scoring buffers; a head whose type or K has no tile16 form is refused at construction
+  // prompt scoring (Engine::score): builds the head's tile16 copy (also with one KV slot; none for a
+  // BF16 / F16 head, which score_head_w16 reads as uploaded) and the scoring buffers; any other head
+  // whose type or K has no tile16 form is refused at construction
   bool scoring = false;
   bool verbose = false;
   // fault-injection test hook, "<rank>:<n>[:dev|:shard]" (empty in production; set only by the tests
@@ -268,7 +269,7 @@ class Engine : public SlotBackend {
   // Prompt log-probabilities (EngineOptions::scoring): embed's route - inputs[i] prefilled into KV
   // slot slots[i] from position 0, packed as slots_begin packs them (one KV slot: one input, chunk
   // by chunk) - with another epilogue: each chunk's residual rows go through the output RMSNorm as
-  // f16 rows and the scoring head (kernels.h ScoreHeadArgs), which never stores the logits. Row r's
+  // 16-bit rows and the scoring head (kernels.h ScoreHeadArgs), which never stores the logits. Row r's
   // target is the input's own token r + 1 (carried across chunk borders; none for the last row).
   // Returns per input its rows' records, SlotBackend::kScoreRowFloats floats each. No lm_head
   // GEMV, no sampler, no sampling state; the slots' KV is overwritten. One rank, all layers.
@@ -372,6 +373,7 @@ class Engine : public SlotBackend {
   size_t score_part_words_ = 0;
   float* score_rec_ = nullptr;    // [nb_cap_][kScoreRecWords]
   float* h_score_rec_ = nullptr;  // pinned mirror
+  bool score_w16_ = false;        // a BF16 / F16 head: scored as uploaded (score_head_w16), no tile16 copy
   int* rpos_ = nullptr;     // [n_batch] per-row position of a packed chunk
   int* rslots_ = nullptr;   // [n_batch] per-row KV slot
   int* h_rmeta_ = nullptr;  // pinned [3][n_batch]: tokens | positions | slots

@@ -291,6 +291,7 @@ SPECS.update({
 # unquantised BF16 (what convert_hf_to_gguf writes by default) and the F16 twin of the 8B shape it is timed against
 SPECS.update({
     "tiny-llama-bf16": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama-bf16", quant="bf16"),
+    "tiny-llama-f16": replace(SPECS["tiny-llama3-q4_k_m"], name="tiny-llama-f16", quant="f16"),
     "tiny-qwen3-bf16": replace(SPECS["tiny-qwen3-g2-hd128"], name="tiny-qwen3-bf16", quant="bf16"),
     "llama3-8b-bf16": replace(SPECS["llama3-8b-q4_k_m"], name="Llama-3-8B-BF16", quant="bf16"),
     "llama3-8b-f16": replace(SPECS["llama3-8b-q4_k_m"], name="Llama-3-8B-F16", quant="f16"),
