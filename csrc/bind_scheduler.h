@@ -28,6 +28,9 @@ inline SamplingOpts sampling_opts_from(pybind11::dict sp) {
     for (auto kv : sp["logit_bias"].cast<py::dict>())
       o.logit_bias.emplace_back(kv.first.cast<int>(), kv.second.cast<float>());
   o.n_probs = sp.contains("n_probs") ? sp["n_probs"].cast<int>() : 0;
+  o.mirostat_mode = sp.contains("mirostat_mode") ? sp["mirostat_mode"].cast<int>() : 0;
+  o.mirostat_tau = sp.contains("mirostat_tau") ? sp["mirostat_tau"].cast<float>() : 5.f;
+  o.mirostat_eta = sp.contains("mirostat_eta") ? sp["mirostat_eta"].cast<float>() : 0.1f;
   return o;
 }
 

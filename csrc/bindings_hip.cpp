@@ -983,8 +983,11 @@ PYBIND11_MODULE(_hip, m) {
   // then - if cand_all is given - stage 2 over `world` gathered blocks, else over this one
   m.def("sample", [](uintptr_t logits, int V, uintptr_t params, uintptr_t ring, uintptr_t state, uintptr_t cand,
                      uintptr_t out_tokens, int out_cap, int advance, uintptr_t stream, uintptr_t dbg_clk,
-                     int vocab_off, int V_glob, int V_span, uintptr_t cand_all, int world, int stage) {
+                     int vocab_off, int V_glob, int V_span, uintptr_t cand_all, int world, int stage,
+                     uintptr_t mscratch, int batch, uintptr_t slots, size_t logits_ld, uintptr_t batch_out) {
     SamplerArgs a;
+    a.mscratch = P<float>(mscratch);
+    a.batch = batch; a.slots = P<const int>(slots); a.logits_ld = logits_ld; a.batch_out = P<int>(batch_out);
     a.dbg_clk = P<long long>(dbg_clk);
     a.logits = P<float>(logits); a.V = V; a.p = P<SamplerParamsDev>(params); a.ring = P<int>(ring);
     a.state = P<int>(state); a.cand = P<unsigned>(cand); a.out_tokens = P<int>(out_tokens);
@@ -997,7 +1000,8 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("logits"), py::arg("V"), py::arg("params"), py::arg("ring"), py::arg("state"), py::arg("cand"),
      py::arg("out_tokens"), py::arg("out_cap"), py::arg("advance"), py::arg("stream"), py::arg("dbg_clk") = 0,
      py::arg("vocab_off") = 0, py::arg("V_glob") = 0, py::arg("V_span") = 0, py::arg("cand_all") = 0,
-     py::arg("world") = 1, py::arg("stage") = 3);
+     py::arg("world") = 1, py::arg("stage") = 3, py::arg("mscratch") = 0, py::arg("batch") = 0, py::arg("slots") = 0,
+     py::arg("logits_ld") = 0, py::arg("batch_out") = 0);
   m.attr("MAX_LOGPROBS") = kMaxLogprobs;
   m.attr("LOGPROB_REC_WORDS") = kLogprobRecWords;
   m.def("logprob_part_words", &logprob_part_words);
@@ -1036,8 +1040,9 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("acc"), py::arg("out"), py::arg("n_inputs"), py::arg("stream"), py::arg("stage") = 3);
   m.def("sampler_params_bytes", [](int top_k, float top_p, float min_p, float temp, float rp, float fp, float pp,
                                    int last_n, unsigned long long seed, int greedy, float tfs_z, float typical_p,
-                                   py::dict logit_bias) {
+                                   py::dict logit_bias, int mirostat_mode, float mirostat_tau, float mirostat_eta) {
     SamplerParamsDev p;
+    p.mirostat_mode = mirostat_mode; p.mirostat_tau = mirostat_tau; p.mirostat_eta = mirostat_eta;
     p.top_k = top_k; p.top_p = top_p; p.min_p = min_p; p.temp = temp; p.repeat_penalty = rp;
     p.freq_penalty = fp; p.presence_penalty = pp; p.last_n = last_n; p.seed = seed; p.greedy = greedy;
     p.tfs_z = tfs_z; p.typical_p = typical_p;
@@ -1049,7 +1054,8 @@ PYBIND11_MODULE(_hip, m) {
     return py::bytes(reinterpret_cast<const char*>(&p), sizeof(p));
   }, py::arg("top_k"), py::arg("top_p"), py::arg("min_p"), py::arg("temp"), py::arg("rp"), py::arg("fp"),
      py::arg("pp"), py::arg("last_n"), py::arg("seed"), py::arg("greedy"), py::arg("tfs_z") = 1.f,
-     py::arg("typical_p") = 1.f, py::arg("logit_bias") = py::dict());
+     py::arg("typical_p") = 1.f, py::arg("logit_bias") = py::dict(), py::arg("mirostat_mode") = 0,
+     py::arg("mirostat_tau") = 5.f, py::arg("mirostat_eta") = 0.1f);
   m.def("fill_random", [](uintptr_t base, int type, size_t rows, size_t K, float std, unsigned long long seed,
                           uintptr_t stream) {
     fill_random_planar(P<uint8_t>(base), type, rows, K, std, seed, S(stream));

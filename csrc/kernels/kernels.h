@@ -716,9 +716,16 @@ struct SamplerParamsDev {
   unsigned long long seed = 0;
   int bias_tok[kMaxLogitBias] = {};
   float bias_val[kMaxLogitBias] = {};
+  // mirostat (0 off, 1, 2; ignored by a greedy row): the row is truncated over the whole vocabulary
+  // by its feedback variable mu (state word S_MU) instead of top-k / tail-free / typical / top-p / min-p
+  int mirostat_mode = 0;
+  float mirostat_tau = 5.f, mirostat_eta = 0.1f;
 };
-// Device state block (ints) shared by the decode kernels.
-enum StateIdx : int { S_TOKEN = 0, S_POS = 1, S_STEP = 2, S_RING_LEN = 3, S_RING_HEAD = 4, S_NOUT = 5, S_NSTATE = 8 };
+// Device state block (ints) shared by the decode kernels. S_MU holds a float: mirostat's mu, written
+// (2 tau) when a request begins and updated by the sampler's stage 2.
+enum StateIdx : int {
+  S_TOKEN = 0, S_POS = 1, S_STEP = 2, S_RING_LEN = 3, S_RING_HEAD = 4, S_NOUT = 5, S_MU = 6, S_NSTATE = 8
+};
 
 // Stage 1 writes, per row, one packed candidate block of sampler_cand_words(V_span) 4-byte
 // words: [values nb*64 f32][global ids nb*64 i32][slice bounds nb][slice maxima nb]
@@ -751,7 +758,11 @@ struct SamplerArgs {
   int* batch_out = nullptr;
   // ... and to host-mapped pinned memory (the batch-step graph's token read-back: no copy node)
   int* batch_out_host = nullptr;
+  // mirostat rows (world 1): stage 1 stores the row's prepared, temperature-scaled logits here,
+  // [rows][V] f32, for stage 2 to read again. Null: a row that asks for mirostat is sampled plainly.
+  float* mscratch = nullptr;
 };
+static constexpr int kMirostatWindow = 4096;  // kept tokens stage 2 sorts in LDS; beyond: value bisection
 int sampler_blocks(int V);
 size_t sampler_cand_words(int V);
 void sample_stage1(const SamplerArgs& a, hipStream_t s);

@@ -12,6 +12,10 @@
 // one wave selects, bitonic-sorts, applies top-p / min-p / temperature, draws,
 // and updates the device state (token, position, RNG step, penalty ring).
 //
+// A mirostat row (SamplerParamsDev::mirostat_mode, not greedy) branches off in both stages:
+// stage 1 stores its prepared, temperature-scaled slice to the row's scratch, stage 2 runs
+// mirostat_row over it (below) - same two launches, no top-k chain.
+//
 // The uniform draw is SplitMix64(seed ^ step*C) >> 40 - identical to
 // engine/sampling.py:philox_uniform and the CPU backend.
 #include <cfloat>
@@ -24,6 +28,7 @@ namespace lfk {
 static constexpr int KMAX = 64;
 static constexpr int SLICE = 1024;  // logits per stage-1 wave (16 per lane)
 static constexpr int NE1 = SLICE / 64;
+static constexpr int MIROSTAT_M = 100;  // leading ratios of mirostat v1's s_hat (engine/sampling.py)
 
 __device__ __forceinline__ unsigned fkey(float f) {
   const unsigned u = __float_as_uint(f);
@@ -176,6 +181,32 @@ __global__ __launch_bounds__(64) void sample_stage1_kernel(SamplerArgs a) {
 #pragma unroll
     for (int e = 0; e < NE1; ++e) v[e] = sl[64 * e + lane];
   }
+  // ---- mirostat row: the truncation runs over the whole vocabulary, so the prepared slice goes
+  // to the row's scratch, temperature-scaled (+ 0: a -0 becomes +0, the two order as equals), and
+  // the slice's sum of exp(l - m_s) and maximum m_s take the bound and maximum words of the block
+  if (a.mscratch && P.mirostat_mode != 0 && !P.greedy) {
+    float* row = a.mscratch + (size_t)blockIdx.y * a.V;
+    float ms = -FLT_MAX;
+#pragma unroll
+    for (int e = 0; e < NE1; ++e) {
+      const int i = lo + 64 * e + lane;
+      if (i < a.V) {
+        v[e] = v[e] / P.temp + 0.f;
+        row[i] = v[e];
+        ms = fmaxf(ms, v[e]);
+      }
+    }
+    ms = wave_max_fast(ms);
+    float sum = 0.f;
+#pragma unroll
+    for (int e = 0; e < NE1; ++e) sum += lo + 64 * e + lane < a.V ? expf(v[e] - ms) : 0.f;
+    sum = wave_sum_fast(sum);
+    if (lane == 0) {
+      cand_tau[blockIdx.x] = __float_as_uint(sum);
+      cand_tau[nb + blockIdx.x] = __float_as_uint(ms);
+    }
+    return;
+  }
   // ---- top-K superset of the slice
   const float T = wave_superset_threshold<NE1>(v, K);
   float* ov = cand_val + blockIdx.x * KMAX;
@@ -315,6 +346,315 @@ __device__ __forceinline__ int top_superset(int n, int K, const float* cval, con
   return wave_collect<NW>(w, wi, T, KMAX, tval, tidx);
 }
 
+// the sampled token into the row's state: token, penalty ring, outputs, counters
+__device__ __forceinline__ void commit_token(const SamplerArgs& a, int brow, int tok) {
+  int* st = a.state;
+  tok = min(max(tok, 0), (a.V_glob > 0 ? a.V_glob : a.V) - 1);  // non-finite logits must not leave an out-of-range id behind
+  st[S_TOKEN] = tok;
+  const int head = st[S_RING_HEAD];
+  a.ring[head & 63] = tok;
+  st[S_RING_HEAD] = (head + 1) & 63;
+  st[S_RING_LEN] = min(st[S_RING_LEN] + 1, 64);
+  if (a.out_tokens) a.out_tokens[st[S_NOUT] % a.out_cap] = tok;
+  if (a.batch_out) a.batch_out[brow] = tok;
+  if (a.batch_out_host) __hip_atomic_store(a.batch_out_host + brow, tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  st[S_NOUT] += 1;
+  st[S_STEP] += 1;
+  if (a.advance_pos) st[S_POS] += 1;
+}
+
+// ---------------------------------------------------------------- mirostat (stage 2 of a mirostat row)
+// engine/sampling.py:HostSampler._mirostat on the row's scratch l[V] (prepared, temperature-scaled):
+// with M = max l and Z = sum exp(l - M) from stage 1's slice pairs, the kept set is a prefix of the
+// order (value descending, id ascending), described by a value class and a tie count: every value
+// above the class, and the `ntie` lowest ids of the class itself.
+//   v2: the class of M + ln Z - mu ln 2 (surprise <= mu is a value threshold), all of its ties;
+//   v1: the class of the k-th largest value (k from the 101 leading values), k - count(above) ties.
+// Values are compared by their ordered bit patterns (fkey), so a class is one key and the k-th value
+// is found by radix selection on the key (4 passes over the row) and the drawn class of a large
+// kept set by bisecting it (at most 32 passes), no sort.
+// Up to kMirostatWindow kept tokens are compacted into LDS, sorted by a block-wide bitonic network,
+// prefix-summed in that order and drawn by inverse CDF. A larger kept set (mu drifts, tau is the
+// user's) is drawn without sorting: bisect for the class t with mass(> t) <= u Z_k < mass(>= t), then
+// the tie by ascending id. Every sum is taken in a fixed order (no floating-point atomics; the LDS
+// counter below only hands out slots that the sort reorders), so two runs are bit-equal.
+struct MiroLds {
+  unsigned key[kMirostatWindow];
+  int id[kMirostatWindow];
+  float redf[4];
+  int redi[4];
+  int cnt, pick, k;
+};
+
+// block-wide reductions of the 256 threads, fixed order; every thread gets the result
+__device__ __forceinline__ float block_sum(float x, float* red) {
+  x = wave_sum_fast(x);
+  __syncthreads();  // (reads of red by the previous reduction are done)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float block_max(float x, float* red) {
+  x = wave_max_fast(x);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+// exclusive prefix sum of one int per thread
+__device__ __forceinline__ int block_excl_scan(int x, int* red) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int inc = x;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(inc, o);
+    if (lane >= o) inc += t;
+  }
+  __syncthreads();
+  if (lane == 63) red[w] = inc;
+  __syncthreads();
+  int off = 0;
+  for (int k = 0; k < w; ++k) off += red[k];
+  return off + inc - x;
+}
+
+// the row's values above the class K and in it (counts below 2^24 are exact as floats)
+__device__ __forceinline__ void miro_counts(const float* l, int V, unsigned K, int& c_gt, int& c_eq, MiroLds& ml) {
+  int g = 0, q = 0;
+  for (int i = threadIdx.x; i < V; i += 256) {
+    const unsigned k = fkey(l[i]);
+    g += k > K;
+    q += k == K;
+  }
+  c_gt = (int)block_sum((float)g, ml.redf);
+  c_eq = (int)block_sum((float)q, ml.redf);
+}
+__device__ __forceinline__ float miro_mass_gt(const float* l, int V, unsigned K, float M, MiroLds& ml) {
+  float s = 0.f;
+  for (int i = threadIdx.x; i < V; i += 256) {
+    const float v = l[i];
+    s += fkey(v) > K ? expf(v - M) : 0.f;
+  }
+  return block_sum(s, ml.redf);
+}
+// the smallest key in [lo, hi] at which the block-uniform, monotone `pred` holds (it holds at hi)
+template <class F>
+__device__ __forceinline__ unsigned miro_bisect(unsigned lo, unsigned hi, F pred) {
+  while (lo < hi) {
+    const unsigned mid = lo + ((hi - lo) >> 1);
+    if (pred(mid)) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+// the class of the k-th largest value (count(above) < k <= count(above) + count(in it)) by radix
+// selection on the key: 4 passes over the row, one byte each, into a 256-bin LDS histogram of the
+// values that share the bytes found so far (integer atomics: the counts are exact). The histogram
+// borrows ml.id, which no caller holds anything in at that point.
+__device__ __forceinline__ unsigned miro_kth(const float* l, int V, int k, MiroLds& ml) {
+  const int tid = threadIdx.x;
+  int* hist = ml.id;
+  unsigned prefix = 0u;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    const unsigned mask = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
+    hist[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < V; i += 256) {
+      const unsigned key = fkey(l[i]);
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
+    }
+    __syncthreads();
+    const int x = hist[255 - tid];                      // thread tid looks at bin 255 - tid
+    const int above = block_excl_scan(x, ml.redi);      // values in the bins above it
+    if (above < k && k <= above + x) { ml.k = 255 - tid; ml.cnt = above; }
+    __syncthreads();
+    prefix |= (unsigned)ml.k << shift;
+    k -= ml.cnt;
+    __syncthreads();
+  }
+  return prefix;
+}
+
+// each thread's contiguous part [i0, i1) of the row: ties are ranked by ascending id through it
+__device__ __forceinline__ void miro_part(int V, int& i0, int& i1) {
+  const int C = (V + 255) / 256;
+  i0 = min((int)threadIdx.x * C, V);
+  i1 = min(i0 + C, V);
+}
+
+// the kept set into LDS: the c_gt values above K (any order, the sort follows), then the ntie
+// lowest ids of the class; c_gt + ntie <= kMirostatWindow
+__device__ __forceinline__ void miro_collect(const float* l, int V, unsigned K, int c_gt, int ntie, MiroLds& ml) {
+  if (threadIdx.x == 0) ml.cnt = 0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < V; i += 256) {
+    const unsigned k = fkey(l[i]);
+    if (k > K) {
+      const int p = atomicAdd(&ml.cnt, 1);
+      if (p < kMirostatWindow) { ml.key[p] = k; ml.id[p] = i; }
+    }
+  }
+  int i0, i1, c = 0;
+  miro_part(V, i0, i1);
+  for (int i = i0; i < i1; ++i) c += fkey(l[i]) == K;
+  int r = block_excl_scan(c, ml.redi);
+  for (int i = i0; i < i1 && r < ntie; ++i)
+    if (fkey(l[i]) == K) {
+      if (c_gt + r < kMirostatWindow) { ml.key[c_gt + r] = K; ml.id[c_gt + r] = i; }
+      ++r;
+    }
+  __syncthreads();
+}
+
+// the id of the j-th (from 0) value of class K by ascending id; 0 if there is none
+__device__ __forceinline__ int miro_nth_eq(const float* l, int V, unsigned K, int j, MiroLds& ml) {
+  int i0, i1, c = 0;
+  miro_part(V, i0, i1);
+  for (int i = i0; i < i1; ++i) c += fkey(l[i]) == K;
+  if (threadIdx.x == 0) ml.pick = 0;
+  int r = block_excl_scan(c, ml.redi);  // (its barriers order the store above before the one below)
+  if (r <= j && j < r + c)
+    for (int i = i0; i < i1; ++i)
+      if (fkey(l[i]) == K && r++ == j) ml.pick = i;
+  __syncthreads();
+  return ml.pick;
+}
+
+// block-wide bitonic sort of the n <= kMirostatWindow pairs in LDS by (key descending, id ascending)
+__device__ __forceinline__ void miro_sort(int n, MiroLds& ml) {
+  int n2 = 2;
+  while (n2 < n) n2 <<= 1;
+  for (int i = n + threadIdx.x; i < n2; i += 256) { ml.key[i] = 0u; ml.id[i] = 0x7fffffff; }
+  __syncthreads();
+  for (int size = 2; size <= n2; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < (n2 >> 1); t += 256) {
+        const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+        const unsigned ki = ml.key[i], kj = ml.key[j];
+        const int ii = ml.id[i], ij = ml.id[j];
+        const bool j_first = kj > ki || (kj == ki && ij < ii);
+        if (j_first == ((i & size) == 0)) {
+          ml.key[i] = kj; ml.id[i] = ij;
+          ml.key[j] = ki; ml.id[j] = ii;
+        }
+      }
+      __syncthreads();
+    }
+}
+
+// v1: k from the n1 = min(101, V) leading values, sorted in LDS (one thread, fp64: 100 terms).
+// s_hat is the least-squares slope of log(p_i / p_i+1) = l_i - l_i+1 against log((i + 2) / (i + 1));
+// s_hat 0 or a k that is not finite (s_hat 1, an overflow) keeps the whole vocabulary, as on the host.
+__device__ __forceinline__ int miro_v1_k(int n1, int V, float mu, const MiroLds& ml) {
+  const int m = n1 - 1;
+  double tb = 0., tt = 0.;
+  for (int i = 0; i < m; ++i) {
+    const double t = log((double)(i + 2) / (double)(i + 1));
+    tb += t * ((double)kfloat(ml.key[i]) - (double)kfloat(ml.key[i + 1]));
+    tt += t * t;
+  }
+  const double s_hat = m > 0 ? tb / tt : 1., eps = s_hat - 1.;
+  if (s_hat == 0.) return V;  // (the host's 1 / s_hat raises; pow(x, inf) would be a finite 0)
+  const double k = pow((eps * exp2((double)mu)) / (1. - pow((double)V, -eps)), 1. / s_hat);
+  return isfinite(k) ? (int)fmax(1., fmin(k, (double)V)) : V;
+}
+
+__device__ __forceinline__ void mirostat_row(const SamplerArgs& a, int brow, const CandRow& cr, MiroLds& ml) {
+  const SamplerParamsDev& P = *a.p;
+  const int tid = threadIdx.x, V = a.V, nb = cr.nb_l;
+  const float* l = a.mscratch + (size_t)brow * V;
+  // ---- M and Z = sum_s sum_s * exp(m_s - M) (a slice past V holds sum 0, maximum -FLT_MAX)
+  float M = -FLT_MAX;
+  for (int g = tid; g < nb; g += 256) M = fmaxf(M, cr.smax(g));
+  M = block_max(M, ml.redf);
+  float Z = 0.f;
+  for (int g = tid; g < nb; g += 256) Z += cr.bound(g) * expf(cr.smax(g) - M);
+  Z = block_sum(Z, ml.redf);
+  const float lnZ = logf(Z);
+  const unsigned kM = fkey(M);
+  const float mu = __int_as_float(a.state[S_MU]);
+  // ---- the kept set: class K, c_gt values above it, ntie of its c_eq ties
+  unsigned K;
+  int c_gt, c_eq, ntie;
+  if (P.mirostat_mode == 2) {
+    K = fkey(M + lnZ - mu * 0.69314718f);
+    miro_counts(l, V, K, c_gt, c_eq, ml);
+    ntie = c_eq;
+    if (c_gt + c_eq == 0) {  // at least the best token
+      K = kM;
+      miro_counts(l, V, K, c_gt, c_eq, ml);
+      ntie = 1;
+    }
+  } else {
+    const int n1 = min(MIROSTAT_M + 1, V);
+    K = miro_kth(l, V, n1, ml);
+    miro_counts(l, V, K, c_gt, c_eq, ml);
+    miro_collect(l, V, K, c_gt, n1 - c_gt, ml);
+    miro_sort(n1, ml);
+    if (tid == 0) ml.k = miro_v1_k(n1, V, mu, ml);
+    __syncthreads();
+    const int k = ml.k;
+    K = miro_kth(l, V, k, ml);
+    miro_counts(l, V, K, c_gt, c_eq, ml);
+    ntie = k - c_gt;
+  }
+  ntie = max(min(ntie, c_eq), 0);
+  const int n = c_gt + ntie;
+  const int step = a.state[S_STEP];
+  const unsigned long long h = splitmix64(P.seed ^ ((unsigned long long)step * 0xD1B54A32D192ED03ull));
+  const float u = (float)(h >> 40) * (1.f / 16777216.f);
+  int tok;
+  float lp;  // ln of the drawn token's probability among the kept ones
+  if (n <= kMirostatWindow) {
+    // ---- window: sort, prefix sums over each thread's contiguous part, first cum > u * Z_k
+    miro_collect(l, V, K, c_gt, ntie, ml);
+    miro_sort(n, ml);
+    int i0, i1;
+    miro_part(n, i0, i1);
+    float s = 0.f;
+    for (int i = i0; i < i1; ++i) s += expf(kfloat(ml.key[i]) - M);
+    const float inc = wave_scan(s);
+    const float prev = __shfl_up(inc, 1);
+    if ((tid & 63) == 63) ml.redf[tid >> 6] = inc;
+    if (tid == 0) ml.pick = n - 1;
+    __syncthreads();
+    float cum = 0.f;
+    for (int w = 0; w < (tid >> 6); ++w) cum += ml.redf[w];
+    if (tid & 63) cum += prev;
+    const float Zk = ((ml.redf[0] + ml.redf[1]) + ml.redf[2]) + ml.redf[3];
+    const float target = u * Zk;
+    int first = n - 1;
+    for (int i = i0; i < i1; ++i) {
+      cum += expf(kfloat(ml.key[i]) - M);
+      if (cum > target) { first = i; break; }
+    }
+    if (first < n - 1) atomicMin(&ml.pick, first);
+    __syncthreads();
+    const int pick = max(ml.pick, 0);
+    tok = ml.id[pick];
+    lp = (kfloat(ml.key[pick]) - M) - logf(Zk);
+  } else {
+    // ---- beyond the window: Z_k from the same masses the bisection compares, then the class, then the tie
+    const float e_t = expf(kfloat(K) - M);
+    const float Zk = miro_mass_gt(l, V, K, M, ml) + (float)ntie * e_t;
+    // (u * Z_k can round up to Z_k itself: keep the target inside the kept mass)
+    const float target = fminf(u * Zk, __uint_as_float(__float_as_uint(Zk) - 1u));
+    const unsigned Kd = miro_bisect(K, kM, [&](unsigned k) { return miro_mass_gt(l, V, k, M, ml) <= target; });
+    const float above = miro_mass_gt(l, V, Kd, M, ml);
+    const float x = kfloat(Kd), e_x = expf(x - M);
+    int g, q;
+    miro_counts(l, V, Kd, g, q, ml);
+    const int nk = Kd == K ? ntie : q;
+    const int j = max(min((int)floorf((target - above) / e_x), nk - 1), 0);
+    tok = miro_nth_eq(l, V, Kd, j, ml);
+    lp = (x - M) - logf(Zk);
+  }
+  if (tid == 0) {
+    a.state[S_MU] = __float_as_int(mu - P.mirostat_eta * (-lp * 1.44269504f - P.mirostat_tau));
+    commit_token(a, brow, a.vocab_off + tok);
+  }
+}
+
 template <int NE2, bool TL = false>
 __global__ __launch_bounds__(256) void sample_stage2_kernel(SamplerArgs a, int nb_l) {
   const int brow = blockIdx.x;
@@ -352,6 +692,13 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(SamplerArgs a, int n
   for (int e = 0; e < NE2; ++e) {  // independent loads (no value-dependent second load)
     const int i = min(256 * e + tid, nb * KMAX - 1);
     cr.cand(i, v[e], idx[e]);
+  }
+  // a mirostat row (block-uniform; behind the loads above, which a plain row is waiting for anyway)
+  // takes its own path over the row's scratch: none of the top-k chain below applies to it
+  __shared__ MiroLds ml;
+  if (a.mscratch && P.mirostat_mode != 0 && !P.greedy) {
+    mirostat_row(a, brow, cr, ml);
+    return;
   }
   for (int b = tid + 256; b < nb; b += 256) lb = fmaxf(lb, cr.bound(b));
   lb = wave_max_fast(lb);
@@ -463,20 +810,8 @@ __global__ __launch_bounds__(256) void sample_stage2_kernel(SamplerArgs a, int n
     tok = __shfl(id, pick);
   }
   if (lane == 0) {
-    int* st = a.state;
-    tok = min(max(tok, 0), (a.V_glob > 0 ? a.V_glob : a.V) - 1);  // non-finite logits must not leave an out-of-range id behind
-    st[S_TOKEN] = tok;
-    const int head = st[S_RING_HEAD];
-    a.ring[head & 63] = tok;
-    st[S_RING_HEAD] = (head + 1) & 63;
-    st[S_RING_LEN] = min(st[S_RING_LEN] + 1, 64);
-    if (a.out_tokens) a.out_tokens[st[S_NOUT] % a.out_cap] = tok;
-    if (a.batch_out) a.batch_out[brow] = tok;
-    if (a.batch_out_host) __hip_atomic_store(a.batch_out_host + brow, tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    commit_token(a, brow, tok);
     LFK_ST(3);
-    st[S_NOUT] += 1;
-    st[S_STEP] += 1;
-    if (a.advance_pos) st[S_POS] += 1;
   }
 }
 
@@ -489,6 +824,7 @@ void sample_stage1(const SamplerArgs& a, hipStream_t s) {
     throw std::runtime_error("sample: bad batched arguments");
   if (!a.cand || a.V < 0 || (a.V == 0 && a.V_span <= 0)) throw std::runtime_error("sample: no candidate buffer / empty vocabulary");
   if (a.V_span && a.V_span < a.V) throw std::runtime_error("sample: V_span < V");
+  if (a.mscratch && (a.world != 1 || a.vocab_off != 0)) throw std::runtime_error("sample: mirostat scratch needs world 1");
   hipLaunchKernelGGL(sample_stage1_kernel, dim3(sampler_blocks(a.V_span ? a.V_span : a.V), rows), dim3(64), 0, s, a);
 }
 

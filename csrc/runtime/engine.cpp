@@ -468,6 +468,8 @@ void Engine::alloc_buffers() {
     HIPCHK(hipHostMalloc((void**)&h_rmeta_, sizeof(int) * 3 * B, hipHostMallocDefault));
   }
   HIPCHK(hipMemset(out_tokens_, 0, sizeof(int) * 64));
+  // mirostat rows' prepared logits, next to the candidate blocks (one rank, the stage that holds the head)
+  if (!tp_on_ && has_head()) mscratch_ = (float*)dalloc(sizeof(float) * std::max(bmax_, 1) * (size_t)V_real_l_);
   // token log-probabilities (one rank, the stage that holds the head)
   h_nprobs_.assign(NS, 0);
   if (!tp_on_ && has_head()) {
@@ -815,6 +817,7 @@ void Engine::enqueue_sample(const float* logits, int rows, size_t ld, int slot, 
   sa.V_glob = hp_.n_vocab;
   sa.V_span = V_l_;
   sa.advance_pos = advance_pos;
+  sa.mscratch = mscratch_;
   if (batched) {
     sa.p = sparams_; sa.ring = ring_; sa.state = state_;
     sa.batch = rows; sa.slots = bslots_; sa.logits_ld = ld; sa.batch_out = btok_out_; sa.batch_out_host = sample_host_;
@@ -1356,12 +1359,18 @@ void Engine::launch_step(int slot) {
 
 // ------------------------------------------------------------------------ generation
 SamplerParamsDev Engine::make_sparams(const SamplingOpts& sp) const {
-  if (sp.top_k < 0 || sp.top_k > 64) throw std::runtime_error("GPU sampler: top_k must be in [0, 64]");
+  const bool miro = sp.mirostat_mode != 0 && sp.temp > 0.f;  // top-k is not applied under mirostat
+  if (!miro && (sp.top_k < 0 || sp.top_k > 64)) throw std::runtime_error("GPU sampler: top_k must be in [0, 64]");
   if (sp.n_probs > kMaxLogprobs) throw std::runtime_error("GPU sampler: at most 20 logprobs per token");
   if (sp.n_probs > 0 && !lp_rec_) throw std::runtime_error("GPU sampler: logprobs need one rank holding the head");
   SamplerParamsDev p;
   p.greedy = sp.temp <= 0.f ? 1 : 0;
-  p.top_k = p.greedy ? 1 : (sp.top_k == 0 ? 64 : sp.top_k);
+  p.top_k = p.greedy || miro ? 1 : (sp.top_k == 0 ? 64 : sp.top_k);
+  if (miro) {  // (a greedy request ignores mirostat, as on the host)
+    if (sp.mirostat_mode != 1 && sp.mirostat_mode != 2) throw std::runtime_error("GPU sampler: mirostat_mode must be 0, 1 or 2");
+    if (!mscratch_) throw std::runtime_error("GPU sampler: mirostat needs one rank holding the head");
+    p.mirostat_mode = sp.mirostat_mode; p.mirostat_tau = sp.mirostat_tau; p.mirostat_eta = sp.mirostat_eta;
+  }
   p.top_p = sp.top_p; p.min_p = sp.min_p; p.temp = sp.temp;
   p.repeat_penalty = sp.repeat_penalty; p.freq_penalty = sp.freq_penalty; p.presence_penalty = sp.presence_penalty;
   p.last_n = std::min(sp.last_n, 64);
@@ -1390,6 +1399,8 @@ void Engine::begin_slot_state(int slot, const std::vector<int>& prompt, const Sa
   hstate[S_POS] = n_prompt;  // position the first generated token will occupy
   hstate[S_RING_LEN] = rl;
   hstate[S_RING_HEAD] = rl & 63;
+  const float mu0 = 2.f * p.mirostat_tau;  // mirostat's feedback variable; the sampler's stage 2 updates it
+  std::memcpy(&hstate[S_MU], &mu0, sizeof(float));
   HIPCHK(hipMemcpyAsync(sparams_ + slot, &p, sizeof(p), hipMemcpyHostToDevice, stream_));
   HIPCHK(hipMemcpyAsync(ring_ + 64 * slot, hring, sizeof(hring), hipMemcpyHostToDevice, stream_));
   HIPCHK(hipMemcpyAsync(state_ + (size_t)S_NSTATE * slot, hstate, sizeof(hstate), hipMemcpyHostToDevice, stream_));

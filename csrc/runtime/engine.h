@@ -470,6 +470,7 @@ class Engine : public SlotBackend {
   size_t cand_words_ = 0;     // sampler candidate block of one row (sampler_cand_words(V_l))
   unsigned* cand_ = nullptr;  // [cand_words_] this rank's stage-1 block (single row)
   unsigned* cand_all_ = nullptr;   // [tp][cand_words_] gathered blocks (tp > 1)
+  float* mscratch_ = nullptr;  // [max(bmax, 1)][V] mirostat rows' prepared logits (SamplerArgs::mscratch; tp 1)
   int* state_ = nullptr;
   int* ring_ = nullptr;
   int* out_tokens_ = nullptr;

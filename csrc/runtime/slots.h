@@ -18,6 +18,8 @@ struct SamplingOpts {
   float tfs_z = 1.f, typical_p = 1.f;
   std::vector<std::pair<int, float>> logit_bias;  // distinct tokens, at most kMaxLogitBias
   int n_probs = 0;  // > 0: log-probabilities of every generated token, with the n_probs most probable ones
+  int mirostat_mode = 0;  // 1 / 2: mirostat (ignored at temperature <= 0); mu starts at 2 tau
+  float mirostat_tau = 5.f, mirostat_eta = 0.1f;
 };
 
 // One generated token's log-probabilities of the raw logits (engine/sampling.py:token_logprobs):

@@ -78,17 +78,19 @@ class SamplingParams:
     def greedy(self) -> bool:
         return self.temperature <= 0.0
 
-    def gpu_compatible(self, vocab: int, max_logprobs: int = 0) -> bool:
+    def gpu_compatible(self, vocab: int, max_logprobs: int = 0, mirostat: bool = False) -> bool:
         """Whether the on-device chain (csrc/kernels/sampler.hip) computes exactly this
-        chain: top-k within its 64-candidate window, few enough bias entries, no
-        mirostat, and no more log-probabilities per token than the backend computes on
-        the device (``max_logprobs``; 0: none, such requests take the host route)."""
-        if self.mirostat_mode and not self.greedy():
+        chain: top-k within its 64-candidate window, few enough bias entries, mirostat
+        only where the backend samples it on the device (``mirostat``; one GPU), and no
+        more log-probabilities per token than the backend computes on the device
+        (``max_logprobs``; 0: none, such requests take the host route)."""
+        miro = bool(self.mirostat_mode) and not self.greedy()
+        if miro and not (mirostat and self.mirostat_mode in (1, 2)):
             return False
         if self.n_probs > max_logprobs or self.logits_processor is not None or self.grammar is not None \
                 or len(self.logit_bias) > GPU_MAX_LOGIT_BIAS:
             return False
-        if self.greedy():
+        if self.greedy() or miro:   # (mirostat truncates over the whole vocabulary: no top-k)
             return True
         return 0 < self.top_k <= 64 or (self.top_k <= 0 and vocab <= 64)
 

@@ -75,6 +75,8 @@ def gpu_sampling_dict(params: SamplingParams, n_vocab: int) -> dict:
             "frequency_penalty": params.frequency_penalty, "presence_penalty": params.presence_penalty,
             "last_n": params.last_n, "seed": params.seed & 0xFFFFFFFFFFFFFFFF, "tfs_z": params.tfs_z,
             "typical_p": params.typical_p, "n_probs": max(0, int(params.n_probs)),
+            "mirostat_mode": int(params.mirostat_mode), "mirostat_tau": float(params.mirostat_tau),
+            "mirostat_eta": float(params.mirostat_eta),
             "logit_bias": {int(t): float(b) for t, b in params.logit_bias.items() if 0 <= int(t) < n_vocab}}
 
 
@@ -166,7 +168,7 @@ class HipBackend:
         """Whether this request runs as a row of the continuous batch (the facade then
         skips its single-sequence lock and KV prefix bookkeeping: the scheduler reuses
         prefixes per slot)."""
-        return self.sched is not None and params.gpu_compatible(self.n_vocab, self.max_logprobs)
+        return self.sched is not None and params.gpu_compatible(self.n_vocab, self.max_logprobs, mirostat=self.tp_size == 1)
 
     def close(self):
         if self.sched is not None:
@@ -211,7 +213,7 @@ class HipBackend:
     def generate(self, prompt: Sequence[int], n_keep: int, max_new: int, params: SamplingParams,
                  stop_ids: Sequence[int], poll: Optional[Callable[[], bool]] = None,
                  on_token: Optional[Callable[[int], None]] = None) -> GenerationResult:
-        if not params.gpu_compatible(self.n_vocab, self.max_logprobs):
+        if not params.gpu_compatible(self.n_vocab, self.max_logprobs, mirostat=self.tp_size == 1):
             return host_generate(self._forward, prompt, n_keep, max_new, params, stop_ids, self.n_ctx, poll,
                                  on_token)
         if self.sched is not None:
