@@ -38,6 +38,13 @@ static void hip_ok(const char* what) {
 
 static SamplingOpts sampling_opts(py::dict sp) { return sampling_opts_from(sp); }
 
+// the kernel-level bindings' kv_type keyword: "f16" (the default) or "q8_0"
+static bool kv_is_q8(const std::string& kv_type, const char* who) {
+  if (kv_type == "q8_0") return true;
+  if (kv_type != "f16") throw std::runtime_error(std::string(who) + ": kv_type must be \"f16\" or \"q8_0\", got \"" + kv_type + "\"");
+  return false;
+}
+
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "MI355X (gfx950) runtime: GGUF engine + HIP kernels";
 
@@ -45,8 +52,9 @@ PYBIND11_MODULE(_hip, m) {
       .def(py::init([](const std::string& path, int n_ctx, int n_batch, int device, bool use_graph, int tp_rank,
                        int tp_size, py::bytes nccl_id, int layer_begin, const std::vector<float>& tensor_split,
                        int n_slots, const std::string& comm, int layer_end, const std::string& test_fault,
-                       bool scoring) {
+                       bool scoring, const std::string& kv_type) {
              EngineOptions o;
+             o.kv_type = kv_type;
              o.scoring = scoring;
              o.test_fault = test_fault;
              o.layer_begin = layer_begin;
@@ -68,7 +76,8 @@ PYBIND11_MODULE(_hip, m) {
            py::arg("use_graph") = true, py::arg("tp_rank") = 0, py::arg("tp_size") = 1,
            py::arg("nccl_id") = py::bytes(""), py::arg("layer_begin") = 0,
            py::arg("tensor_split") = std::vector<float>{}, py::arg("n_slots") = 1, py::arg("comm") = "auto",
-           py::arg("layer_end") = -1, py::arg("test_fault") = "", py::arg("scoring") = false)
+           py::arg("layer_end") = -1, py::arg("test_fault") = "", py::arg("scoring") = false,
+           py::arg("kv_type") = "f16")
       .def(
           "generate",
           [](Engine& e, const std::vector<int>& prompt, int n_keep, int max_new, py::dict sp,
@@ -286,6 +295,7 @@ PYBIND11_MODULE(_hip, m) {
                d["wo_rows"] = p.wo_rows;
                d["tp"] = to_string(p.tp);
                d["zero_qkv"] = to_string(p.zero_qkv);
+               d["kv"] = e.kv_type();
                out.append(d);
              }
              return out;
@@ -314,7 +324,9 @@ PYBIND11_MODULE(_hip, m) {
            })
       .def("kv_load",
            [](Engine& e, py::array_t<uint8_t, py::array::c_style> a, int n) {
-             if ((size_t)a.size() != e.kv_state_bytes(n)) throw std::runtime_error("kv_load: size mismatch");
+             if ((size_t)a.size() != e.kv_state_bytes(n)) 
+               throw std::runtime_error(std::string("kv_load: size mismatch (a snapshot of other positions, or of a cache that is "
+                                                    "not kv_type=") + e.kv_type() + ")");
              void* p = const_cast<uint8_t*>(a.data());
              py::gil_scoped_release nogil;
              e.kv_transfer(p, n, true);
@@ -582,20 +594,46 @@ PYBIND11_MODULE(_hip, m) {
   m.def("bmm_qkv_fits", &bmm_qkv_fits);
   m.def("rope_kv_prefill", [](uintptr_t qkv, int T, int pos0, int n_q, int n_kv, int head_dim, int n_ctx,
                               uintptr_t rope, uintptr_t q_out, uintptr_t k_cache, uintptr_t v_cache, uintptr_t stream,
-                              uintptr_t pos_arr, uintptr_t slot_arr, size_t slot_stride, uintptr_t bias) {
+                              uintptr_t pos_arr, uintptr_t slot_arr, size_t slot_stride, uintptr_t bias,
+                              const std::string& kv_type, uintptr_t pos_dev) {
+    if (pos_dev && kv_type == "f16") throw std::runtime_error("rope_kv_prefill: pos_dev is the Q8_0 writer's (kv_type=\"q8_0\")");
+    if (kv_is_q8(kv_type, "rope_kv_prefill")) {  // the Q8_0 cache's writer (attention_q8.hip)
+      KvAppendQ8Args a;
+      a.qkv = P<float>(qkv); a.T = T; a.pos0 = pos0; a.n_q = n_q; a.n_kv = n_kv; a.head_dim = head_dim; a.n_ctx = n_ctx;
+      a.rope = P<float2>(rope); a.bias = P<float>(bias); a.q_out = P<float>(q_out);
+      a.k_cache = P<void>(k_cache); a.v_cache = P<void>(v_cache);
+      a.pos_arr = P<int>(pos_arr); a.slot_arr = P<int>(slot_arr); a.slot_stride = slot_stride;
+      a.pos_dev = P<int>(pos_dev);
+      rope_kv_append_q8(a, S(stream));
+      hip_ok("rope_kv_append_q8");
+      return;
+    }
     rope_kv_prefill(P<float>(qkv), T, pos0, n_q, n_kv, head_dim, n_ctx, P<float2>(rope), P<float>(q_out),
                     P<__half>(k_cache), P<__half>(v_cache), S(stream), P<int>(pos_arr), P<int>(slot_arr), slot_stride,
                     P<float>(bias));
     hip_ok("rope_kv_prefill");
   }, py::arg("qkv"), py::arg("T"), py::arg("pos0"), py::arg("n_q"), py::arg("n_kv"), py::arg("head_dim"),
      py::arg("n_ctx"), py::arg("rope"), py::arg("q_out"), py::arg("k_cache"), py::arg("v_cache"), py::arg("stream"),
-     py::arg("pos_arr") = 0, py::arg("slot_arr") = 0, py::arg("slot_stride") = 0, py::arg("bias") = 0);
+     py::arg("pos_arr") = 0, py::arg("slot_arr") = 0, py::arg("slot_stride") = 0, py::arg("bias") = 0,
+     py::arg("kv_type") = "f16", py::arg("pos_dev") = 0);
   // QK-norm models (qwen3): head norm + RoPE + KV append of projection rows [T][n_q + 2 n_kv];
   // qk_norm = [q_norm | k_norm] (2 head_dim floats). pos_dev: T = 1 at the position read from the device
   m.def("qk_norm_rope_kv", [](uintptr_t qkv, int T, int pos0, int n_q, int n_kv, int head_dim, int n_ctx,
                               uintptr_t rope, uintptr_t qk_norm, float eps, uintptr_t q_out, uintptr_t k_cache,
                               uintptr_t v_cache, uintptr_t stream, uintptr_t pos_arr, uintptr_t slot_arr,
-                              size_t slot_stride, uintptr_t pos_dev) {
+                              size_t slot_stride, uintptr_t pos_dev, const std::string& kv_type) {
+    if (kv_is_q8(kv_type, "qk_norm_rope_kv")) {
+      KvAppendQ8Args a;
+      a.qkv = P<float>(qkv); a.T = T; a.pos0 = pos0; a.n_q = n_q; a.n_kv = n_kv; a.head_dim = head_dim; a.n_ctx = n_ctx;
+      a.rope = P<float2>(rope); a.qk_norm = P<float>(qk_norm); a.eps = eps; a.q_out = P<float>(q_out);
+      a.k_cache = P<void>(k_cache); a.v_cache = P<void>(v_cache);
+      a.pos_arr = P<int>(pos_arr); a.slot_arr = P<int>(slot_arr); a.slot_stride = slot_stride;
+      a.pos_dev = P<int>(pos_dev);
+      if (!a.qk_norm) throw std::runtime_error("qk_norm_rope_kv: the norm weights are required");
+      rope_kv_append_q8(a, S(stream));
+      hip_ok("rope_kv_append_q8");
+      return;
+    }
     qk_norm_rope_kv(P<float>(qkv), T, pos0, n_q, n_kv, head_dim, n_ctx, P<float2>(rope), P<float>(qk_norm), eps,
                     P<float>(q_out), P<__half>(k_cache), P<__half>(v_cache), S(stream), P<int>(pos_arr),
                     P<int>(slot_arr), slot_stride, P<int>(pos_dev));
@@ -603,7 +641,7 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("qkv"), py::arg("T"), py::arg("pos0"), py::arg("n_q"), py::arg("n_kv"), py::arg("head_dim"),
      py::arg("n_ctx"), py::arg("rope"), py::arg("qk_norm"), py::arg("eps"), py::arg("q_out"), py::arg("k_cache"),
      py::arg("v_cache"), py::arg("stream"), py::arg("pos_arr") = 0, py::arg("slot_arr") = 0,
-     py::arg("slot_stride") = 0, py::arg("pos_dev") = 0);
+     py::arg("slot_stride") = 0, py::arg("pos_dev") = 0, py::arg("kv_type") = "f16");
   m.def("state_layout", []() { return std::make_tuple((int)S_NSTATE, (int)S_TOKEN, (int)S_POS); });
   m.def("batch_gather", [](uintptr_t slots, int B, uintptr_t state, uintptr_t tok, uintptr_t pos, uintptr_t stream,
                            uintptr_t zero, int zero_n, int zero_stride) {
@@ -860,7 +898,7 @@ PYBIND11_MODULE(_hip, m) {
                           int debug_stop, uintptr_t dbg_clk, int batch, uintptr_t slots, size_t slot_stride,
                           uintptr_t out_h, uintptr_t qkv_raw, size_t qkv_ld, size_t k_off, size_t v_off, uintptr_t ss,
                           float inv_k, float eps, uintptr_t rope_freq, uintptr_t qkv_bias, int live, uintptr_t qk_norm,
-                          float qkn_eps) {
+                          float qkn_eps, const std::string& kv_type) {
     AttnDecodeArgs a;
     a.qk_norm = P<float>(qk_norm); a.qkn_eps = qkn_eps;
     a.live = live;
@@ -880,7 +918,8 @@ PYBIND11_MODULE(_hip, m) {
     a.q = P<float>(q); a.k_cache = P<__half>(kc); a.v_cache = P<__half>(vc); a.pos = P<int>(pos);
     a.n_ctx = n_ctx; a.n_head = n_head; a.n_kv_head = n_kv; a.head_dim = hd; a.scale = scale;
     a.part = P<float>(part); a.out = P<float>(out);
-    attn_decode(a, S(stream));
+    if (kv_is_q8(kv_type, "attn_decode")) attn_decode_q8(a, S(stream));
+    else attn_decode(a, S(stream));
     hip_ok("attn_decode");
   }, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("pos"), py::arg("n_ctx"), py::arg("n_head"), py::arg("n_kv"),
      py::arg("hd"), py::arg("scale"), py::arg("part"), py::arg("out"), py::arg("stream"), py::arg("counters"),
@@ -888,7 +927,7 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("slot_stride") = 0, py::arg("out_h") = 0, py::arg("qkv_raw") = 0, py::arg("qkv_ld") = 0,
      py::arg("k_off") = 0, py::arg("v_off") = 0, py::arg("ss") = 0, py::arg("inv_k") = 0.f, py::arg("eps") = 1e-5f,
      py::arg("rope_freq") = 0, py::arg("qkv_bias") = 0, py::arg("live") = 0, py::arg("qk_norm") = 0,
-     py::arg("qkn_eps") = 1e-6f);
+     py::arg("qkn_eps") = 1e-6f, py::arg("kv_type") = "f16");
   // the single-row decode attention and its Wo GEMV in one launch, set up as
   // Engine::enqueue_layer_decode does (tests/test_decode_fused_gpu.py): attn_decode's single-row
   // arguments, then done (64 ints the caller zeroed), Wo planar (w, type, n_out rows, K = n_head hd),
@@ -940,7 +979,8 @@ PYBIND11_MODULE(_hip, m) {
   m.def("attn_decode_workspace_floats", &attn_decode_workspace_floats);
   m.def("attn_prefill", [](uintptr_t q, uintptr_t kc, uintptr_t vc, int T, int pos0, int n_ctx, int n_head, int n_kv,
                            int hd, float scale, uintptr_t out, uintptr_t stream, bool out_bf16, bool out_h,
-                           const std::vector<std::array<int, 4>>& pieces, size_t slot_stride) {
+                           const std::vector<std::array<int, 4>>& pieces, size_t slot_stride,
+                           const std::string& kv_type) {
     AttnPrefillArgs a;
     // packed pieces: (row, n, pos, slot) each, against caches slot * slot_stride halves in
     if (pieces.size() > (size_t)AttnPrefillArgs::kMaxPieces) throw std::runtime_error("attn_prefill: too many pieces");
@@ -955,11 +995,13 @@ PYBIND11_MODULE(_hip, m) {
     else if (out_bf16) a.out_bf16 = P<__hip_bfloat16>(out);
     else a.out = P<float>(out);
     a.out_stride = n_head * hd;
-    attn_prefill(a, S(stream));
+    if (kv_is_q8(kv_type, "attn_prefill")) attn_prefill_q8(a, S(stream));
+    else attn_prefill(a, S(stream));
     hip_ok("attn_prefill");
   }, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("T"), py::arg("pos0"), py::arg("n_ctx"), py::arg("n_head"),
      py::arg("n_kv"), py::arg("hd"), py::arg("scale"), py::arg("out"), py::arg("stream"), py::arg("out_bf16") = false,
-     py::arg("out_h") = false, py::arg("pieces") = std::vector<std::array<int, 4>>{}, py::arg("slot_stride") = 0);
+     py::arg("out_h") = false, py::arg("pieces") = std::vector<std::array<int, 4>>{}, py::arg("slot_stride") = 0,
+     py::arg("kv_type") = "f16");
   m.def("embed", [](uintptr_t w, int type, int V, int d, uintptr_t tokens, int T, uintptr_t x, uintptr_t stream) {
     embed_rows(make_qmat(P<void>(w), type, V, d), P<int>(tokens), T, P<float>(x), S(stream));
     hip_ok("embed");

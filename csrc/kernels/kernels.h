@@ -497,6 +497,37 @@ struct AttnPrefillArgs {
 };
 void attn_prefill(const AttnPrefillArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- Q8_0 KV cache (attention_q8.hip)
+// Per layer and slot a cache is an int8 plane [n_kv_head][n_ctx][head_dim] with the f16 scale plane
+// [n_kv_head][n_ctx][head_dim / 32] directly behind it. The cache pointers of the argument structs
+// address the int8 plane (their __half type is the f16 cache's); slot strides stay in halves.
+constexpr size_t kv_q8_layer_halves(int n_kv_head, int n_ctx, int head_dim) {  // rounded to 16 bytes
+  return ((size_t)n_kv_head * n_ctx * head_dim / 32 * 17 + 7) / 8 * 8;
+}
+// The only writer: rope_kv_prefill (bias) and qk_norm_rope_kv (qk_norm) in one, with their
+// addressing modes - a chunk (T, pos0), per-row pos_arr / slot_arr, or one row at *pos_dev. q leaves
+// as f32; K (rotated) and V are quantised per 32 values of a head.
+struct KvAppendQ8Args {
+  const float* qkv = nullptr;      // [T][n_q + 2 n_kv] raw sums
+  int T = 0, pos0 = 0, n_q = 0, n_kv = 0, head_dim = 0, n_ctx = 0;
+  const float2* rope = nullptr;    // [n_ctx][head_dim / 2] (cos, sin)
+  const float* bias = nullptr;     // optional [n_q + 2 n_kv], added before the rotation
+  const float* qk_norm = nullptr;  // optional [q_norm | k_norm]: per-head RMSNorm (eps) before the rotation
+  float eps = 1e-6f;
+  float* q_out = nullptr;          // [T][n_q]
+  void* k_cache = nullptr;         // layer base of slot 0
+  void* v_cache = nullptr;
+  const int* pos_arr = nullptr;
+  const int* slot_arr = nullptr;
+  size_t slot_stride = 0;          // halves
+  const int* pos_dev = nullptr;
+};
+void rope_kv_append_q8(const KvAppendQ8Args& a, hipStream_t s);
+// attn_decode's plain form (finished q, appended keys; single row or batched rows) and
+// attn_prefill's MFMA form (every output form, packed pieces, groups 1..16) over such caches
+void attn_decode_q8(const AttnDecodeArgs& a, hipStream_t s);
+void attn_prefill_q8(const AttnPrefillArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------- prefill GEMM (MFMA)
 enum GemmEpi : int { GEMM_STORE = 0, GEMM_ADD = 1, GEMM_SWIGLU = 2 };
 struct GemmArgs {

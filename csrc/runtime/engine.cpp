@@ -138,6 +138,16 @@ Engine::Engine(const std::string& path, const EngineOptions& opts) : opt_(opts) 
   // comm=rccl at tp_size 1: the tensor-parallel code paths over a ONE-rank RCCL communicator
   // (every collective a copy) - how a one-GPU box runs the RCCL branch inside captured graphs
   tp_on_ = tp > 1 || opt_.comm == "rccl";
+  if (opt_.kv_type != "f16" && opt_.kv_type != "q8_0")
+    throw std::runtime_error("kv_type must be \"f16\" or \"q8_0\", got \"" + opt_.kv_type + "\"");
+  kvq8_ = opt_.kv_type == "q8_0";
+  if (kvq8_) {
+    if (tp_on_) throw std::runtime_error("kv_type=q8_0 is not served with tensor parallelism (tp_size > 1)");
+    if (opt_.layer_begin > 0 || layer_end_ < hp_.n_layer)
+      throw std::runtime_error("kv_type=q8_0 needs the GPU to hold every layer (layer_begin / layer_end name a range)");
+    if (hp_.head_dim != 64 && hp_.head_dim != 128) throw std::runtime_error("kv_type=q8_0: head_dim must be 64 or 128");
+    if (hp_.n_head / std::max(1, hp_.n_head_kv) > 8) throw std::runtime_error("kv_type=q8_0: gqa group must be 1 to 8");
+  }
   if (tp_on_ && opt_.comm != "ipc") {
     if (opt_.nccl_id.size() != sizeof(ncclUniqueId)) throw std::runtime_error("bad nccl id");
     ncclUniqueId id;
@@ -360,7 +370,8 @@ void Engine::alloc_buffers() {
   logits_l_ = (float*)dalloc(sizeof(float) * V_l_);
   HIPCHK(hipMemset(logits_l_, 0, sizeof(float) * V_l_));
   // KV of this engine's layers only (a layer-split / hybrid stage holds its range's part)
-  const size_t kv = (size_t)(layer_end_ - opt_.layer_begin) * nkv_l_ * opt_.n_ctx * hd;
+  // (in halves: the f16 rows, or the Q8_0 planes at 17/32 of them)
+  const size_t kv = (size_t)(layer_end_ - opt_.layer_begin) * kv_layer_halves();
   const int NS = opt_.n_slots;
   slot_stride_ = kv;
   kc_ = (__half*)dalloc(kv * 2 * NS);
@@ -894,11 +905,21 @@ std::vector<LogprobEntry> Engine::step_logprobs() {
   return last_lp_;
 }
 
+void Engine::append_q8(const Layer& L, int T, int pos0, __half* kcl, __half* vcl, const int* pos_arr,
+                       const int* slot_arr, const int* pos_dev, hipStream_t s) {
+  KvAppendQ8Args a;
+  a.qkv = qkv_; a.T = T; a.pos0 = pos0; a.n_q = nq_; a.n_kv = nkvd_; a.head_dim = hp_.head_dim; a.n_ctx = opt_.n_ctx;
+  a.rope = rope_; a.bias = L.bqkv; a.qk_norm = L.qkn; a.eps = hp_.rms_eps; a.q_out = q_;
+  a.k_cache = kcl; a.v_cache = vcl;
+  a.pos_arr = pos_arr; a.slot_arr = slot_arr; a.slot_stride = slot_arr ? slot_stride_ : 0; a.pos_dev = pos_dev;
+  rope_kv_append_q8(a, s);
+}
+
 void Engine::enqueue_layer_decode(int l, hipStream_t s) {
   const Layer& L = layers_[l];
   const int d = hp_.n_embd, hd = hp_.head_dim;
   const bool tp = tp_on_;
-  const size_t kv_layer = (size_t)nkv_l_ * opt_.n_ctx * hd;
+  const size_t kv_layer = kv_layer_halves();
   int* st = state_ + (size_t)S_NSTATE * dslot_;
   QkvArgs qa;
   qa.wq = L.wq; qa.wk = L.wk; qa.wv = L.wv;
@@ -909,12 +930,17 @@ void Engine::enqueue_layer_decode(int l, hipStream_t s) {
   qa.n_ctx = opt_.n_ctx; qa.head_dim = hd;
   qa.pos = st + S_POS;
   qa.rope = rope_;
-  if (L.bqkv) { qa.bq = L.bqkv; qa.bk = L.bqkv + nq_; qa.bv = L.bqkv + nq_ + nkvd_; }
+  // (a Q8_0 cache: the raw sums leave without the biases, which the append kernel adds)
+  if (L.bqkv && !kvq8_) { qa.bq = L.bqkv; qa.bk = L.bqkv + nq_; qa.bv = L.bqkv + nq_ + nkvd_; }
   // QK-norm (qwen3): the GEMV rotates two rows at a time and never sees a head - it stores the
   // normalised sums, and the head norm + RoPE + append kernel finishes them at the device's position
-  if (L.qkn) qa.raw_out = qkv_;
+  // A Q8_0 cache: every layer takes that chain - raw sums, the quantising append kernel, the plain
+  // attention over the int8 rows, the Wo GEMV on its own
+  if (L.qkn || kvq8_) qa.raw_out = qkv_;
   gemv_qkv(qa, s);
-  if (L.qkn)
+  if (kvq8_)
+    append_q8(L, 1, 0, qa.k_cache, qa.v_cache, nullptr, nullptr, st + S_POS, s);
+  else if (L.qkn)
     qk_norm_rope_kv(qkv_, 1, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, qa.k_cache, qa.v_cache, s,
                     nullptr, nullptr, 0, st + S_POS);
 
@@ -928,7 +954,7 @@ void Engine::enqueue_layer_decode(int l, hipStream_t s) {
   const bool tpe = tp && tp_epilogue(o);  // the all-reduce in the GEMV epilogue (no collective launch)
   // attention + Wo in one launch: Wo's weights stream while the attention runs
   bool fused = false;
-  if (!tp && wo_fuse_ && !L.qkn) {  // (QK-norm layers: the plain attention after the norm kernel)
+  if (!tp && wo_fuse_ && !L.qkn && !kvq8_) {  // (QK-norm layers: the plain attention after the norm kernel)
     aa.done = dec_done_ + 64 * l;
     o.out = x_;
     o.wait = aa.done; o.wait_cnt = nkv_l_; o.wait_n = 1; o.wait_err = wo_err_;
@@ -940,12 +966,14 @@ void Engine::enqueue_layer_decode(int l, hipStream_t s) {
     }
   }
   if (!fused) {
-    if (attn_touch_ && nkv_l_ < 63) {  // this layer's Wo into the memory-side cache under the attention
+    // this layer's Wo into the memory-side cache under the attention (the Q8_0 kernel has no touch plane)
+    if (attn_touch_ && nkv_l_ < 63 && !kvq8_) {
       aa.pf_sink = attn_cnt_ + 63;
       aa.pf[0] = L.wo.base;
       aa.pf_bytes[0] = qmat_bytes(L.wo);
     }
-    attn_decode(aa, s);
+    if (kvq8_) attn_decode_q8(aa, s);
+    else attn_decode(aa, s);
   }
 
   if (fused) {
@@ -1057,7 +1085,7 @@ void Engine::enqueue_prefill(int T, int pos0, hipStream_t s, bool embed) {
 void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_t s) {
   const int d = hp_.n_embd, hd = hp_.head_dim;
   const bool tp = tp_on_;
-  const size_t kv_layer = (size_t)nkv_l_ * opt_.n_ctx * hd;
+  const size_t kv_layer = kv_layer_halves();
   const int ncol = nq_ + 2 * nkvd_;
   {
     const Layer& L = layers_[l];
@@ -1100,7 +1128,9 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
     if (!batched && segs_) {  // packed prompts: per-row slot / position, attention per piece
       __half* kcl = kc_ + kv_layer * (l - opt_.layer_begin);  // slot 0's layer l; + slot * slot_stride_
       __half* vcl = vc_ + kv_layer * (l - opt_.layer_begin);
-      if (L.qkn)
+      if (kvq8_)
+        append_q8(L, T, 0, kcl, vcl, rpos_, rslots_, nullptr, s);
+      else if (L.qkn)
         qk_norm_rope_kv(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, kcl, vcl, s, rpos_, rslots_,
                         slot_stride_);
       else
@@ -1117,7 +1147,7 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
         if (t16) pa.out_h = attnh16;
         else pa.out_bf16 = attnb_;
         pa.out_stride = nq_;
-        if (mfma && pieces_attn_) {
+        if (kvq8_ || (mfma && pieces_attn_)) {  // (the Q8_0 kernel: every group size it serves, pieces included)
           pa.slot_stride = slot_stride_;
           const size_t i1 = std::min(sg.size(), i0 + AttnPrefillArgs::kMaxPieces);
           for (size_t i = i0; i < i1; ++i) {
@@ -1125,7 +1155,8 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
             pa.pc_row[k] = sg[i].row; pa.pc_n[k] = sg[i].n; pa.pc_pos[k] = sg[i].pos; pa.pc_slot[k] = sg[i].slot;
           }
           pa.n_pieces = (int)(i1 - i0);
-          attn_prefill(pa, s);
+          if (kvq8_) attn_prefill_q8(pa, s);
+          else attn_prefill(pa, s);
           i0 = i1;
           continue;
         }
@@ -1140,7 +1171,9 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
     } else if (!batched) {
       __half* kcl = kc_ + slot_stride_ * kv_slot_ + kv_layer * (l - opt_.layer_begin);
       __half* vcl = vc_ + slot_stride_ * kv_slot_ + kv_layer * (l - opt_.layer_begin);
-      if (L.qkn)
+      if (kvq8_)
+        append_q8(L, T, pos0, kcl, vcl, nullptr, nullptr, nullptr, s);
+      else if (L.qkn)
         qk_norm_rope_kv(qkv_, T, pos0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, kcl, vcl, s);
       else
         rope_kv_prefill(qkv_, T, pos0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, nullptr, nullptr, 0, L.bqkv);
@@ -1150,11 +1183,14 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
       if (t16) pa.out_h = attnh16;  // straight into the Wo GEMM's input (f16 / bf16)
       else pa.out_bf16 = attnb_;
       pa.out_stride = nq_;
-      attn_prefill(pa, s);
+      if (kvq8_) attn_prefill_q8(pa, s);
+      else attn_prefill(pa, s);
     } else {  // T decode rows, each of its own KV slot and position
       __half* kcl = kc_ + kv_layer * (l - opt_.layer_begin);  // slot 0's layer l; the kernels add slot * slot_stride_
       __half* vcl = vc_ + kv_layer * (l - opt_.layer_begin);
-      if (L.qkn)
+      if (kvq8_)
+        append_q8(L, T, 0, kcl, vcl, bpos_, bslots_, nullptr, s);
+      else if (L.qkn)
         qk_norm_rope_kv(qkv_, T, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, L.qkn, hp_.rms_eps, q_, kcl, vcl, s, bpos_, bslots_,
                         slot_stride_);
       else
@@ -1168,7 +1204,8 @@ void Engine::enqueue_rows_layer(int l, int T, int pos0, bool batched, hipStream_
       aa.batch = T; aa.slots = bslots_; aa.slot_stride = slot_stride_;
       aa.q_stride = nq_; aa.out_stride = nq_;
       aa.part_stride = attn_decode_workspace_floats(opt_.n_ctx, nh_l_, hd);
-      attn_decode(aa, s);
+      if (kvq8_) attn_decode_q8(aa, s);
+      else attn_decode(aa, s);
       to_bf16(attn_, T * nq_, attnb_, s);
     }
     if (t16) {
@@ -1453,7 +1490,8 @@ BatchLayerPlan Engine::plan_batch_layer(int l, int B) const {
   // appended to the caches by the attention
   // (Q|K|V biases: only with the RoPE deferred to the attention, which adds them to the normalised
   // sums before rotating; the form with rotated partials takes the one-part / unfused path)
-  const bool sk = qkv_sk_ && bmm_qkv_sk_supported(L.t_wq.type, L.t_wk.type, L.t_wv.type, d, B) &&
+  // (a Q8_0 cache: only the append kernel writes it - neither the split-K attention nor the epilogue does)
+  const bool sk = !kvq8_ && qkv_sk_ && bmm_qkv_sk_supported(L.t_wq.type, L.t_wk.type, L.t_wv.type, d, B) &&
                   (!(L.bqkv || L.qkn) || bmm_qkv_sk_defers_rope());
   if (sk) {
     p.qkv = P::Qkv::split_k;
@@ -1463,10 +1501,11 @@ BatchLayerPlan Engine::plan_batch_layer(int l, int B) const {
     // a QK-norm layer (qwen3) declines the epilogue and its folded norm: the epilogue's tile holds 16
     // rows of a head, never the head - such a layer takes bprep + bmm + the head-norm kernel as a
     // model too wide for one part does (its FFN keeps `fused` / `fnorm`)
-    const bool qepi = fused && !L.qkn;
+    const bool qepi = fused && !L.qkn && !kvq8_;
     p.qkv = qepi ? P::Qkv::epilogue : P::Qkv::unfused;
-    p.qkv_norm_folded = fnorm && !L.qkn;
-    p.finish = L.qkn ? P::Finish::qk_norm_rope_kv : qepi ? P::Finish::none : P::Finish::rope_kv_prefill;
+    p.qkv_norm_folded = fnorm && !L.qkn && !kvq8_;
+    p.finish = kvq8_ ? P::Finish::rope_kv_append_q8
+               : L.qkn ? P::Finish::qk_norm_rope_kv : qepi ? P::Finish::none : P::Finish::rope_kv_prefill;
     // bumped layers (Q|K Q4_K + V Q6_K): both runs in one launch
     if (qepi) {
       const std::vector<BmmArgs> rl = batch_qkv_runs(l, B, p);
@@ -1595,6 +1634,9 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
       rope_kv_prefill(qkv_, B, 0, nq_, nkvd_, hd, opt_.n_ctx, rope_, q_, kcl, vcl, s, bpos_, bslots_, slot_stride_,
                       L.bqkv);
       break;
+    case P::Finish::rope_kv_append_q8:
+      append_q8(L, B, 0, kcl, vcl, bpos_, bslots_, nullptr, s);
+      break;
   }
   // ---- attention
   AttnDecodeArgs aa;
@@ -1614,13 +1656,16 @@ void Engine::enqueue_batch_layer(int l, int B, hipStream_t s) {
     aa.qkv_bias = L.bqkv;
     aa.qk_norm = L.qkn; aa.qkn_eps = hp_.rms_eps;
   }
-  aa.dbg_clk = clk_of(l, 1);
-  aa.live = attn_live_;
+  if (!kvq8_) {
+    aa.dbg_clk = clk_of(l, 1);
+    aa.live = attn_live_;
+  }
   // (the batched Wo stays its own launch: in one launch with the attention - Wo planes streaming
   // their weights meanwhile and starting on done counters - the B = 6 step measured 2.42 vs 2.34
   // ms, r4: the in-launch hand-off costs what the boundary did and the weight stream slowed the
   // attention's K / V loads)
-  attn_decode(aa, s);
+  if (kvq8_) attn_decode_q8(aa, s);
+  else attn_decode(aa, s);
   // ---- Wo + FFN
   const BatchFfnArgs f = batch_ffn_args(l, B, p);
   auto tp_begin = [&]() {
@@ -2575,6 +2620,8 @@ GenOut Engine::chain_generate(const std::vector<Engine*>& st, const std::vector<
                               const std::function<bool()>& poll, const std::function<void(int)>& on_token) {
   const size_t n = st.size();
   if (n == 0) throw std::runtime_error("chain_generate: no stages");
+  for (Engine* e : st)
+    if (e && e->kvq8_) throw std::runtime_error("chain_generate: not served with kv_type=q8_0");
   for (size_t i = 0; i < n; ++i) {
     const Engine* e = st[i];
     if (!e || e->tp_on_ || e->opt_.tp_size > 1) throw std::runtime_error("chain_generate: stages are single-rank engines");
@@ -2771,6 +2818,28 @@ void Engine::kv_transfer(void* buf, int n, bool load) {
     throw std::runtime_error("KV snapshots hold one rank's heads: not available with tensor parallelism");
   if (n < 0 || n > opt_.n_ctx) throw std::runtime_error("kv_transfer: n out of range");
   if (n == 0) return;
+  // per layer and cache: n rows of every head's int8 plane, then of its scale plane - 4 n_layer 2-D
+  // copies where the f16 cache issues 2 (a layer's two planes differ in pitch, and the 16-byte rounding
+  // of a layer need not be a multiple of either). The snapshot carries no type tag: one of the other
+  // cache type differs in size, which the callers check (kv_load, HipBackend.load_kv)
+  if (kvq8_) {
+    const int hd = hp_.head_dim, nl = layer_end_ - opt_.layer_begin;
+    char* b = static_cast<char*>(buf);
+    for (int which = 0; which < 2; ++which)
+      for (int l = 0; l < nl; ++l) {
+        char* layer = reinterpret_cast<char*>((which == 0 ? kc_ : vc_) + kv_layer_halves() * l);
+        for (int plane = 0; plane < 2; ++plane) {
+          const size_t rb = plane == 0 ? (size_t)hd : (size_t)hd / 16;  // bytes per key
+          char* cache = layer + (plane == 0 ? 0 : (size_t)nkv_l_ * opt_.n_ctx * hd);
+          const size_t row = (size_t)n * rb, pitch = (size_t)opt_.n_ctx * rb;
+          if (load) HIPCHK(hipMemcpy2DAsync(cache, pitch, b, row, row, nkv_l_, hipMemcpyDefault, stream_));
+          else HIPCHK(hipMemcpy2DAsync(b, row, cache, pitch, row, nkv_l_, hipMemcpyDefault, stream_));
+          b += row * nkv_l_;
+        }
+      }
+    HIPCHK(hipStreamSynchronize(stream_));
+    return;
+  }
   const size_t row = (size_t)n * hp_.head_dim * 2, pitch = (size_t)opt_.n_ctx * hp_.head_dim * 2;
   const size_t rows = (size_t)(layer_end_ - opt_.layer_begin) * nkv_l_;
   char* b = static_cast<char*>(buf);

@@ -51,6 +51,9 @@ struct EngineOptions {
   // BF16 / F16 head, which score_head_w16 reads as uploaded) and the scoring buffers; any other head
   // whose type or K has no tile16 form is refused at construction
   bool scoring = false;
+  // KV cache format: "f16", or "q8_0" (GGML's Q8_0 along head_dim, planar; attention_q8.hip). Q8_0 is
+  // served on one GPU holding every layer: refused with tp_size > 1, a layer range, chain_generate
+  std::string kv_type = "f16";
   bool verbose = false;
   // fault-injection test hook, "<rank>:<n>[:dev|:shard]" (empty in production; set only by the tests
   // through the Python backend's explicit opt-in, runtime/hip_backend.py): follower <rank> fails its
@@ -89,7 +92,7 @@ struct BatchLayerPlan {
     epilogue,   // one K part, RoPE and KV append in the epilogue
     unfused,    // bprep + bmm, then the finishing kernel
   };
-  enum class Finish { none, rope_kv_prefill, qk_norm_rope_kv };
+  enum class Finish { none, rope_kv_prefill, qk_norm_rope_kv, rope_kv_append_q8 };
   enum class Ffn {
     wo_ffn_chain,  // Wo, gate/up and down in one launch
     ffn_chain,     // Wo; gate/up and down in one launch
@@ -118,7 +121,7 @@ inline const char* to_string(BatchLayerPlan::Qkv v) {
   return n[(int)v];
 }
 inline const char* to_string(BatchLayerPlan::Finish v) {
-  static constexpr const char* n[] = {"none", "rope_kv_prefill", "qk_norm_rope_kv"};
+  static constexpr const char* n[] = {"none", "rope_kv_prefill", "qk_norm_rope_kv", "rope_kv_append_q8"};
   return n[(int)v];
 }
 inline const char* to_string(BatchLayerPlan::Ffn v) {
@@ -157,7 +160,12 @@ class Engine : public SlotBackend {
   static constexpr int kStepClkBlocks = 8192;
   std::vector<long long> step_clk();
   void step_clk_zero();
-  size_t kv_state_bytes(int n) const { return 2ull * (layer_end_ - opt_.layer_begin) * nkv_l_ * (size_t)n * hp_.head_dim * 2; }
+  // (Q8_0: n rows of int8 values and of scales, 34 bytes per 32 values)
+  size_t kv_state_bytes(int n) const {
+    const size_t vals = 2ull * (layer_end_ - opt_.layer_begin) * nkv_l_ * (size_t)n * hp_.head_dim;
+    return kvq8_ ? vals / 32 * 34 : vals * 2;
+  }
+  const char* kv_type() const { return kvq8_ ? "q8_0" : "f16"; }
   void kv_transfer(void* buf, int n, bool load);
   // hybrid placement: hidden states [T][d] of layer `layer_begin` in, last-row logits out
   std::vector<float> eval_hidden(const float* x, int T, int pos0);
@@ -405,8 +413,17 @@ class Engine : public SlotBackend {
     return p.tp == BatchLayerPlan::Tp::p2p_accumulate ? tmp_b_ : p.tp == BatchLayerPlan::Tp::rccl ? tmp_ : x_;
   }
   __half* batch_kv(__half* cache, int l) const {  // slot 0's layer l; the kernels add slot * slot_stride_
-    return cache + (size_t)nkv_l_ * opt_.n_ctx * hp_.head_dim * (l - opt_.layer_begin);
+    return cache + kv_layer_halves() * (l - opt_.layer_begin);
   }
+  // one layer of one slot's K (or V) cache in halves: the f16 rows, or the Q8_0 planes (kernels.h)
+  size_t kv_layer_halves() const {
+    return kvq8_ ? kv_q8_layer_halves(nkv_l_, opt_.n_ctx, hp_.head_dim) : (size_t)nkv_l_ * opt_.n_ctx * hp_.head_dim;
+  }
+  // the Q8_0 cache's writer over this engine's buffers (qkv_ -> q_ and the caches at kcl / vcl): the
+  // layer's bias or QK-norm, and one of the addressing modes (pos_arr + slot_arr, pos_dev, or T rows at pos0)
+  void append_q8(const Layer& L, int T, int pos0, __half* kcl, __half* vcl, const int* pos_arr, const int* slot_arr,
+                 const int* pos_dev, hipStream_t s);
+  bool kvq8_ = false;
   void bmm_rows(const QMat& w, const __half* xh, int ldh, float* out, int ldo, int B, hipStream_t s,
                 long long* dbg = nullptr);
   void bprep_rows(const float* x, int ldx, bool swiglu, const float* norm_w, int K, int B, float* zero, int zero_n,

@@ -77,6 +77,9 @@ class Settings:
     # Llama(logits_all=True): /v1/completions with echo and logprobs fills the prompt tokens'
     # log-probabilities (the MI355X engine builds its scoring head)
     logits_all: bool = False
+    # KV cache format of the MI355X engine: f16, or q8_0 (Llama(type_k=8, type_v=8): 0.53 of the bytes;
+    # one GPU, no tensor parallelism)
+    kv_type: str = "f16"
     # tensor parallelism (split_mode=row over torchrun ranks): the engine's collectives -
     # "auto" (one-shot P2P kernel for decode, RCCL for prefill), "rccl", or "ipc" (the P2P
     # kernel only: ranks may share a GPU). tp_device puts EVERY rank on that GPU (the one-GPU
@@ -140,6 +143,9 @@ class Settings:
         if s.embedding_pooling not in ("auto", "mean", "last", "cls"):
             raise ValueError(f"EMBEDDING_POOLING={s.embedding_pooling!r}: auto, mean, last or cls")
         s.logits_all = _env("LOGITS_ALL", s.logits_all, bool)
+        s.kv_type = _env("KV_TYPE", s.kv_type).lower()
+        if s.kv_type not in ("f16", "q8_0"):
+            raise ValueError(f"KV_TYPE={s.kv_type!r}: f16 or q8_0")
         s.tp_comm = _env("TP_COMM", s.tp_comm).lower()
         tpd = _env("TP_DEVICE", None)
         s.tp_device = int(tpd) if tpd is not None else None

@@ -20,4 +20,5 @@ def build_engine(settings: Settings):
                  main_gpu=settings.main_gpu, seed=settings.seed, chat_format=settings.chat_format,
                  use_graphs=settings.use_graphs, verbose=settings.verbose,
                  **({"max_batch": settings.max_batch} if settings.max_batch > 1 else {}),
-                 **({"logits_all": True} if settings.logits_all else {}), **tp)
+                 **({"logits_all": True} if settings.logits_all else {}),
+                 **({"type_k": 8, "type_v": 8} if settings.kv_type == "q8_0" else {}), **tp)

@@ -68,6 +68,21 @@ def _select_backend(reader, hp: LlamaHParams, n_gpu_layers: int, backend: Option
     return "cpu"
 
 
+GGML_TYPE_F16, GGML_TYPE_Q8_0 = 1, 8
+
+
+def _kv_type(type_k: Optional[int], type_v: Optional[int]) -> str:
+    """Upstream's type_k / type_v (GGML type ids; None = F16) as the engine's kv_type. K and V share one
+    format: F16 (1) or Q8_0 (8)."""
+    names = {None: "f16", GGML_TYPE_F16: "f16", GGML_TYPE_Q8_0: "q8_0"}
+    for name, v in (("type_k", type_k), ("type_v", type_v)):
+        if v not in names:
+            raise ValueError(f"{name}={v}: the KV cache is F16 (1) or Q8_0 (8)")
+    if names[type_k] != names[type_v]:
+        raise ValueError(f"type_k={type_k} and type_v={type_v}: K and V share one cache type (mixed pairs are not served)")
+    return names[type_k]
+
+
 class Llama:
     supports_cancel = True
 
@@ -76,8 +91,10 @@ class Llama:
                  main_gpu: int = 0, seed: Optional[int] = None, chat_format: Optional[str] = None,
                  last_n_tokens_size: int = 64, use_graphs: bool = True, verbose: bool = True,
                  backend: Optional[str] = None, n_threads: Optional[int] = None, embedding: bool = False,
-                 pooling_type: int = -1, logits_all: bool = False, **kwargs):
+                 pooling_type: int = -1, logits_all: bool = False, type_k: Optional[int] = None,
+                 type_v: Optional[int] = None, **kwargs):
         t0 = time.perf_counter()
+        kv_type = _kv_type(type_k, type_v)
         if not os.path.exists(model_path):
             raise ValueError(f"Model path does not exist: {model_path}")
         self.model_path = model_path
@@ -107,6 +124,11 @@ class Llama:
         self.chat_format, self._formatter = get_formatter(self.metadata, chat_format, bos, eos)
         kind = _select_backend(reader, self.hparams, n_gpu_layers, backend, split_mode, tensor_split)
         self.backend_name = kind
+        if kv_type != "f16" and kind != "hip":
+            raise NotImplementedError(f"type_k / type_v = {kv_type}: the {kind} backend keeps an f16 KV cache "
+                                      "(a Q8_0 cache is served by the hip backend on one GPU)")
+        if kv_type != "f16" and split_mode == "row" and sum(1 for v in (tensor_split or []) if v > 0) > 1:
+            raise NotImplementedError(f"type_k / type_v = {kv_type} is not served under tensor parallelism")
         if self.hparams.arch == ARCH_QWEN3MOE and kind != "reference" and (
                 kind == "layer" or (split_mode == "row" and sum(1 for v in (tensor_split or []) if v > 0) > 1)):
             raise NotImplementedError("qwen3moe: tensor parallelism and the layer split across GPUs are not supported "
@@ -135,7 +157,8 @@ class Llama:
             from ..runtime.hip_backend import HipBackend
             self._backend = HipBackend(model_path, self.hparams, n_ctx=self._n_ctx, n_gpu_layers=n_gpu_layers,
                                        tensor_split=tensor_split, split_mode=split_mode, main_gpu=main_gpu,
-                                       n_batch=n_batch, use_graphs=use_graphs, logits_all=self.logits_all, **kwargs)
+                                       n_batch=n_batch, use_graphs=use_graphs, logits_all=self.logits_all,
+                                       kv_type=kv_type, **kwargs)
         else:
             raise ValueError(f"unknown backend {kind!r}")
         del reader

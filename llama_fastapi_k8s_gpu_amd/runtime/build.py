@@ -28,7 +28,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 EXT = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 
-HIP_SOURCES = ["kernels/gemv.hip", "kernels/gemv_legacy.hip", "kernels/gemv_bf16.hip", "kernels/gemm_w16.hip", "kernels/attention.hip", "kernels/sampler.hip", "kernels/gemm.hip",
+HIP_SOURCES = ["kernels/gemv.hip", "kernels/gemv_legacy.hip", "kernels/gemv_bf16.hip", "kernels/gemm_w16.hip", "kernels/attention.hip", "kernels/attention_q8.hip", "kernels/sampler.hip", "kernels/gemm.hip",
                "kernels/misc.hip", "kernels/bmm.hip",
                "kernels/moe.hip", "kernels/moe_wide.hip", "kernels/p2p_allreduce.hip", "kernels/score.hip", "kernels/score_w16.hip"]
 # Per-source device flags. score.hip is compiled without the packed fp32 instructions (v_pk_add_f32 /
@@ -41,7 +41,8 @@ HIP_SOURCES = ["kernels/gemv.hip", "kernels/gemv_legacy.hip", "kernels/gemv_bf16
 # loop is fp32 FMA pairs, where the flag's cost has not been measured (docs/DESIGN.md, section 8).
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA_FLAGS = {"kernels/score.hip": _NO_PK_F32, "kernels/score_w16.hip": _NO_PK_F32, "kernels/moe_wide.hip": _NO_PK_F32,
-                   "kernels/gemv_bf16.hip": _NO_PK_F32, "kernels/gemm_w16.hip": _NO_PK_F32}
+                   "kernels/gemv_bf16.hip": _NO_PK_F32, "kernels/gemm_w16.hip": _NO_PK_F32,
+                   "kernels/attention_q8.hip": _NO_PK_F32}
 HOST_HIP_SOURCES = ["runtime/engine.cpp", "runtime/p2p.cpp", "runtime/scheduler.cpp", "kernels/bmm_args.cpp",
                     "bindings_hip.cpp"]     # host code against the HIP runtime
 HOST_SOURCES = ["runtime/gguf.cpp", "runtime/repack.cpp", "runtime/tp_channel.cpp"]          # plain C++ (+OpenMP)

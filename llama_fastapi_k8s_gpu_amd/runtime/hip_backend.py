@@ -91,8 +91,10 @@ class HipBackend:
     def __init__(self, model_path: str, hparams, n_ctx: int = 1024, n_gpu_layers: int = -1,
                  tensor_split: Optional[Sequence[float]] = None, split_mode: str = "layer", main_gpu: int = 0,
                  n_batch: int = 512, use_graphs: bool = True, max_batch: int = 1, tp_comm: Optional[str] = None,
-                 device: Optional[int] = None, logits_all: bool = False, **_):
+                 device: Optional[int] = None, logits_all: bool = False, kv_type: str = "f16", **_):
         hip = load_hip()
+        if kv_type not in ("f16", "q8_0"):
+            raise ValueError(f"kv_type={kv_type!r}: the KV cache is 'f16' or 'q8_0'")
         if 0 <= n_gpu_layers < hparams.n_layer:
             raise ValueError(f"n_gpu_layers={n_gpu_layers} < n_layer={hparams.n_layer}: partial offload runs on "
                              "the hybrid backend (backend='hybrid')")
@@ -115,7 +117,8 @@ class HipBackend:
                                  use_graph=use_graphs, tp_rank=rank, tp_size=size, nccl_id=nccl_id,
                                  tensor_split=ts, n_slots=max_batch + 1 if max_batch > 1 else 1, comm=comm,
                                  test_fault=_test_fault() if size > 1 else "",
-                                 scoring=bool(logits_all) and size == 1)
+                                 scoring=bool(logits_all) and size == 1, kv_type=kv_type)
+        self.kv_type = kv_type
         self.n_ctx = n_ctx
         self.n_vocab = int(hparams.n_vocab)
         self.n_batch = min(n_batch, n_ctx)  # the engine's prefill chunk bound (eval_logits rejects T > n_batch)
@@ -303,8 +306,11 @@ class HipBackend:
 
     def load_kv(self, kv, n: int):
         if hasattr(kv, "data_ptr"):
-            if kv.numel() < self.engine.kv_state_bytes(int(n)):
+            need = self.engine.kv_state_bytes(int(n))
+            if kv.numel() < need:
                 raise ValueError("load_kv: device snapshot too small")
+            if self.kv_type != "f16" and kv.numel() != max(1, need):  # (an f16 snapshot is larger, not smaller)
+                raise ValueError(f"load_kv: the snapshot is not one of a kv_type={self.kv_type} cache")
             self.engine.kv_transfer_ptr(kv.data_ptr(), int(n), True)
         else:
             self.engine.kv_load(kv, int(n))
